@@ -461,6 +461,34 @@ def generate_seeds(host, spec, chunk_ids, sizes, seed_of, threads, arena=None, t
     return tg, arena
 
 
+DUMP_MAX_SEEDS = 262144        # 24 result fields + the seed index in float64: 52 MB, under the 64 MB of --dump-outputs
+
+
+def dump_outputs(out_dir, ctx, batches):
+    """--dump-outputs: the result records the timed path left in its resident batches (what a caller downloads), one float64
+    .npy per field (tag, qb, ..., left_score, ..., right_cells; every field is a 32-bit integer, exact in float64).  More than
+    DUMP_MAX_SEEDS seeds: a sample drawn with a fixed generator seed, in order; seed_index.npy holds the seeds' positions."""
+    n = sum(b.n for b in batches)
+    idx = np.arange(n) if n <= DUMP_MAX_SEEDS else np.sort(np.random.default_rng(20240917).choice(n, DUMP_MAX_SEEDS, replace=False))
+    parts, lo = [], 0
+    for b in batches:
+        r = ctx.download(b)
+        parts.append(r[idx[(idx >= lo) & (idx < lo + b.n)] - lo])
+        lo += b.n
+    res = np.concatenate(parts)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"seed_index": idx}
+    for name in res.dtype.names:
+        if res.dtype[name].names:
+            for sub in res.dtype[name].names:
+                arrays[name + "_" + sub] = res[name][sub]
+        else:
+            arrays[name] = res[name]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    return {"dir": out_dir, "seeds": int(len(idx)), "of_seeds": int(n), "files": len(arrays), "dtype": "float64"}
+
+
 def sides_of(tasks):
     return int((tasks["lqlen"] > 0).sum() + (tasks["rqlen"] > 0).sum())
 
@@ -505,6 +533,9 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses device 0 (needs --backend gloo)")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto (batch manager picks per bin), 1 wave-per-task only, 2 force lane bins")
     ap.add_argument("--dry-run", action="store_true", help="launcher check without a GPU: the ranks rendezvous over gloo, count themselves and rank 0 prints the count")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write rank 0's results of the last step as DIR/<field>.npy (float64; a fixed, seeded sample "
+                         "of at most %d seeds)" % DUMP_MAX_SEEDS)
     ap.add_argument("--preset", default=None, choices=sorted(PRESETS),
                     help="BASELINE.json configs[3] / configs[4] as one flag (sets --workload/--scaling/--pool; explicit flags still win)")
     args = ap.parse_args()
@@ -673,6 +704,7 @@ def main():
     step_ms = [float(sum(h[0] for h in hist[i:i + nb])) for i in range(0, len(hist), nb)]
     stage_ms = [float(sum(h[1] for h in hist[i:i + nb])) for i in range(0, len(hist), nb)]
     dp_ms = [a - b for a, b in zip(step_ms, stage_ms)]
+    dumped = dump_outputs(args.dump_outputs, ctx, batches) if args.dump_outputs and rank == 0 else None
     # ---- the same batches, DP kernels alone (what rounds 1-5 timed) ----
     dt_k, kern_ms = None, []
     if args.kernels_only_steps > 0:
@@ -856,6 +888,7 @@ def main():
             "collective_backend": (("rccl" if args.backend == "nccl" else args.backend) if dist is not None else None),
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt_all / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
+            "dumped_outputs": dumped,
             "vs_baseline": None,
             "dtype": "u8 scores in packed u16 VALU ops (v_pk_*_u16: two seeds per lane), range-checked per seed; wider scores run 16-bit rows / int32",
             "data": "synthetic",

@@ -26,6 +26,7 @@ def test_batch_manager_host_logic_under_asan_ubsan(tmp_path):
     hipcc = "/opt/rocm/bin/hipcc"
     inc = ["-I", os.path.join(ROOT, "include")]
     san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    hip_san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=all"]   # host code only
     objs = []
     csrc = os.path.join(ROOT, "bwa-mem-sw_amd", "csrc")
     for name, src, cc in (("ctx", os.path.join(csrc, "bsw_ctx.hip"), "hip"), ("batch", os.path.join(csrc, "bsw_batch.hip"), "hip"),
@@ -37,12 +38,12 @@ def test_batch_manager_host_logic_under_asan_ubsan(tmp_path):
                           ("refbatch", os.path.join(ROOT, "bwa-mem-sw_amd", "csrc", "bsw_refbatch.c"), "c")):
         obj = str(tmp_path / (name + ".o"))
         if cc == "hip":
-            subprocess.check_call([hipcc, "--cuda-host-only", "-x", "hip", "-std=c++17"] + san + inc + ["-c", src, "-o", obj])
+            subprocess.check_call([hipcc, "--cuda-host-only", "-x", "hip", "-std=c++17"] + hip_san + inc + ["-c", src, "-o", obj])
         else:
             subprocess.check_call(["gcc"] + san + inc + ["-c", src, "-o", obj])
         objs.append(obj)
     exe = str(tmp_path / "asan_plan")
-    subprocess.check_call([hipcc, "-fsanitize=address,undefined"] + objs + ["-o", exe, "-lpthread"])
+    subprocess.check_call([hipcc, "-fsanitize=address,undefined", "-fno-gpu-sanitize"] + objs + ["-o", exe, "-lpthread"])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
     assert "asan_plan ok" in out.stdout

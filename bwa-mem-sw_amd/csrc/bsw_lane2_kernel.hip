@@ -143,6 +143,7 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane2_kernel(const bsw_dparams P
             qlen = T.rqlen; tlen = T.rtlen; wlim = T.wlim_r; q_off = T.rq_off; t_off[x] = T.rt_off;
             h0 = T.lqlen > 0 ? (FUSED ? (int)((lsc2 >> (16 * x)) & 0xffffu) : out[ti[x]].left.score) : T.h0;          /* h0 = score after the left ext (:1671) */
         }
+        if (!valid[x]) { qlen = 1; q_off = 0; t_off[x] = 0; }       /* (task 0's record stands in: its lengths may be any class's, up to BSW_MAX_QLEN) */
         has[x] = valid[x] && qlen > 0;
         if (!has[x]) { tlen = 0; qlen = qlen > 0 ? qlen : 1; t_off[x] = 0; }      /* (the target staging reads word t_off + 0 of every lane: a seed without this side has no offset worth reading at) */
         ntw[x] = (tlen + 15) >> 4;

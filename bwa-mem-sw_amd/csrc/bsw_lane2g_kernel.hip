@@ -142,6 +142,7 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane2g_kernel(const bsw_dparams 
             qlen = T.rqlen; tlen = T.rtlen; wlim = T.wlim_r; q_off = T.rq_off; t_off[x] = T.rt_off;
             h0 = T.lqlen > 0 ? (side == 2 ? lsc[x] : out[ti[x]].left.score) : T.h0;          /* h0 = score after the left ext (:1671) */
         }
+        if (!valid[x]) { qlen = 1; q_off = 0; t_off[x] = 0; }       /* (task 0's record stands in: its lengths may be any class's, up to BSW_MAX_QLEN) */
         has[x] = valid[x] && qlen > 0;
         if (!has[x]) { tlen = 0; qlen = qlen > 0 ? qlen : 1; }
         ntw[x] = (tlen + 15) >> 4;

@@ -30,6 +30,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "bsw_device.h"
 
 namespace bsw {
@@ -279,14 +281,30 @@ __global__ __launch_bounds__(64 * WPB) void bsw_long_kernel(const bsw_dparams P,
     }
 }
 
+/* The dynamic-LDS limit is a property of the kernel ON A DEVICE: it is set on every device the kernel is launched on (the
+ * current one), remembered per device only once it has succeeded, and a failure is returned, never cached. */
+template <int VAR, int WPB>
+static hipError_t long_lds_attr()
+{
+    static std::atomic<uint64_t> set_on{0};                            /* bit d: set on device d */
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+    if (bit && (set_on.load(std::memory_order_acquire) & bit)) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bsw_long_kernel<VAR, WPB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) set_on.fetch_or(bit, std::memory_order_release);
+    return e;
+}
+
 /* cols = eh[] columns of the seed class (1 024 < cols <= 8 192); n = seed count (or an upper bound of *n_dev).  Up to 2 048
- * columns four wavefronts share a workgroup's LDS (4 x 2 176 records x 16 B = 136 KB), beyond that a wavefront has it alone. */
+ * columns four wavefronts share a workgroup's LDS (4 x 2 112 records x 16 B = 132 KiB), beyond that a wavefront has it alone. */
 template <int VAR, int WPB>
 static hipError_t launch_long_t(int rec, const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks, const uint32_t *order,
                                 uint32_t n, const uint32_t *n_dev, bsw_result *out, hipStream_t s)
 {
     const size_t lds = (size_t)rec * 16u * (size_t)WPB;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&bsw_long_kernel<VAR, WPB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const hipError_t attr = long_lds_attr<VAR, WPB>();
     if (attr != hipSuccess) return attr;
     uint32_t blocks = (n + (uint32_t)WPB - 1u) / (uint32_t)WPB;
     if (n_dev && blocks > 8192u) blocks = 8192u;                        /* device-side count: stride over the list */

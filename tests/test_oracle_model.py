@@ -74,6 +74,31 @@ def test_full_matrix_dp_agrees_when_nothing_binds(oracle, variant):
         assert a["cells"] == ql * tl
 
 
+@pytest.mark.parametrize("variant", [0, 1])
+def test_full_matrix_dp_agrees_at_long_lengths(oracle, variant):
+    # the long-query kernel's lengths (qlen > 1 024) and scores (> 16 bits): an asymmetric general matrix with matches of
+    # 60 - 90, asymmetric gaps; w >= max(qlen, tlen), zdrop 0 and h0 above every gap path's cost -> nothing binds
+    rng = np.random.default_rng(1025 + variant)
+    m = rng.integers(-40, -1, (5, 5)).astype(np.int8)
+    for i in range(4):
+        m[i, i] = rng.integers(60, 91)
+    m = m.reshape(25)
+    for it in range(2):
+        ql, tl = int(rng.integers(1025, 1101)), int(rng.integers(1025, 1101))
+        t = rng.integers(0, 4, tl)
+        q = np.array([b if rng.random() > 0.05 else rng.integers(0, 5) for b in np.resize(t, ql)]) if it == 0 else rng.integers(0, 5, ql)
+        pen = (6, 1, 4, 2) if it == 0 else (3, 2, 9, 1)
+        h0 = 6000
+        a = oracle.extend2(q, t, m, *pen, 1200, 100000, 0, h0, variant=variant)
+        b = full_dp(q, t, m, *pen, h0, variant=variant)
+        assert b["minH"] > 0
+        if it == 0:
+            assert a["score"] > 65535
+        for k in ("score", "qle", "tle", "gtle", "gscore", "max_off"):
+            assert a[k] == b[k], (it, k, a, b)
+        assert a["cells"] == ql * tl
+
+
 def test_properties(oracle):
     rng = np.random.default_rng(5)
     m = mat()

@@ -11,6 +11,13 @@
  *   Left edge: eh[j] == 0 for every j < beg is an invariant (zero-trimming only passes zeros; columns the band
  *   clamp drops are zeroed explicitly) and the match mask is cleared below beg, so cells left of beg compute to
  *   zero and need no masking — only blocks that hold some lane's `end` run the masked ("edge") body.
+ *   Right edge: eh[j].e == 0 for every j >= end when a row starts.  Induction: the first row's e are all 0; a row stores
+ *   e' only at j < end and {h1, 0} at end; the K8 trim sets end = last non-zero + 2 (or qlen), so the entries it uncovers
+ *   are zero; and the band clamp end <= i + w + 1 only cuts columns no earlier row reached (row i' < i stored at
+ *   j <= i' + w + 1 < i + w + 1).  So the edge body only forces H to 0 at j >= end: E', the stored pair at end ({h1, 0})
+ *   and the non-zero bits follow from it.  The h bytes beyond end are NOT always zero — when the w clip cuts the first
+ *   row short (qlen >= w + 2 and h0 > oe_ins + (w + 1) e_ins) the first row's values h0 - oe_ins - (j - 1) e_ins stay
+ *   there until `end` reaches them, and bwa reads them then — so the edge body keeps the entries beyond end as they are.
  *   Next-row range (K8): non-zero bits of the stored eh entries accumulate in 16-column bit masks.
  * This header is compiled twice: by hipcc into the kernel, and by g++ into the CPU model the tests check against
  * the oracle (tests/lane2_model.cpp) — same source, so the arithmetic is verified without a GPU.
@@ -404,12 +411,16 @@ struct lane2 {
      * subtract are exact on the high byte whatever the low bytes hold (a tie in the high byte is a tie in the
      * score), so eh[j] = {e:8 | h:8} itself serves as "e" without an extraction; only the key and the stored pair
      * need clean bytes, and both take them by byte selection.
-     * EDGE: the block holds some seed's `end` -> writes, the row max and the non-zero bits are masked per half to
-     *       J < end (cells) / J <= end (the eh[end] = {h1, 0} store, :1775).  NQ: some query has an N in this block.
-     * State flows through h1, f (scaled), mk, nz. */
+     * EDGE: the block holds some seed's `end`.  H is forced to 0 at J >= end (one AND per column); with the right-edge
+     *       invariant (header comment) everything else follows unmasked: E' and the stored pairs at J >= end come out as
+     *       bwa's, the row-max key and the non-zero bits read zeros there.  The chain hp carries the MASKED H(i, j-1) (the
+     *       h byte of the stored pair), h1 the last H below `end` (= H(i, end-1), K7's gscore reads it); the store keeps the
+     *       old entry at J > end (J - 1 < end is the previous column's mask).  NQ: some query has an N in this block.
+     * State flows through hp / h1, f (scaled), mk, nz; a dense cell is called with hp and h1 the same variable. */
     template <int J, bool EDGE, bool NQ>
     L2_MFN void cell(uint32_t &P, const uint32_t Wc8, const uint32_t WNc, const uint32_t Bv2s, const uint32_t D2s,
-                           const consts &k, const uint32_t END2, uint32_t &mi_prev, uint32_t &h1, uint32_t &f, uint32_t &mk, uint32_t &nz)
+                           const consts &k, const uint32_t END2, uint32_t &mi_prev, uint32_t &hp, uint32_t &h1, uint32_t &f,
+                           uint32_t &mk, uint32_t &nz)
     {
         /* key and non-zero bit are relative to the 8-column block: 16 distinct SGPR constants in the whole kernel
          * (column-absolute ones would be ~80, all hoisted out of the row loop, and spill) */
@@ -428,39 +439,38 @@ struct lane2 {
         uint32_t M = pk_subs(X, Bv2s);                       /* max(hd + s, 0): e and f are >= 0 anyway */
         if (VM) M &= pk_nzmask(hd);                          /* variant M: a zero H(i-1,j-1) stays zero (only a match could lift it) */
         uint32_t h = pk_max(pk_max(M, e), f);                /* (:1798,1809) */
+        uint32_t mi = 0xffffffffu;
+        if (EDGE) {
+            mi = pk_nzmask(pk_subs_vs(END2, dup16(C)));      /* END2 is relative to the block here: 0xffff where J < end */
+            h1 = bfi(mi, h, h1);                             /* the last H below end */
+            h &= mi;                                         /* H = 0 at J >= end */
+        }
         const uint32_t g = VM ? M : h;                       /* what a gap opens from: h in variant H (:1863,1866), M in variant M */
         const uint32_t tD = pk_subs_vs(g, k.OED2s);
         const uint32_t tI = SYM ? tD : pk_subs_vs(g, k.OEI2s);
         uint32_t en = pk_max(pk_subs_vs(e, k.ED2s), tD);     /* (:1866,1770-1771) */
+        if (EDGE && VM) en &= mi;                            /* (variant M opens gaps from the unmasked M) */
         f = pk_max(pk_subs_vs(f, SYM ? k.ED2s : k.EI2s), tI);   /* (:1863,1780-1781) */
+        const uint32_t key = and_or_vvs(h, k.HI2, JJ);       /* row max of this block, ties -> later j */
+        mk = C ? pk_max(mk, key) : key;
+        const uint32_t np = pack_hi_bytes(en, hp);           /* eh[j] = {e', H(i,j-1)} (:1776); {0, h1} at end, 0 beyond */
+        const uint32_t nb = pk_min_vs(np, k.ONE2);
+        nz = C ? pk_mad_vsv(nb, BIT, nz) : nb;
         if (!EDGE) {
-            const uint32_t key = and_or_vvs(h, k.HI2, JJ);   /* row max of this block, ties -> later j */
-            mk = C ? pk_max(mk, key) : key;
-            const uint32_t np = pack_hi_bytes(en, h1);       /* eh[j] = {e', H(i,j-1)} (:1776) */
-            const uint32_t nb = pk_min_vs(np, k.ONE2);
-            nz = C ? pk_mad_vsv(nb, BIT, nz) : nb;
             P = np;
-            h1 = h;
+            hp = h;                                          /* (the same variable as h1) */
         } else {
-            const uint32_t d = pk_subs_vs(END2, dup16(C));   /* END2 is relative to the block here: non-zero iff J < end */
-            const uint32_t mi = pk_nzmask(d);                /* 0xffff where J < end */
-            const uint32_t mw = mi_prev;                     /* 0xffff where J <= end: J - 1 < end, the previous column's mask */
+            P = bfi(mi_prev, np, P);                         /* J <= end: stored; beyond, bwa leaves the entry alone */
             mi_prev = mi;
-            const uint32_t key = and_or_vvs(h & mi, k.HI2, JJ);
-            mk = C ? pk_max(mk, key) : key;
-            en &= mi;
-            const uint32_t np = pack_hi_bytes(en, h1) & mw;
-            const uint32_t nb = pk_min_vs(np, k.ONE2);
-            nz = C ? pk_mad_vsv(nb, BIT, nz) : nb;
-            P = bfi(mw, np, P);
-            h1 = bfi(mi, h, h1);
+            hp = h;
         }
     }
 
     /* The eight cells of one block.  WN: the N bits of the block's columns in bits 0..7 of each half (NQ only); END /
-     * mi_in: END2 relative to the block and the mask of column j0 - 1 (EDGE only).  On the GPU, with BSW_L2_ASM_BODY, one
-     * hand-scheduled asm statement (bsw_lane2_body_asm.inc) instead of eight cell() calls: same instructions, ordered for
-     * instruction-level parallelism (what the one-wave-per-SIMD kernel needs). */
+     * mi_in: END2 relative to the block and the mask of column j0 - 1 (EDGE only; the masked H(i, j0-1) entering the
+     * block is h1 & mi_in).  On the GPU, with BSW_L2_ASM_BODY, one hand-scheduled asm statement (bsw_lane2_body_asm.inc)
+     * instead of eight cell() calls: same instructions, ordered for instruction-level parallelism (what the
+     * one-wave-per-SIMD kernel needs). */
     template <bool EDGE, bool NQ>
     L2_MFN void block8(uint32_t (&T)[8], const uint32_t Wc, const uint32_t WN, const uint32_t Bv2s, const uint32_t D2s, const consts &k,
                        const uint32_t END, const uint32_t mi_in, uint32_t &h1, uint32_t &f, uint32_t &mk, uint32_t &nz)
@@ -472,7 +482,12 @@ struct lane2 {
         else block8_asm<false, false, VM, SYM>::run(T, Wc, Bv2s, k, h1, f, mk, nz);
 #else
         uint32_t mi_prev = mi_in;
-        sfor<8>([&](auto ci) { cell<decltype(ci)::value, EDGE, NQ>(T[decltype(ci)::value], Wc, WN, Bv2s, D2s, k, END, mi_prev, h1, f, mk, nz); });
+        if (EDGE) {
+            uint32_t hp = h1 & mi_in;
+            sfor<8>([&](auto ci) { cell<decltype(ci)::value, EDGE, NQ>(T[decltype(ci)::value], Wc, WN, Bv2s, D2s, k, END, mi_prev, hp, h1, f, mk, nz); });
+        } else {
+            sfor<8>([&](auto ci) { cell<decltype(ci)::value, EDGE, NQ>(T[decltype(ci)::value], Wc, WN, Bv2s, D2s, k, END, mi_prev, h1, h1, f, mk, nz); });
+        }
 #endif
     }
 
@@ -491,13 +506,15 @@ struct lane2 {
         else block8_seq_asm<false, VM, SYM>::run(T, Wc, Bv2s, k, guard, h1, f, mk, nz);
 #else
         uint32_t mi_prev = mi_in;
+        uint32_t hp = EDGE ? h1 & mi_in : 0u;
+        uint32_t &hpr = EDGE ? hp : h1;
         mk = 0; nz = 0;
         sfor<8>([&](auto ci) {
             constexpr int c = decltype(ci)::value;
             if (EDGE ? c > guard : c < guard) return;
             /* (column 0 of cell() assigns mk / nz instead of folding: fold by hand when it was not the first one run) */
             uint32_t mkc = 0, nzc = 0;
-            cell<c, EDGE, false>(T[c], Wc, 0u, Bv2s, 0u, k, END, mi_prev, h1, f, c ? mk : mkc, c ? nz : nzc);
+            cell<c, EDGE, false>(T[c], Wc, 0u, Bv2s, 0u, k, END, mi_prev, hpr, h1, f, c ? mk : mkc, c ? nz : nzc);
             if (c == 0) { mk = mkc; nz = nzc; }
         });
 #endif

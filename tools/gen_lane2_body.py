@@ -43,6 +43,8 @@ def build(edge, nq, vm, sym):
 
     f, h1, mi_prev = "f_in", "h1_in", "mi_in"
     mk = nz = None
+    # EDGE: hp = the masked H(i, j-1) of the stored pair, h1 = the last H below end (lane2::cell)
+    hp = op("hp", "v_and_b32_e32 {d}, {0}, {1}", "hp_in", ["h1_in", "mi_in"], packed=False) if edge else h1
     for c in range(8):
         P = "P%d" % c
         bit = (1 << c) * 0x00010001
@@ -63,35 +65,31 @@ def build(edge, nq, vm, sym):
             M = op("Mz", "v_and_b32_e32 {d}, {0}, {1}", "Mz%d" % c, [M, z], packed=False)
         me = op("me", "v_pk_max_u16 {d}, {0}, {1}", "me%d" % c, [M, P])
         h = op("h", "v_pk_max_u16 {d}, {0}, {1}", "h%d" % c, [me, f])
+        if edge:
+            # H = 0 at J >= end; the rest of the cell runs unmasked (the right-edge invariant of bsw_lane2_core.h)
+            d = "END" if c == 0 else op("d", "v_pk_sub_u16 {d}, {0}, %s clamp" % jj, "d%d" % c, ["END"])
+            mi = op("mi", "v_pk_mad_u16 {d}, {0}, -1, 0 op_sel_hi:[1,0,0] clamp", "mi%d" % c, [d])
+            h1 = op("h1", "v_bfi_b32 {d}, {0}, {1}, {2}", "h1n%d" % c, [mi, h, h1])
+            h = op("hm", "v_and_b32_e32 {d}, {0}, {1}", "hm%d" % c, [h, mi], packed=False)
         g = M if vm else h
         tD = op("tD", "v_pk_sub_u16 {d}, {0}, %[OED] clamp", "tD%d" % c, [g])
         tI = tD if sym else op("tI", "v_pk_sub_u16 {d}, {0}, %[OEI] clamp", "tI%d" % c, [g])
         es = op("es", "v_pk_sub_u16 {d}, {0}, %[ED] clamp", "es%d" % c, [P])
         en = op("en", "v_pk_max_u16 {d}, {0}, {1}", "en%d" % c, [es, tD])
+        if edge and vm:
+            en = op("enm", "v_and_b32_e32 {d}, {0}, {1}", "enm%d" % c, [en, mi], packed=False)   # (gaps open from the unmasked M)
         fs = op("fs", "v_pk_sub_u16 {d}, {0}, %%[%s] clamp" % ("ED" if sym else "EI"), "fs%d" % c, [f])
         f = op("f", "v_pk_max_u16 {d}, {0}, {1}", "f%d" % c, [fs, tI])
+        key = op("key", "v_and_or_b32 {d}, {0}, {1}, %s" % jj, "key%d" % c, [h, "HI"])
+        mk = key if c == 0 else op("mk", "v_pk_max_u16 {d}, {0}, {1}", "mk%d" % c, [mk, key])
+        np_ = op("np", "v_perm_b32 {d}, {0}, {1}, %[PERM]", "np%d" % c, [en, hp])
+        nb = op("nb", "v_pk_min_u16 {d}, {0}, %[ONE]", "nb%d" % c, [np_])
+        nz = nb if c == 0 else op("nz", "v_lshl_or_b32 {d}, {0}, %d, {1}" % c, "nz%d" % c, [nb, nz])
         if not edge:
-            key = op("key", "v_and_or_b32 {d}, {0}, {1}, %s" % jj, "key%d" % c, [h, "HI"])
-            mk = key if c == 0 else op("mk", "v_pk_max_u16 {d}, {0}, {1}", "mk%d" % c, [mk, key])
-            np_ = op("np", "v_perm_b32 {d}, {0}, {1}, %[PERM]", "np%d" % c, [en, h1])
-            nb = op("nb", "v_pk_min_u16 {d}, {0}, %[ONE]", "nb%d" % c, [np_])
-            nz = nb if c == 0 else op("nz", "v_lshl_or_b32 {d}, {0}, %d, {1}" % c, "nz%d" % c, [nb, nz])
-            newP, h1 = np_, h
+            newP, h1, hp = np_, h, h
         else:
-            d = "END" if c == 0 else op("d", "v_pk_sub_u16 {d}, {0}, %s clamp" % jj, "d%d" % c, ["END"])
-            mi = op("mi", "v_pk_mad_u16 {d}, {0}, -1, 0 op_sel_hi:[1,0,0] clamp", "mi%d" % c, [d])
-            mw = mi_prev
-            mi_prev = mi
-            hm = op("hm", "v_and_b32_e32 {d}, {0}, {1}", "hm%d" % c, [h, mi], packed=False)
-            key = op("key", "v_and_or_b32 {d}, {0}, {1}, %s" % jj, "key%d" % c, [hm, "HI"])
-            mk = key if c == 0 else op("mk", "v_pk_max_u16 {d}, {0}, {1}", "mk%d" % c, [mk, key])
-            enm = op("enm", "v_and_b32_e32 {d}, {0}, {1}", "enm%d" % c, [en, mi], packed=False)
-            np0 = op("np0", "v_perm_b32 {d}, {0}, {1}, %[PERM]", "npr%d" % c, [enm, h1])
-            np_ = op("np", "v_and_b32_e32 {d}, {0}, {1}", "np%d" % c, [np0, mw], packed=False)
-            nb = op("nb", "v_pk_min_u16 {d}, {0}, %[ONE]", "nb%d" % c, [np_])
-            nz = nb if c == 0 else op("nz", "v_lshl_or_b32 {d}, {0}, %d, {1}" % c, "nz%d" % c, [nb, nz])
-            newP = op("Pn", "v_bfi_b32 {d}, {0}, {1}, {2}", "Pn%d" % c, [mw, np_, P])
-            h1 = op("h1", "v_bfi_b32 {d}, {0}, {1}, {2}", "h1n%d" % c, [mi, h, h1])
+            newP = op("Pn", "v_bfi_b32 {d}, {0}, {1}, {2}", "Pn%d" % c, [mi_prev, np_, P])   # J > end: the entry stays
+            mi_prev, hp = mi, h
         ops[-1].__dict__.setdefault("x", None)
         # remember which SSA value becomes the new P of this column
         build.newP[c] = newP
@@ -291,6 +289,12 @@ def emit_seq(edge, vm, sym):
     lines, ntmp_max = [], 0
     lines.append("v_mov_b32_e32 %[mk], 0")
     lines.append("v_mov_b32_e32 %[nz], 0")
+    # (edge) the column masks and the masked H(i, j-1) alternate between two registers each (column c writes MI<c&1>,
+    # HP<c&1> and reads the other one): no moves between the columns; MI1 enters as mi_in, HP1 as h1 & mi_in
+    MI = lambda c: "%%[MI%d]" % (c & 1)
+    HP = lambda c: "%%[HP%d]" % (c & 1)
+    if edge:
+        lines.append("v_and_b32_e32 %s, %%[h1], %s" % (HP(1), MI(1)))
     for c in range(8):
         if edge and c:
             lines += ["s_cmp_gt_i32 %d, %%[G]" % c, "s_cbranch_scc1 9f"]           # c > last: done
@@ -301,7 +305,7 @@ def emit_seq(edge, vm, sym):
         jj = "0" if c == 0 else "%%[JJ%d]" % c
         T = lambda i: "%%[T%d]" % i
         col = []
-        # (temporaries: T0 t/X/M/h-chain, T1 hd, T2 tD, T3 es/en, T4 fs/nb, T5 key (tI before it), T6 edge mask)
+        # (temporaries: T0 t/X/M/h-chain, T1 hd, T2 tD, T3 es/en, T4 fs/nb, T5 key (tI before it); edge: MI / HP above)
         # One column is a serial chain (hd -> X -> M -> me -> h -> tD -> en); what does not depend on it is placed INTO its
         # gaps (a packed result read by the next instruction costs a wait state, which at one wave per SIMD is an issue slot)
         col.append("v_and_b32_e32 %s, 0x%x, %%[Wc]" % (T(0), bit))
@@ -310,12 +314,12 @@ def emit_seq(edge, vm, sym):
         col.append("v_pk_mad_u16 %s, %s, %%[MC%d], %s" % (T(0), T(0), c, T(1)))
         if edge:
             if c:
-                col.append("v_pk_sub_u16 %s, %%[END], %s clamp" % (T(6), jj))
+                col.append("v_pk_sub_u16 %s, %%[END], %s clamp" % (MI(c), jj))
         else:
             col.append("v_pk_sub_u16 %s, %%[f], %%[%s] clamp" % (T(4), "ED" if sym else "EI"))      # fs
         col.append("v_pk_sub_u16 %s, %s, %%[B] clamp" % (T(0), T(0)))                                  # M
         if edge:
-            col.append("v_pk_mad_u16 %s, %s, -1, 0 op_sel_hi:[1,0,0] clamp" % (T(6), T(6) if c else "%[END]"))   # mi
+            col.append("v_pk_mad_u16 %s, %s, -1, 0 op_sel_hi:[1,0,0] clamp" % (MI(c), MI(c) if c else "%[END]"))   # mi
         if vm:
             col.append("v_pk_mad_u16 %s, %s, -1, 0 op_sel_hi:[1,0,0] clamp" % (T(1), T(1)))
             if edge:
@@ -328,10 +332,16 @@ def emit_seq(edge, vm, sym):
             col.append("v_pk_sub_u16 %s, %%[f], %%[%s] clamp" % (T(4), "ED" if sym else "EI"))      # fs
         col.append("v_pk_max_u16 %s, %s, %s" % (T(0), T(0), P))                                        # me
         col.append("v_pk_max_u16 %s, %s, %%[f]" % (T(0), T(0)))                                        # h
+        if edge:
+            col.append("v_bfi_b32 %%[h1], %s, %s, %%[h1]" % (MI(c), T(0)))                             # the last H below end
+            col.append("v_and_b32_e32 %s, %s, %s" % (HP(c), T(0), MI(c)))                              # H = 0 at J >= end
+            T0h = HP(c)
+        else:
+            T0h = T(0)
         if not vm:
-            col.append("v_pk_sub_u16 %s, %s, %%[OED] clamp" % (T(2), T(0)))
+            col.append("v_pk_sub_u16 %s, %s, %%[OED] clamp" % (T(2), T0h))
             if not sym:
-                col.append("v_pk_sub_u16 %s, %s, %%[OEI] clamp" % (T(5), T(0)))
+                col.append("v_pk_sub_u16 %s, %s, %%[OEI] clamp" % (T(5), T0h))
         if not edge:
             if sym:
                 col.append("v_mov_b32_e32 %s, %%[h1]" % T(6))                                          # H(i,j-1) for the stored pair
@@ -348,23 +358,17 @@ def emit_seq(edge, vm, sym):
             col.append("v_pk_min_u16 %s, %s, %%[ONE]" % (T(4), P))
             col.append("v_lshl_or_b32 %%[nz], %s, %d, %%[nz]" % (T(4), c))
         else:
-            # T6 = mi (c < end), %[mi] = mw (c <= end) from the previous column
-            if sym:
-                col.append("v_and_b32_e32 %s, %s, %s" % (T(5), T(0), T(6)))                             # h & mi
+            # MI(c) = mi (c < end), MI(c - 1) = mw (c <= end); HP(c) = masked h, HP(c - 1) = the previous column's
             col.append("v_pk_max_u16 %s, %s, %s" % (T(3), T(3), T(2)))                                 # en
             col.append("v_pk_max_u16 %%[f], %s, %s" % (T(4), T(2) if sym else T(5)))                   # f
-            if not sym:
-                col.append("v_and_b32_e32 %s, %s, %s" % (T(5), T(0), T(6)))                             # h & mi (T5 held tI until f)
-            col.append("v_and_or_b32 %s, %s, %%[HI], %s" % (T(5), T(5), jj))                           # key
-            col.append("v_and_b32_e32 %s, %s, %s" % (T(3), T(3), T(6)))                                 # en & mi
+            if vm:
+                col.append("v_and_b32_e32 %s, %s, %s" % (T(3), T(3), MI(c)))                            # en & mi (gaps open from M)
+            col.append("v_and_or_b32 %s, %s, %%[HI], %s" % (T(5), HP(c), jj))                          # key
+            col.append("v_perm_b32 %s, %s, %s, %%[PERM]" % (T(3), T(3), HP(c - 1)))                    # {e', H(i, j-1)}
             col.append("v_pk_max_u16 %%[mk], %%[mk], %s" % T(5))
-            col.append("v_perm_b32 %s, %s, %%[h1], %%[PERM]" % (T(3), T(3)))
-            col.append("v_bfi_b32 %%[h1], %s, %s, %%[h1]" % (T(6), T(0)))
-            col.append("v_and_b32_e32 %s, %s, %%[mi]" % (T(3), T(3)))
             col.append("v_pk_min_u16 %s, %s, %%[ONE]" % (T(4), T(3)))
-            col.append("v_bfi_b32 %s, %%[mi], %s, %s" % (P, T(3), P))
+            col.append("v_bfi_b32 %s, %s, %s, %s" % (P, MI(c - 1), T(3), P))                           # J > end: the entry stays
             col.append("v_lshl_or_b32 %%[nz], %s, %d, %%[nz]" % (T(4), c))
-            col.append("v_mov_b32_e32 %%[mi], %s" % T(6))
         lines += [l for l in col if l != "s_nop 0"]
         if not edge and c < 7:
             lines.append("%d:" % (10 + c))
@@ -391,14 +395,14 @@ def emit_seq(edge, vm, sym):
                 out2.append("s_nop 0")
         out2.append(l)
     lines = on_grid(out2)
-    ntmp = 7
+    ntmp = 6 if edge else 7
     sig = ["uint32_t (&P)[8]", "uint32_t Wc", "uint32_t B", "const consts &k"]
     if edge:
         sig += ["uint32_t END", "uint32_t mi_in"]
     sig += ["int guard", "uint32_t &h1", "uint32_t &f", "uint32_t &mk", "uint32_t &nz"]
     outs_c = ['[P%d] "+v"(P[%d])' % (c, c) for c in range(8)] + ['[h1] "+v"(h1)', '[f] "+v"(f)', '[mk] "=&v"(mk)', '[nz] "=&v"(nz)']
     if edge:
-        outs_c += ['[mi] "+v"(mi)']
+        outs_c += ['[MI0] "=&v"(mi0)', '[MI1] "+v"(mi1)', '[HP0] "=&v"(hp0)', '[HP1] "=&v"(hp1)']
     outs_c += ['[T%d] "=&v"(t%d)' % (i, i) for i in range(ntmp)]
     ins_c = ['[Wc] "v"(Wc)', '[B] "v"(B)', '[HI] "v"(k.HI2)', '[G] "s"(guard)']
     if edge:
@@ -413,7 +417,7 @@ def emit_seq(edge, vm, sym):
     body.append("{")
     body.append("    uint32_t %s;" % ", ".join("t%d" % i for i in range(ntmp)))
     if edge:
-        body.append("    uint32_t mi = mi_in;")
+        body.append("    uint32_t mi0, mi1 = mi_in, hp0, hp1;")
     body.append("    asm volatile(")
     for i, l in enumerate(lines):
         body.append("        " + c_string(l, i == len(lines) - 1))

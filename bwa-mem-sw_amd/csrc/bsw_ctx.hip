@@ -389,7 +389,7 @@ BSW_LOCAL int check_params(errs &e, const bsw_params *p, bsw_dparams *dp)
     if (p->e_del < 1 || p->e_ins < 1 || p->o_del < 0 || p->o_ins < 0)
         return fail(e, BSW_E_INVAL, "need e_del,e_ins >= 1 and o_del,o_ins >= 0");
     if (p->w < 0 || p->w > (1 << 20) || p->max_band_try > 8) return fail(e, BSW_E_INVAL, "band out of range");
-    if (p->variant != BSW_VARIANT_H && p->variant != BSW_VARIANT_M) return fail(e, BSW_E_INVAL, "bad variant");
+    if (p->variant != BSW_VARIANT_H && p->variant != BSW_VARIANT_M && p->variant != BSW_VARIANT_RTL) return fail(e, BSW_E_INVAL, "bad variant");
     if (p->o_del + p->e_del > 4096 || p->o_ins + p->e_ins > 4096) return fail(e, BSW_E_LIMIT, "gap penalties too large");
     memset(dp, 0, sizeof(*dp));
     memcpy(dp->mat, p->mat, 25);

@@ -83,7 +83,7 @@ __device__ __forceinline__ uint32_t eh_put(uint32_t Pw, const int J, const uint3
 
 /* One DP cell of column J for every lane whose [beg,end) contains J (EDGE) or for all live lanes (dense).
  * Pw is the VGPR holding eh[J]: B8 -> byte pair at bit (J&1)*16, else the whole word.
- * Returns true when the stored eh[J] is non-zero (for the next-row trimming, K8).
+ * Returns, for the next-row trimming (K8), true when the stored eh[J] is non-zero (H, M) or when its h is zero (RTL).
  * NQ: some lane of the wave has an N in this block of the query -> rnw marks those columns and they
  * score k.vn whatever the target base is (mat[.][4], sw_pe_array_sw_extend.v:1915-1940). */
 template <int VAR, bool SYM, bool EDGE, bool B8, bool NQ>
@@ -117,8 +117,9 @@ __device__ __forceinline__ bool lane_cell(uint32_t &Pw, const int J, const uint3
         f = max(max(f - k.e_ins, tI), 0);                             /* (:1863,1780-1781)              */
         const uint32_t np = ((uint32_t)en << HB) | (uint32_t)h1;      /* eh[j] = {e', H(i,j-1)} (:1776) */
         Pw = eh_put<B8>(Pw, J, np);
+        if (VAR == BSW_VARIANT_RTL) nz = h1 == 0;                     /* (:1790: the zero test is on h alone) */
         h1 = h;
-        nz = np != 0;
+        if (VAR != BSW_VARIANT_RTL) nz = np != 0;
     }
     return nz;
 }
@@ -234,15 +235,17 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane_kernel(const bsw_dparams P,
 #pragma unroll
             for (int wd = 0; wd < NW; ++wd)                            /* rm: 1 where q_j == t_i (and neither is N) */
                 rm[wd] = (lds_q[wv][3 * wd][lane] ^ n0) & (lds_q[wv][3 * wd + 1][lane] ^ n1) & tn & ~lds_q[wv][3 * wd + 2][lane];
-            int h1 = beg == 0 ? max(h0 - (o_del + e_del * (i + 1)), 0) : 0;
+            /* RTL: column 0 on every row, whatever beg is (:1795-1796,1835,849) */
+            int h1 = (VAR == BSW_VARIANT_RTL || beg == 0) ? max(h0 - (o_del + e_del * (i + 1)), 0) : 0;
             /* Row max key and first/last non-zero column are kept per 64-column group, relative to the
              * group: VOP3 forms take no 32-bit literal on gfx9, so absolute column numbers > 64 would
              * each occupy a VGPR.  The groups are folded once per row. */
             constexpr int NG = (QMAX + 63) / 64;
             constexpr int NONE = 1 << 20;
             int f = 0, mkg[NG], fnzg[NG], lnzg[NG];
+            uint64_t zmg[NG];                                          /* RTL: bit J & 63 = eh[J].h written zero inside [beg, end] */
 #pragma unroll
-            for (int g = 0; g < NG; ++g) { mkg[g] = -NONE; fnzg[g] = NONE; lnzg[g] = -NONE; }
+            for (int g = 0; g < NG; ++g) { mkg[g] = -NONE; fnzg[g] = NONE; lnzg[g] = -NONE; zmg[g] = 0; }
             cells += (unsigned)len;
             static_for<QB>([&](auto blki) {
                 constexpr int j0 = decltype(blki)::value * 8, g = j0 >> 6;
@@ -275,6 +278,15 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane_kernel(const bsw_dparams P,
                         });
                     }
                 }
+                if (VAR == BSW_VARIANT_RTL) {                          /* zero-h mask of the group (K8, RTL) */
+                    uint32_t zb = 0;
+                    static_for<8>([&](auto ci) {
+                        constexpr int c = decltype(ci)::value;
+                        zb |= nz[c] ? (1u << c) : 0u;
+                    });
+                    zmg[g] |= (uint64_t)zb << (j0 & 63);
+                    return;
+                }
                 /* first / last non-zero eh entry (K8) from the 8 compare masks of the block */
                 int fb = NONE;
                 static_for<8>([&](auto ci) {
@@ -291,8 +303,10 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane_kernel(const bsw_dparams P,
 #pragma unroll
             for (int g = 1; g < NG; ++g) {
                 mk = max(mk, mkg[g] + 64 * g);
-                fnz = min(fnz, fnzg[g] + 64 * g);
-                lnz = max(lnz, lnzg[g] + 64 * g);
+                if (VAR != BSW_VARIANT_RTL) {
+                    fnz = min(fnz, fnzg[g] + 64 * g);
+                    lnz = max(lnz, lnzg[g] + 64 * g);
+                }
             }
             /* K7 row tail */
             if (max(beg, end) == qlen) {                              /* ties -> later i (:1829-1833) */
@@ -309,11 +323,30 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane_kernel(const bsw_dparams P,
                 const int pen = di > dj ? (di - dj) * e_del : (dj - di) * k.e_ins;
                 stop = stop || (mx - m - pen > zdrop);
             }
-            /* K8 next-row range (CPU semantics) */
-            const int nbeg = fnz < end ? fnz : end;
-            const int last = h1 != 0 ? end : (lnz >= 0 ? lnz : nbeg - 1);
-            beg = nbeg;
-            end = min(last + 2, qlen);
+            if (VAR == BSW_VARIANT_RTL) {
+                /* K8, RTL (:1767-1769,1779,1790,1872): the run of non-zero eh[].h around mj.  beg = 1 + the highest zero in
+                 * [beg, mj] (else beg), end = the lowest zero in [mj + 2, end] (else end + 1; the next row's K3 clamps it).
+                 * Bits outside [beg, end] are never set; eh[end] = {0, h1} is folded in here. */
+                int zlo = -1, zhi = NONE;
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    uint64_t z = zmg[g];
+                    z |= (h1 == 0 && (end >> 6) == g) ? 1ull << (end & 63) : 0ull;
+                    const int dl = mj - 64 * g, dh = mj + 2 - 64 * g;     /* keep bits <= dl, bits >= dh */
+                    const uint64_t zl = dl < 0 ? 0ull : dl >= 63 ? z : z & ((2ull << dl) - 1ull);
+                    const uint64_t zh = dh > 63 ? 0ull : dh <= 0 ? z : z & ~((1ull << dh) - 1ull);
+                    zlo = zl ? 64 * g + 63 - (int)__builtin_clzll(zl) : zlo;
+                    zhi = (zh && zhi == NONE) ? 64 * g + (int)__builtin_ctzll(zh) : zhi;
+                }
+                beg = zlo >= 0 ? zlo + 1 : beg;
+                end = zhi != NONE ? zhi : end + 1;
+            } else {
+                /* K8 next-row range (CPU semantics) */
+                const int nbeg = fnz < end ? fnz : end;
+                const int last = h1 != 0 ? end : (lnz >= 0 ? lnz : nbeg - 1);
+                beg = nbeg;
+                end = min(last + 2, qlen);
+            }
             alive = !stop;
         }
     }
@@ -372,9 +405,14 @@ static hipError_t launch_lane_qb(int variant, bool sym, const bsw_dparams &P, in
     if (variant == BSW_VARIANT_M) {
         if (sym) hipLaunchKernelGGL((bsw_lane_kernel<QB, BSW_VARIANT_M, true, B8, WPS>), grid, block, 0, s, P, side, seq, tasks, order, n, out);
         else hipLaunchKernelGGL((bsw_lane_kernel<QB, BSW_VARIANT_M, false, B8, WPS>), grid, block, 0, s, P, side, seq, tasks, order, n, out);
-    } else {
+    } else if (variant == BSW_VARIANT_H) {
         if (sym) hipLaunchKernelGGL((bsw_lane_kernel<QB, BSW_VARIANT_H, true, B8, WPS>), grid, block, 0, s, P, side, seq, tasks, order, n, out);
         else hipLaunchKernelGGL((bsw_lane_kernel<QB, BSW_VARIANT_H, false, B8, WPS>), grid, block, 0, s, P, side, seq, tasks, order, n, out);
+    } else if (variant == BSW_VARIANT_RTL) {
+        if (sym) hipLaunchKernelGGL((bsw_lane_kernel<QB, BSW_VARIANT_RTL, true, B8, WPS>), grid, block, 0, s, P, side, seq, tasks, order, n, out);
+        else hipLaunchKernelGGL((bsw_lane_kernel<QB, BSW_VARIANT_RTL, false, B8, WPS>), grid, block, 0, s, P, side, seq, tasks, order, n, out);
+    } else {
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

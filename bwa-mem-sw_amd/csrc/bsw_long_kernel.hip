@@ -137,8 +137,8 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
             /* K3 band clamp (:1803,1894-1897,1842,1898) */
             beg = max(beg, i - w);
             end = min(min(end, i + w + 1), qlen);
-            /* K4 column 0, CPU semantics (:1795-1796,1835; Q4 avoided) */
-            const int h1_init = beg == 0 ? max(h0 - (o_del + e_del * (i + 1)), 0) : 0;
+            /* K4 column 0 (:1795-1796,1835): CPU semantics (Q4 avoided) for H and M; every row for RTL (:849) */
+            const int h1_init = (VAR == BSW_VARIANT_RTL || beg == 0) ? max(h0 - (o_del + e_del * (i + 1)), 0) : 0;
             cells += (unsigned)max(end - beg, 0);
 
             /* ---- the row's chunks: columns beg + 64 c + lane, c = 0 .. (end - beg) / 64 (the entry eh[end] included) ---- */
@@ -205,6 +205,26 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
                 } else {
                     if (mx - mrow - ((mj - max_j) - (i - max_i)) * e_ins > P.zdrop) break;
                 }
+            }
+            if (VAR == BSW_VARIANT_RTL) {
+                /* K8, RTL (:1767-1769,1779,1790,1872): the run of non-zero eh[].h around mj, found by a second pass over the
+                 * row's records outward from mj, 64 columns per step, until a zero h turns up (usually the first step: the
+                 * run is about as wide as the live band).  beg = 1 + the highest zero in [beg, mj] (else beg), end = the
+                 * lowest zero in [mj + 2, end] (else end + 1: the next row's K3 clamps it). */
+                int nb = beg, ne = end + 1;
+                for (int hi = mj; hi >= beg; hi -= 64) {
+                    const int j = hi - lane;
+                    const uint64_t zb = __builtin_amdgcn_ballot_w64(j >= beg && row[j].x == 0u);
+                    if (zb) { nb = hi - (int)__builtin_ctzll(zb) + 1; break; }
+                }
+                for (int lo = mj + 2; lo <= end; lo += 64) {
+                    const int j = lo + lane;
+                    const uint64_t zb = __builtin_amdgcn_ballot_w64(j <= end && row[j].x == 0u);
+                    if (zb) { ne = lo + (int)__builtin_ctzll(zb); break; }
+                }
+                beg = nb;
+                end = ne;
+                continue;
             }
             /* K8 next-row range, CPU semantics (Q5 avoided) */
             const int nbeg = first_nz < end ? first_nz : end;
@@ -317,9 +337,13 @@ hipError_t launch_long(int cols, int variant, const bsw_dparams &P, const uint64
 {
     if (n == 0) return hipSuccess;
     const int rec = ((cols + 63) & ~63) + 64;                          /* LDS records per wave */
-    const bool m = variant == BSW_VARIANT_M;
-    if (cols <= 2048) return m ? launch_long_t<BSW_VARIANT_M, 4>(rec, P, seq, tasks, order, n, n_dev, out, s) : launch_long_t<BSW_VARIANT_H, 4>(rec, P, seq, tasks, order, n, n_dev, out, s);
-    return m ? launch_long_t<BSW_VARIANT_M, 1>(rec, P, seq, tasks, order, n, n_dev, out, s) : launch_long_t<BSW_VARIANT_H, 1>(rec, P, seq, tasks, order, n, n_dev, out, s);
+    const bool four = cols <= 2048;
+    switch (variant) {
+    case BSW_VARIANT_H: return four ? launch_long_t<BSW_VARIANT_H, 4>(rec, P, seq, tasks, order, n, n_dev, out, s) : launch_long_t<BSW_VARIANT_H, 1>(rec, P, seq, tasks, order, n, n_dev, out, s);
+    case BSW_VARIANT_M: return four ? launch_long_t<BSW_VARIANT_M, 4>(rec, P, seq, tasks, order, n, n_dev, out, s) : launch_long_t<BSW_VARIANT_M, 1>(rec, P, seq, tasks, order, n, n_dev, out, s);
+    case BSW_VARIANT_RTL: return four ? launch_long_t<BSW_VARIANT_RTL, 4>(rec, P, seq, tasks, order, n, n_dev, out, s) : launch_long_t<BSW_VARIANT_RTL, 1>(rec, P, seq, tasks, order, n, n_dev, out, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace bsw

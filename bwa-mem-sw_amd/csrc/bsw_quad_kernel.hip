@@ -86,6 +86,13 @@ __device__ __forceinline__ int shr1_max(int p, int b)
     asm volatile("v_mov_b32 %0, %2\n\tv_max_i32_dpp %0, %1, %2 row_shr:1 row_mask:0xf bank_mask:0xf" : "=&v"(d) : "v"(p), "v"(b));
     return d;
 }
+/* two maxima over the 16 lanes of a DPP row, the result in every lane of the row (row_max4's chains, two of them) */
+__device__ __forceinline__ void row_max2(int &a, int &b)
+{
+#define BSW_Q_ROR(n) "v_max_i32_dpp %0, %0, %0 row_ror:" #n " row_mask:0xf bank_mask:0xf\n\tv_max_i32_dpp %1, %1, %1 row_ror:" #n " row_mask:0xf bank_mask:0xf\n\t"
+    asm volatile("s_nop 1\n\t" BSW_Q_ROR(8) "s_nop 1\n\t" BSW_Q_ROR(4) "s_nop 1\n\t" BSW_Q_ROR(2) "s_nop 1\n\t" BSW_Q_ROR(1) "s_nop 0" : "+v"(a), "+v"(b));
+#undef BSW_Q_ROR
+}
 /* max(p of the row's lane 15, b) in every lane */
 __device__ __forceinline__ int bcast15_max(int p, int b)
 {
@@ -350,8 +357,8 @@ __global__ __launch_bounds__(256, quad_wps<S>()) void bsw_quad_kernel(const bsw_
             const int tb = (int)((tw >> ((i & 7) * 4)) & 7u);
             const bool tn = tb >= 4;
             const uint32_t sh = (uint32_t)(tb & 3) * 8u;
-            /* K4 column 0, CPU semantics (:1795-1796,1835; Q4 avoided) */
-            const int h1_init = beg == 0 ? max(h0 - (o_del + __mul24(e_del, i + 1)), 0) : 0;   /* (e_del <= 4096, i < 65536) */
+            /* K4 column 0 (:1795-1796,1835): CPU semantics (Q4 avoided) for H and M; every row for RTL (:849) */
+            const int h1_init = (VAR == BSW_VARIANT_RTL || beg == 0) ? max(h0 - (o_del + __mul24(e_del, i + 1)), 0) : 0;   /* (e_del <= 4096, i < 65536) */
             cells += (unsigned)max(end - beg, 0);
             const int rel = l2 - beg, span_e = end - beg;
             const unsigned span_in = (unsigned)max(span_e, 0), span_wr = (unsigned)max(span_e + 1, 0);
@@ -359,7 +366,8 @@ __global__ __launch_bounds__(256, quad_wps<S>()) void bsw_quad_kernel(const bsw_
             int Bm1 = NEGQ;                           /* f entering the stripe, minus 2 e_ins; nothing enters the first one */
             int h31 = 0;                              /* H(i, 32c - 1): the previous stripe's last column */
             int bestv = -1, bestk = 0, hl = -1;       /* bestk = 2 c + (second column) */
-            uint32_t nzb = 0;                         /* bit 2 c + k: this lane's eh[] entry of stripe c, column k, is non-zero (inside [beg, end]) */
+            uint32_t nzb = 0;                         /* bit 2 c + k: this lane's eh[] entry of stripe c, column k, is non-zero (inside [beg, end]);
+                                                         RTL: its h is zero */
             /* one stripe.  INT: every column of the stripe lies strictly inside every live seed's range — no masks.
              * TNV: some live seed's target base is an N this row (its scores come from the matrix's N row). */
             const auto stripe = [&](auto ci, auto intv, auto tnv) {
@@ -410,7 +418,8 @@ __global__ __launch_bounds__(256, quad_wps<S>()) void bsw_quad_kernel(const bsw_
                     hl = jend1 ? xb : hl;
                 }
                 Xa[c] = xa; Xb[c] = xb; Ea[c] = ea; Eb[c] = eb;
-                const bool nz0 = wr0 && ((xa | ea) != 0), nz1 = wr1 && ((xb | eb) != 0);
+                const bool nz0 = VAR == BSW_VARIANT_RTL ? wr0 && xa == 0 : wr0 && ((xa | ea) != 0);      /* (RTL: :1790) */
+                const bool nz1 = VAR == BSW_VARIANT_RTL ? wr1 && xb == 0 : wr1 && ((xb | eb) != 0);
                 nzb |= (nz0 ? (1u << (2 * c)) : 0u) | (nz1 ? (2u << (2 * c)) : 0u);
             };
             using no_t = std::integral_constant<bool, false>;
@@ -431,8 +440,8 @@ __global__ __launch_bounds__(256, quad_wps<S>()) void bsw_quad_kernel(const bsw_
             /* column of code k = 2 c + (second column): 32 c + 2 l + (k & 1) = 16 k - 15 (k & 1) + 2 l */
             const auto col_of = [&](int kcode) { return 16 * kcode - 15 * (kcode & 1) + l2; };
             int key = bestv < 0 ? -1 : ((bestv << BSW_KEY_BITS) | col_of(bestk));
-            int nfz = nzb ? -col_of(__builtin_ctz(nzb)) : INT_MIN;
-            int lz = nzb ? col_of(31 - __builtin_clz(nzb)) : -1;
+            int nfz = VAR == BSW_VARIANT_RTL ? 0 : nzb ? -col_of(__builtin_ctz(nzb)) : INT_MIN;
+            int lz = VAR == BSW_VARIANT_RTL ? 0 : nzb ? col_of(31 - __builtin_clz(nzb)) : -1;
             row_max4(key, nfz, lz, hl);
             const int mrow = key < 0 ? 0 : (key >> BSW_KEY_BITS);
             const int mj = key < 0 ? -1 : (key & ((1 << BSW_KEY_BITS) - 1));
@@ -452,19 +461,38 @@ __global__ __launch_bounds__(256, quad_wps<S>()) void bsw_quad_kernel(const bsw_
             max_i = gt ? i : max_i;
             max_j = gt ? mj : max_j;
             mx = gt ? mrow : mx;
-            /* K8 next-row range, CPU semantics (Q5 avoided) */
-            const int nbeg = first_nz < end ? first_nz : end;
-            const int last = last_nz >= 0 ? last_nz : nbeg - 1;
-            beg = nbeg;
-            end = min(last + 2, qlen);
+            if (VAR == BSW_VARIANT_RTL) {
+                /* K8, RTL (:1767-1769,1779,1872): the run of non-zero eh[].h around mj, known only now.  The lane's codes k
+                 * ascend with the column, so its zeros <= mj are the codes below the count of its columns <= mj
+                 * (32 c + 2 l + (k & 1) <= mj), its zeros >= mj + 2 the codes from the count of its columns <= mj + 1. */
+                const auto ncols_upto = [&](int jm) {          /* codes k of this lane with col_of(k) <= jm, at most 2 S */
+                    const int d = jm - l2;
+                    return d < 0 ? 0 : min(2 * (d >> 5) + ((d & 31) >= 1 ? 2 : 1), 2 * S);
+                };
+                const int nl = ncols_upto(mj), nh = ncols_upto(mj + 1);
+                const uint32_t zl = nzb & ((1u << nl) - 1u), zh = nzb & ~((1u << nh) - 1u);
+                int zlo = zl ? col_of(31 - __builtin_clz(zl)) : -1;
+                int nzhi = zh ? -col_of(__builtin_ctz(zh)) : INT_MIN;
+                row_max2(zlo, nzhi);
+                beg = zlo >= 0 ? zlo + 1 : beg;
+                end = nzhi != INT_MIN ? -nzhi : end + 1;
+            } else {
+                /* K8 next-row range, CPU semantics (Q5 avoided) */
+                const int nbeg = first_nz < end ? first_nz : end;
+                const int last = last_nz >= 0 ? last_nz : nbeg - 1;
+                beg = nbeg;
+                end = min(last + 2, qlen);
+            }
             ++i;
         }
 
     }
 }
 
-template <int S>
-static hipError_t launch_qc(int variant, const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks,
+/* The file is compiled twice (Makefile): as itself (variants H and M, launch_quad) and with -DBSW_QUAD_RTL_TU (variant RTL,
+ * launch_quad_rtl), so that each object holds the instantiations its audits expect (tests/test_isa_audit.py). */
+template <int S, int VAR>
+static hipError_t launch_qv(const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks,
                             const uint32_t *order, uint32_t n, const uint32_t *n_dev, uint32_t *next_slot, bsw_result *out, hipStream_t s)
 {
     /* one row of lanes per seed up to a grid that fills the machine several times over; beyond that the rows refill
@@ -472,23 +500,43 @@ static hipError_t launch_qc(int variant, const bsw_dparams &P, const uint64_t *s
     uint32_t blocks = (n + 15u) / 16u;
     if (blocks > 2048u) blocks = 2048u;
     const dim3 grid(blocks), block(256);
-    if (variant == BSW_VARIANT_M)
-        hipLaunchKernelGGL((bsw_quad_kernel<S, BSW_VARIANT_M>), grid, block, 0, s, P, seq, tasks, order, n, n_dev, next_slot, out);
-    else
-        hipLaunchKernelGGL((bsw_quad_kernel<S, BSW_VARIANT_H>), grid, block, 0, s, P, seq, tasks, order, n, n_dev, next_slot, out);
+    hipLaunchKernelGGL((bsw_quad_kernel<S, VAR>), grid, block, 0, s, P, seq, tasks, order, n, n_dev, next_slot, out);
     return hipGetLastError();
 }
 
+template <int VAR>
+static hipError_t launch_quad_v(int cols, const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks,
+                                const uint32_t *order, uint32_t n, const uint32_t *n_dev, uint32_t *next_slot, bsw_result *out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    if (cols <= 64) return launch_qv<2, VAR>(P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    if (cols <= 128) return launch_qv<4, VAR>(P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    if (cols <= 192) return launch_qv<6, VAR>(P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    return launch_qv<8, VAR>(P, seq, tasks, order, n, n_dev, next_slot, out, s);
+}
+
+hipError_t launch_quad_rtl(int cols, const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks,
+                           const uint32_t *order, uint32_t n, const uint32_t *n_dev, uint32_t *next_slot, bsw_result *out, hipStream_t s);
+
+#ifdef BSW_QUAD_RTL_TU
+hipError_t launch_quad_rtl(int cols, const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks,
+                           const uint32_t *order, uint32_t n, const uint32_t *n_dev, uint32_t *next_slot, bsw_result *out, hipStream_t s)
+{
+    return launch_quad_v<BSW_VARIANT_RTL>(cols, P, seq, tasks, order, n, n_dev, next_slot, out, s);
+}
+#else
 /* cols = eh[] columns of the seed class (qlen + 1 <= cols <= 256); n = seed count (or an upper bound of *n_dev);
  * next_slot = a device word that is ZERO when the kernel starts (the caller's memset on the same stream) */
 hipError_t launch_quad(int cols, int variant, const bsw_dparams &P, const uint64_t *seq, const bsw_dtask *tasks,
                        const uint32_t *order, uint32_t n, const uint32_t *n_dev, uint32_t *next_slot, bsw_result *out, hipStream_t s)
 {
-    if (n == 0) return hipSuccess;
-    if (cols <= 64) return launch_qc<2>(variant, P, seq, tasks, order, n, n_dev, next_slot, out, s);
-    if (cols <= 128) return launch_qc<4>(variant, P, seq, tasks, order, n, n_dev, next_slot, out, s);
-    if (cols <= 192) return launch_qc<6>(variant, P, seq, tasks, order, n, n_dev, next_slot, out, s);
-    return launch_qc<8>(variant, P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    switch (variant) {
+    case BSW_VARIANT_H: return launch_quad_v<BSW_VARIANT_H>(cols, P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    case BSW_VARIANT_M: return launch_quad_v<BSW_VARIANT_M>(cols, P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    case BSW_VARIANT_RTL: return launch_quad_rtl(cols, P, seq, tasks, order, n, n_dev, next_slot, out, s);
+    default: return hipErrorInvalidValue;
+    }
 }
+#endif
 
 }  // namespace bsw

@@ -92,7 +92,11 @@ static int g_ctx_rc = 0;
 static std::atomic<int> g_variant{BSW_VARIANT_H};
 static std::atomic<uint64_t> g_scalar_calls{0}, g_scalar_trips{0};
 
-extern "C" void bsw_set_default_variant(int variant) { g_variant = variant == BSW_VARIANT_M ? BSW_VARIANT_M : BSW_VARIANT_H; }
+/* M and RTL are taken as given; every other value selects H, as before */
+extern "C" void bsw_set_default_variant(int variant)
+{
+    g_variant = (variant == BSW_VARIANT_M || variant == BSW_VARIANT_RTL) ? variant : BSW_VARIANT_H;
+}
 
 /* calls served and device round trips made by the scalar ABI so far (calls / trips = mean coalescing factor) */
 extern "C" void bsw_scalar_stats(uint64_t *calls, uint64_t *trips)

@@ -138,8 +138,8 @@ __device__ __forceinline__ void extend_side(const bsw_dparams &P, const uint64_t
             /* K3 band clamp (:1803,1894-1897,1842,1898) */
             beg = max(beg, i - w);
             end = min(min(end, i + w + 1), qlen);
-            /* K4 column 0, CPU semantics (:1795-1796,1835; Q4 avoided) */
-            const int h1_init = beg == 0 ? max(h0 - (o_del + e_del * (i + 1)), 0) : 0;
+            /* K4 column 0 (:1795-1796,1835): CPU semantics (Q4 avoided) for H and M; every row for RTL (:849) */
+            const int h1_init = (VAR == BSW_VARIANT_RTL || beg == 0) ? max(h0 - (o_del + e_del * (i + 1)), 0) : 0;
             cells += (unsigned)max(end - beg, 0);
 
             /* ---- phase 1: per-column M, max(M,e), scan input ---- */
@@ -195,7 +195,8 @@ __device__ __forceinline__ void extend_side(const bsw_dparams &P, const uint64_t
                 const int xn = j == beg ? h1_init : hp;
                 X[c] = wr ? xn : X[c];
                 E[c] = j == end ? 0 : E[c];
-                nzb[c] = __builtin_amdgcn_ballot_w64(wr && ((X[c] | E[c]) != 0));
+                if (VAR == BSW_VARIANT_RTL) nzb[c] = __builtin_amdgcn_ballot_w64(wr && X[c] == 0);   /* zero h (:1790) */
+                else nzb[c] = __builtin_amdgcn_ballot_w64(wr && ((X[c] | E[c]) != 0));
             }
             /* row tail scalars (K7) */
             const int lane_e = end / C, ce = end - lane_e * C;
@@ -219,6 +220,26 @@ __device__ __forceinline__ void extend_side(const bsw_dparams &P, const uint64_t
                 } else {
                     if (mx - mrow - ((mj - max_j) - (i - max_i)) * e_ins > P.zdrop) break;
                 }
+            }
+            if (VAR == BSW_VARIANT_RTL) {
+                /* K8, RTL (:1767-1769,1779,1872): the run of non-zero eh[].h around mj.  nzb[c] bit l = column l*C + c holds
+                 * a zero h inside [beg, end]; beg = 1 + the highest one <= mj (else beg), end = the lowest one >= mj + 2 (else
+                 * end + 1: the next row's K3 clamps it) */
+                int zlo = -1, zhi = INT_MAX;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const uint64_t b = nzb[c];
+                    const int dl = mj - c, dh = mj + 2 - c;           /* lanes l with l*C <= dl / l*C >= dh */
+                    const int ll = dl < 0 ? -1 : min(dl / C, 63);
+                    const int lh = dh <= 0 ? 0 : (dh + C - 1) / C;
+                    const uint64_t bl = ll < 0 ? 0ull : b & (ll >= 63 ? ~0ull : (2ull << ll) - 1ull);
+                    const uint64_t bh = lh > 63 ? 0ull : b & ~((1ull << lh) - 1ull);
+                    if (bl) zlo = max(zlo, (63 - (int)__builtin_clzll(bl)) * C + c);
+                    if (bh) zhi = min(zhi, (int)__builtin_ctzll(bh) * C + c);
+                }
+                beg = zlo >= 0 ? zlo + 1 : beg;
+                end = zhi != INT_MAX ? zhi : end + 1;
+                continue;
             }
             /* K8 next-row range, CPU semantics (Q5 avoided) */
             int first_nz = INT_MAX, last_nz = -1;
@@ -321,8 +342,12 @@ static hipError_t launch_c(int variant, const bsw_dparams &P, const uint64_t *se
     const dim3 grid(blocks), block(256);
     if (variant == BSW_VARIANT_M)
         hipLaunchKernelGGL((bsw_wave_kernel<C, BSW_VARIANT_M>), grid, block, 0, s, P, seq, tasks, order, n, n_dev, out);
-    else
+    else if (variant == BSW_VARIANT_H)
         hipLaunchKernelGGL((bsw_wave_kernel<C, BSW_VARIANT_H>), grid, block, 0, s, P, seq, tasks, order, n, n_dev, out);
+    else if (variant == BSW_VARIANT_RTL)
+        hipLaunchKernelGGL((bsw_wave_kernel<C, BSW_VARIANT_RTL>), grid, block, 0, s, P, seq, tasks, order, n, n_dev, out);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -298,7 +298,7 @@ extern "C" int bsw_refbatch_wait(bsw_ctx *ctx, int variant, int zdrop)
     int rc = busy_check(ctx, "bsw_refbatch_wait");
     if (rc) { ctx->ref_queue.clear(); return rc; }
     errs &e = ctx->err;
-    if (variant != BSW_VARIANT_H && variant != BSW_VARIANT_M) { ctx->ref_queue.clear(); return fail(e, BSW_E_INVAL, "bad variant"); }
+    if (variant != BSW_VARIANT_H && variant != BSW_VARIANT_M && variant != BSW_VARIANT_RTL) { ctx->ref_queue.clear(); return fail(e, BSW_E_INVAL, "bad variant"); }
     if (hipSetDevice(ctx->device0()) != hipSuccess) { ctx->ref_queue.clear(); return fail(e, BSW_E_HIP, "hipSetDevice"); }
     const size_t nq = ctx->ref_queue.size();
     /* Runs of batches with the same scoring header become device batches of at most REFBATCH_GROUP wire batches, up to

@@ -58,7 +58,7 @@ REFBATCH_IN_WORDS, REFBATCH_OUT_WORDS, REFBATCH_MAX_TASKS = 65536, 4096, 819
 KERNEL_AUTO, KERNEL_WAVE, KERNEL_LANE = 0, 1, 2
 LANE_AUTO_MIN = 40000          # seeds of the 150 bp single bin (131-base sides) from which BSW_KERNEL_AUTO uses the lane bins: LANE_WORK_MIN = 5 M query bases per launched side (bsw_internal.h)
 LANE_WORK_MIN, GROUP_WORK_MIN = 5_000_000, 1_500_000   # per launched side: lane kernels / the group kernel (bsw_lane2g_kernel) from this many query bases
-VARIANT_H, VARIANT_M = 0, 1
+VARIANT_H, VARIANT_M, VARIANT_RTL = 0, 1, 2
 
 ERRORS = {0: "BSW_OK", -1: "BSW_E_NODEVICE", -2: "BSW_E_INVAL", -3: "BSW_E_LIMIT", -4: "BSW_E_HIP",
           -5: "BSW_E_NOMEM", -6: "BSW_E_BUSY"}

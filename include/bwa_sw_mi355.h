@@ -57,10 +57,15 @@ extern "C" {
 #define BSW_MAX_TLEN   65535   /* target side length per extension                */
 #define BSW_MAX_SCORE  (1 << 20) /* h0 + qlen*max(mat) must stay below this       */
 
-/* recurrence variant: H = bwa<=0.7.8 and the RTL
- * (sw_pe_array_sw_extend.v:1797-1798,1863,1866); M = bwa>=0.7.9 ("M? M+q : 0") */
-#define BSW_VARIANT_H  0
-#define BSW_VARIANT_M  1
+/* recurrence variant:
+ *   H   = the RTL's cell (h += s with no zero test, gaps open from h: sw_pe_array_sw_extend.v:1797-1798,1863,1866) with
+ *         modern bwa's column 0 (only while beg == 0) and next-row trimming (first / last entry with h|e != 0); the default;
+ *   M   = bwa >= 0.7.9 throughout ("M? M+q : 0");
+ *   RTL = the reference: H's cell, column 0 on every row (:1795-1796,1835,849; int32, no 8-bit wrap) and the next row
+ *         trimmed to the run of non-zero h around the row maximum's column, e ignored (:1767-1769,1779,1790,1872). */
+#define BSW_VARIANT_H    0
+#define BSW_VARIANT_M    1
+#define BSW_VARIANT_RTL  2
 
 typedef struct bsw_params {
     int8_t  mat[25];        /* 5x5 scoring matrix, row = target base (K6)        */
@@ -72,7 +77,7 @@ typedef struct bsw_params {
     int32_t pen_clip3;      /* G1 [15:8]   also end_bonus of the right extension */
     int32_t zdrop;          /* not in the RTL (quirk Q3); bwa default 100        */
     int32_t max_band_try;   /* MAX_BAND_TRY, 2 in bwa and in the RTL (:1963)     */
-    int32_t variant;        /* BSW_VARIANT_H (default) or BSW_VARIANT_M          */
+    int32_t variant;        /* BSW_VARIANT_H (default), _M or _RTL               */
 } bsw_params;
 
 /* One seed = left + right extension (what one RTL processing element handles). */

@@ -5,7 +5,7 @@
  * `bwa --target=ASE|Direct mem -t N -b BATCH ...`) with bwa mem's scoring flags:
  *
  *   bsw-bench [--target=hip] [--gpus G | --devices 0,1,..] [-t gather_threads] [-b batch_seeds] [-n seeds] [-l read_len]
- *             [-A a] [-B b] [-O o[,o_ins]] [-E e[,e_ins]] [-L clip] [-w band] [-d zdrop] [--variant=H|M] [--reps R] [--pageable]
+ *             [-A a] [-B b] [-O o[,o_ins]] [-E e[,e_ins]] [-L clip] [-w band] [-d zdrop] [--variant=H|M|RTL] [--reps R] [--pageable]
  *             [--packed] [--dump FILE | --load FILE]
  *
  * --target=cpu is refused: the library has no CPU path (the CPU oracle lives under oracle/ and is test-only).
@@ -105,7 +105,7 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(f, "--dump")) dump = v, ++k; else if (!strcmp(f, "--load")) load = v, ++k;
         else if (!strcmp(f, "--pageable")) pageable = 1;
-        else if (!strcmp(f, "--variant=M")) variant = BSW_VARIANT_M; else if (!strcmp(f, "--variant=H")) variant = BSW_VARIANT_H;
+        else if (!strcmp(f, "--variant=M")) variant = BSW_VARIANT_M; else if (!strcmp(f, "--variant=H")) variant = BSW_VARIANT_H; else if (!strcmp(f, "--variant=RTL")) variant = BSW_VARIANT_RTL;
         else if (!strcmp(f, "--target=hip")) {}
         else if (!strncmp(f, "--target=", 9)) { fprintf(stderr, "%s: only --target=hip exists; this library has no CPU path\n", f); return 2; }
         else { fprintf(stderr, "unknown flag %s\n", f); return 2; }

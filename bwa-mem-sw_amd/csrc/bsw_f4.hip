@@ -7,7 +7,15 @@
 /* ---- banded global alignment with CIGAR (bwa ksw_global2) ------------------------------
  * Host side: lay the alignments out as right-side-only seeds so the byte-per-base sequences travel and are packed
  * exactly like extension tasks (registered arenas are DMA'd as they are), give every alignment its slice of the
- * backtrack matrix, sort by eh[] columns per lane, launch bsw_global_kernel, bring scores and CIGARs back. */
+ * backtrack matrix, sort by eh[] columns per lane, launch bsw_global_kernel, bring scores and CIGARs back.
+ * Queries of 1 024 bases and more (every query under BSW_GLOBAL_LONG=1) go to bsw_global_long_kernel instead, sorted by
+ * the LDS ring their band needs. */
+static bool global_force_long()
+{
+    static const bool on = getenv("BSW_GLOBAL_LONG") && atoi(getenv("BSW_GLOBAL_LONG")) != 0;     /* (fuzzing, rate A/B) */
+    return on;
+}
+
 static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_gtask *tasks, size_t n, int max_cigar,
                         bsw_gresult *res, uint32_t *cigars)
 {
@@ -17,8 +25,9 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
     if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     std::vector<bsw_gdtask> gt(n);
-    const int ncls = bsw::global_class_count();
-    std::vector<uint32_t> order(n), cnt((size_t)ncls + 1, 0), cls(n);
+    const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
+    const bool force_long = global_force_long();
+    std::vector<uint32_t> order(n), cnt((size_t)(ncls + nlong) + 1, 0), cls(n);
     uint64_t acc = 0, accb = 0, zacc = 0;
     const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
     for (size_t i = 0; i < n; ++i) {
@@ -40,10 +49,11 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
         if (cigars) zacc += (uint64_t)n_col * (uint64_t)t.tlen;
         int c = 0;
         while (c < ncls && t.qlen + 1 > bsw::global_class_cols(c)) ++c;
+        if (c == ncls || force_long) c = ncls + bsw::global_long_class_of(n_col);   /* classes ncls.. : the LDS ring kernel */
         cls[i] = (uint32_t)c;
         ++cnt[(size_t)c + 1];
     }
-    for (int c = 0; c < ncls; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
+    for (int c = 0; c < ncls + nlong; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
     {
         std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
         for (size_t i = 0; i < n; ++i) order[pos[cls[i]]++] = (uint32_t)i;
@@ -76,7 +86,7 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
     HIPCHK(e, hipMemcpyAsync(ctx->g_tasks.p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     HIPCHK(e, bsw::launch_pack(st.d_raw.p, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, nullptr, 0, nullptr, st.d_seq.p, nullptr, s));
-    for (int c = 0; c < ncls; ++c) {
+    for (int c = 0; c < ncls + nlong; ++c) {
         const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
         if (!k) continue;
         HIPCHK(e, bsw::launch_global(c, dp, st.d_seq.p, ctx->g_tasks.p, ctx->g_order.p + cnt[(size_t)c], k,
@@ -109,7 +119,8 @@ extern "C" int bsw_global_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_gta
         if ((t.qlen && !t.query) || (t.tlen && !t.target)) return fail(e, BSW_E_INVAL, "global task %zu: NULL sequence pointer", i);
     }
     HIPCHK(e, hipSetDevice(ctx->device0()));
-    /* sub-batches: bounded backtrack memory (1 byte per banded cell) and sequence arena */
+    /* sub-batches: bounded backtrack memory (1 byte per banded cell) and sequence arena; the largest single task
+     * (8 191 x 65 535 bytes of z, 73 726 sequence bytes) fits both bounds on its own */
     const uint64_t zcap = 4ull << 30;
     for (size_t a = 0; a < n;) {
         size_t b = a;

@@ -249,6 +249,8 @@ hipError_t launch_global(int cls, const bsw_dparams &P, const uint64_t *seq, con
                          uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
+    if (cls >= global_class_count())                         /* the LDS ring classes (bsw_global_long_kernel.hip) */
+        return launch_global_long(cls - global_class_count(), P, seq, tasks, order, n, z, cigars, max_cigar, out, s);
     switch (kGlobalClasses[cls]) {
     case 1: return launch_gc<1>(P, seq, tasks, order, n, z, cigars, max_cigar, out, s);
     case 2: return launch_gc<2>(P, seq, tasks, order, n, z, cigars, max_cigar, out, s);

@@ -32,29 +32,12 @@
 
 #include <atomic>
 
+#include "bsw_band_scan.h"
 #include "bsw_device.h"
 
 namespace bsw {
 
 namespace {
-
-template <int CTRL, int ROW_MASK = 0xf, int BANK_MASK = 0xf>
-__device__ __forceinline__ int bdpp(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
-}
-
-/* inclusive max-scan over the 64 lanes (row_shr 1,2,4,8 + row_bcast 15/31) */
-__device__ __forceinline__ int band_scan_max(int x)
-{
-    x = max(x, bdpp<0x111>(INT_MIN, x));
-    x = max(x, bdpp<0x112>(INT_MIN, x));
-    x = max(x, bdpp<0x114>(INT_MIN, x));
-    x = max(x, bdpp<0x118>(INT_MIN, x));
-    x = max(x, bdpp<0x142, 0xa>(INT_MIN, x));
-    x = max(x, bdpp<0x143, 0xc>(INT_MIN, x));
-    return x;
-}
 
 constexpr int NEGB = -(1 << 29);                       /* "minus infinity": 8 191 columns x e_ins <= 4 096 = 2^25 below it is still far from INT_MIN */
 

@@ -61,6 +61,17 @@ int global_class_count();
 int global_class_cols(int cls);
 hipError_t launch_global(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *order, uint32_t n,
                          uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s);
+/* banded global alignment with the row in an LDS ring (bsw_global_long_kernel.hip), classes by ring size, i.e. by the band:
+ * ring class c holds 256 << c records, n_col + 1 <= 256 << c.  launch_global(global_class_count() + c, ...) launches it. */
+constexpr int GLOBAL_LONG_CLASSES = 6;
+inline int global_long_class_of(int n_col)
+{
+    int c = 0;
+    while (c + 1 < GLOBAL_LONG_CLASSES && n_col + 1 > (256 << c)) ++c;
+    return c;
+}
+hipError_t launch_global_long(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *order, uint32_t n,
+                              uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s);
 int align_class_count();
 int align_class_of(int qlen, int byte_mode);                 /* -1: query too long for the mode */
 hipError_t launch_align(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,

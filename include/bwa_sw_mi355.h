@@ -53,7 +53,8 @@ extern "C" {
 /* ---- device limits ------------------------------------------------------- */
 #define BSW_MAX_QLEN   8191    /* query side length per extension (ksw_extend2 and the batch API; up to 1 023 in registers,
                                   beyond that the eh[] row lives in LDS: bsw_long_kernel.hip)                          */
-#define BSW_GLOBAL_MAX_QLEN 1023 /* ksw_global2 / bsw_global_batch                 */
+#define BSW_GLOBAL_MAX_QLEN 8191 /* ksw_global2 / bsw_global_batch (up to 1 023 in registers, beyond that the eh[]
+                                    row lives in an LDS ring the size of the band: bsw_global_long_kernel.hip)       */
 #define BSW_MAX_TLEN   65535   /* target side length per extension                */
 #define BSW_MAX_SCORE  (1 << 20) /* h0 + qlen*max(mat) must stay below this       */
 
@@ -270,7 +271,9 @@ int      bsw_extend_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ext_task 
 /* ---- banded global alignment with CIGAR: bwa's ksw_global2 / ksw_global (ksw.c), the
  * Smith-Waterman user after seed extension inside mem_reg2aln (bwa_gen_cigar2).  Not in the reference RTL — it
  * belongs to the host software named at reference README.md:7-18.  CIGAR encoding is BAM's: len << 4 | op,
- * op 0 = M, 1 = I, 2 = D. ---- */
+ * op 0 = M, 1 = I, 2 = D.  Queries up to BSW_GLOBAL_MAX_QLEN = 8 191 bases (bwa's routine has no limit; the read-sized
+ * path keeps the row in registers, queries of 1 024 bases and more run with the row in LDS), targets and bands up to
+ * BSW_MAX_TLEN. ---- */
 typedef struct bsw_gtask {
     const uint8_t *query, *target;   /* codes 0..4, one per byte */
     int32_t qlen, tlen, w;           /* w = band half-width */

@@ -17,6 +17,10 @@ kernels alone: what rounds 1-5 printed as `value`).  `roofline` prices the domin
 on every rank (timed between barriers, MAX over ranks), with what the host side cost (bsw_host_stats: CPU seconds of the slot
 threads per million seeds) and how many cores 8 GPUs would need at that rate.
 `other_workloads` (N=1): configs[1] (150 bp single bin, 1 M seeds) and configs[4]'s shape (250 bp, w = 500, 1 M seeds).
+
+A plain run does what `value` needs and no more: set up, warm up, time the steps, write --dump-outputs, print the line (with
+the `roofline` figures the timed steps' own HIP events give).  `kernels_only`, `e2e*`, `cpu_baseline`, `parity_spot_check`,
+`other_workloads` and `other_paths` run only under --full (their fields are null or absent without it).
 """
 import argparse
 import json
@@ -497,7 +501,9 @@ def nominal_of(tasks):
     return int((tasks["lqlen"].astype(np.int64) * tasks["ltlen"]).sum() + (tasks["rqlen"].astype(np.int64) * tasks["rtlen"]).sum())
 
 
-def main():
+def parse_args(argv=None):
+    """The command line -> args, with --preset applied and what a plain run (no --full) leaves out switched off."""
+    argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -512,17 +518,21 @@ def main():
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--zdrop", type=int, default=100)
     ap.add_argument("--gaps", default=None, help="o_del,e_del,o_ins,e_ins (default: bwa's 6,1,6,1)")
-    ap.add_argument("--kernels-only-steps", type=int, default=-1, help="steps of the second timed region (bsw_run: DP kernels alone); -1 = --steps, 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the DP kernels alone (a second timed region), the PCIe-inclusive "
+                         "e2e legs, the CPU baseline and parity spot check, the other workloads and side paths; without it a run sets up, "
+                         "warms up, times the steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--kernels-only-steps", type=int, default=-1, help="steps of the second timed region (bsw_run: DP kernels alone); 0 = skip; -1 (default) = --steps under --full, 0 otherwise")
     ap.add_argument("--cpu-sample", type=int, default=250_000, help="seeds timed on the scalar CPU oracle (rank 0, N=1): 3 runs of ~9 s on 16 threads")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = min(affinity, 16): the 1-GPU box's CPU share; an all-core leg is added when the affinity holds more")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the single-bin / 250 bp / side-path measurements (N=1 only, outside the timed region)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity spot check")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the single-bin / 250 bp / side-path measurements (N=1 only, outside the timed region)")
     ap.add_argument("--other-seeds", type=int, default=1_000_000, help="seeds of the other_workloads legs")
     ap.add_argument("--packed-chunk", type=int, default=0, help="seeds per chunk of the packed-input legs (0 = the library's choice: sized by the seeds' work, bsw_config.chunk_tasks = 0)")
     ap.add_argument("--e2e-chunk", type=int, default=0, help="seeds per chunk of the byte-input and device-reference legs (0 = the library's choice)")
     ap.add_argument("--e2e-slots", type=int, default=4, help="slot threads (= streams) of the PCIe-inclusive legs")
     ap.add_argument("--e2e-pack-threads", type=int, default=8, help="bsw_config.pack_threads of the PCIe-inclusive legs: a chunk's host pass runs on 1 + this / slots threads")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the bsw_submit (PCIe-inclusive) measurements")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the bsw_submit (PCIe-inclusive) measurements")
     ap.add_argument("--e2e-reps", type=int, default=5, help="bsw_submit passes timed (median reported)")
     ap.add_argument("--stream-reps", type=int, default=8, help="batches of a stream leg (two submits in flight in ONE context)")
     ap.add_argument("--ref-mbp", type=int, default=64, help="synthetic genome size (Mbp) of the device-resident-reference e2e leg; 0 = skip")
@@ -538,14 +548,21 @@ def main():
                          "of at most %d seeds)" % DUMP_MAX_SEEDS)
     ap.add_argument("--preset", default=None, choices=sorted(PRESETS),
                     help="BASELINE.json configs[3] / configs[4] as one flag (sets --workload/--scaling/--pool; explicit flags still win)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.preset:
-        given = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
+        given = {a.split("=")[0] for a in argv if a.startswith("--")}
         for key, val in PRESETS[args.preset].items():
             if "--" + key not in given:
                 setattr(args, key, val)
     if args.kernels_only_steps < 0:
-        args.kernels_only_steps = args.steps
+        args.kernels_only_steps = args.steps if args.full else 0
+    if not args.full:
+        args.no_e2e = args.no_cpu_baseline = args.no_extra = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without torchrun: start N fresh per-GPU ranks BEFORE anything here touches the GPU
@@ -731,7 +748,7 @@ def main():
         retry = int((r["left"]["aw"] > spec["w"]).sum() + (r["right"]["aw"] > spec["w"]).sum())
         ext_calls += gstats[gi][0] + retry
         nominal += gstats[gi][1]
-        if tasks is not None:
+        if tasks is not None and not (args.no_e2e and args.no_cpu_baseline):      # the result batch the e2e and CPU legs compare against
             res_parts.append(r)
     res = np.concatenate(res_parts) if res_parts else None
     del res_parts

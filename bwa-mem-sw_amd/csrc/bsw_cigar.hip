@@ -1,0 +1,291 @@
+/*
+ * bsw_cigar.hip — host of bsw_cigar_ref_batch: bwa_gen_cigar2 (bwa.c), inside mem_reg2aln's band-widening loop (bwamem.c),
+ * against the device-resident reference (part of the host side of libbwasw_mi355.so; shared types: bsw_internal.h).
+ *
+ * Per chunk of tasks:
+ *   1. the reads cross PCIe (registered memory is DMA'd as it lies, anything else is gathered into pinned staging) and
+ *      bsw_pack_kernel packs them next to the targets it fetches from the resident pac.  A forward-strand interval is a
+ *      right-side-only seed (read forwards, target upwards from rb); a reverse-strand one a left-side-only seed (read
+ *      backwards from its last base, target downwards from re - 1): that is bwa's reversal of both, for free;
+ *   2. every try runs bsw_global_kernel / bsw_global_long_kernel (unchanged, with their class routing) on the tasks still
+ *      in the loop, with their band and a fresh slice of the backtrack matrix; only the scores come back between tries,
+ *      the packed sequences stay where they are.  A try whose band (after bwa's formula) equals the previous one's would
+ *      return the previous score and end the loop on "score == last": it is counted, not run;
+ *   3. bsw_cigar_md_kernel derives NM and MD once per task from its final CIGAR, and settles bwa's no-gap shortcut.
+ */
+#include "bsw_internal.h"
+
+#include <climits>
+
+/* BSW_GLOBAL_LONG=1 sends every alignment to the LDS ring kernel, as it does for bsw_global_batch */
+static bool cigar_force_long()
+{
+    static const bool on = getenv("BSW_GLOBAL_LONG") && atoi(getenv("BSW_GLOBAL_LONG")) != 0;
+    return on;
+}
+
+/* bwa_gen_cigar2's band for a try with w_ (the no-gap shortcut aside) */
+static int gen_cigar_band(const bsw_params &p, int l_query, int rlen, int w_)
+{
+    const int max_ins = (int)((double)(((l_query + 1) >> 1) * p.mat[0] - p.o_ins) / p.e_ins + 1.);
+    const int max_del = (int)((double)(((l_query + 1) >> 1) * p.mat[0] - p.o_del) / p.e_del + 1.);
+    int max_gap = max_ins > max_del ? max_ins : max_del;
+    max_gap = max_gap > 1 ? max_gap : 1;
+    const int d = abs(rlen - l_query);
+    int w = (max_gap + d + 1) >> 1;
+    w = w < w_ ? w : w_;
+    return w > d + 3 ? w : d + 3;
+}
+
+/* the pack kernel reads a word of a sequence as 20 bytes from the dword below its first byte: forwards up to 16 + 3 bytes past
+ * a read's end, backwards (reverse strand) down to 15 + 3 bytes before its start */
+static_assert(RAW_FRONT >= 18 && RAW_SLACK >= 20, "raw slack of the reads");
+
+struct cstate {                       /* one task's place in mem_reg2aln's loop */
+    int w2, wcap, last, tries, band;
+    bool live;                        /* still has a try to run */
+};
+
+static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
+                       size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res)
+{
+    stage_t &st = ctx->small;
+    hipStream_t s = ctx->stream0();
+    hipError_t he;
+    const int64_t l_pac = ref->l_pac;
+    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
+        (he = st.h_desc.reserve(n + 1)) != hipSuccess)
+        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    std::vector<bsw_gdtask> gt(n);
+    std::vector<bsw_cdtask> cd(n);
+    std::vector<cstate> cs(n);
+    uint64_t acc = 0, accb = 0;
+    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_ctask &t = tasks[i];
+        bsw_dtask &d = st.h_tasks.p[i];
+        bsw_rawoff &r = st.h_roff.p[i];
+        bsw_refx &x = st.h_desc.p[i];
+        memset(&d, 0, sizeof(d));
+        memset(&r, 0, sizeof(r));
+        x = bsw_refx{0, 0};
+        bsw_cdtask &c = cd[i];
+        memset(&c, 0, sizeof(c));
+        cstate &q = cs[i];
+        q = cstate{0, 0, -(1 << 30), 0, 0, false};
+        q.wcap = t.w_cap ? t.w_cap : t.w;
+        q.w2 = t.w < q.wcap ? t.w : q.wcap;
+        /* bwa: no alignment for an empty read, an empty or bridging interval, or one bns_get_seq cannot return whole */
+        if (t.l_query == 0 || t.rb >= t.re || (t.rb < l_pac && t.re > l_pac) || t.rb < 0 || t.re > 2 * l_pac) {
+            c.flags = BSW_CD_STATUS;
+            continue;
+        }
+        const int rlen = (int)(t.re - t.rb);
+        const bool rev = t.rb >= l_pac;
+        const uint32_t qw = (uint32_t)acc, tw = (uint32_t)(acc + nwords(t.l_query));
+        acc += nwords(t.l_query) + nwords(rlen);
+        if (rev) {                        /* left side only: read backwards from its last base, target downwards from re - 1 */
+            d.lq_off = qw; d.lt_off = tw; d.lqlen = (uint16_t)t.l_query; d.ltlen = (uint16_t)rlen;
+            r.lq = (uint32_t)accb + (uint32_t)t.l_query - 1u;
+            x.xl = t.re - 1;
+        } else {                          /* right side only: read forwards, target upwards from rb */
+            d.rq_off = qw; d.rt_off = tw; d.rqlen = (uint16_t)t.l_query; d.rtlen = (uint16_t)rlen;
+            r.rq = (uint32_t)accb;
+            x.xr = t.rb;
+        }
+        accb += (uint64_t)t.l_query;
+        if (t.query < lo) lo = t.query;
+        if (t.query + t.l_query > hi) hi = t.query + t.l_query;
+        c.q_off = qw; c.t_off = tw; c.qlen = t.l_query; c.tlen = rlen;
+        c.flags = rev ? BSW_CD_REV : 0u;
+        if (t.l_query == rlen && q.w2 == 0) {            /* the no-gap shortcut: the NM / MD kernel does it */
+            c.flags |= BSW_CD_NOGAP;
+            c.min_score = t.min_score;
+            c.more = (q.wcap != 0 && (t.max_tries > 1)) ? 1 : 0;     /* a second try: same band, same score, then "score == last" */
+            q.tries = 1;
+            continue;
+        }
+        q.band = gen_cigar_band(pp, t.l_query, rlen, q.w2);
+        q.live = true;
+        bsw_gdtask &g = gt[i];
+        g.q_off = qw; g.t_off = tw; g.qlen = t.l_query; g.tlen = rlen; g.w = q.band; g.pad = 0; g.z_off = 0;
+    }
+    /* the reads: the caller's bytes as they lie (registered memory) or gathered forwards into pinned staging; either way a
+     * reverse-strand read's offset names its LAST byte and the pack kernel reads it backwards */
+    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
+    const bool direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * accb + (1u << 20) && is_registered(lo, spanb);
+    if (direct) {
+        for (size_t i = 0; i < n; ++i) {
+            if (cd[i].flags & BSW_CD_STATUS) continue;
+            const uint32_t o = (uint32_t)(tasks[i].query - lo);
+            if (cd[i].flags & BSW_CD_REV) st.h_roff.p[i].lq = o + (uint32_t)tasks[i].l_query - 1u;
+            else st.h_roff.p[i].rq = o;
+        }
+    } else if (accb) {
+        if ((he = st.h_raw.reserve((size_t)accb + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+        for (size_t i = 0; i < n; ++i) {
+            if (cd[i].flags & BSW_CD_STATUS) continue;
+            const uint32_t o = (cd[i].flags & BSW_CD_REV) ? st.h_roff.p[i].lq + 1u - (uint32_t)tasks[i].l_query : st.h_roff.p[i].rq;
+            memcpy(st.h_raw.p + o, tasks[i].query, (size_t)tasks[i].l_query);
+        }
+    }
+    const size_t rawb = direct ? spanb : (size_t)accb;
+    /* backtrack room: the widest band any try can reach is the formula's own (w_ only caps it) */
+    uint64_t zmax = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!cs[i].live) continue;
+        const int wmax = gen_cigar_band(pp, cd[i].qlen, cd[i].tlen, INT_MAX);
+        zmax += (uint64_t)std::min(cd[i].qlen, 2 * wmax + 1) * (uint64_t)cd[i].tlen;
+    }
+    if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
+        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
+        (he = st.d_desc.reserve(n + 1)) != hipSuccess ||
+        (he = ctx->g_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
+        (he = ctx->g_res.reserve(n + 1)) != hipSuccess || (he = ctx->g_z.reserve((size_t)zmax + 64)) != hipSuccess ||
+        (he = ctx->g_cig.reserve(n * (size_t)max_cigar + 1)) != hipSuccess ||
+        (he = ctx->c_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->c_res.reserve(n + 1)) != hipSuccess ||
+        (md && (he = ctx->c_md.reserve(n * (size_t)max_md + 1)) != hipSuccess))
+        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(ctx->c_tasks.p, cd.data(), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
+    HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 1, ref->d_pac[0], l_pac, st.d_desc.p,
+                               st.d_seq.p, nullptr, s));
+
+    /* the tries: each launches the global kernels on the tasks still in the loop, then reads their scores */
+    const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
+    const bool force_long = cigar_force_long();
+    std::vector<bsw_gresult> gr(n);
+    std::vector<uint32_t> order, cnt((size_t)(ncls + nlong) + 1), cls;
+    std::vector<uint32_t> live;
+    for (size_t i = 0; i < n; ++i) if (cs[i].live) live.push_back((uint32_t)i);
+    while (!live.empty()) {
+        std::fill(cnt.begin(), cnt.end(), 0u);
+        cls.assign(live.size(), 0u);
+        uint64_t zacc = 0;
+        for (size_t k = 0; k < live.size(); ++k) {
+            bsw_gdtask &g = gt[live[k]];
+            g.w = cs[live[k]].band;
+            g.z_off = zacc;
+            const int n_col = g.qlen < 2 * g.w + 1 ? g.qlen : 2 * g.w + 1;
+            zacc += (uint64_t)n_col * (uint64_t)g.tlen;
+            int c = 0;                    /* bsw_global_batch's routing */
+            while (c < ncls && g.qlen + 1 > bsw::global_class_cols(c)) ++c;
+            if (c == ncls || force_long) c = ncls + bsw::global_long_class_of(n_col);
+            cls[k] = (uint32_t)c;
+            ++cnt[(size_t)c + 1];
+        }
+        for (int c = 0; c < ncls + nlong; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
+        order.assign(live.size(), 0u);
+        {
+            std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
+            for (size_t k = 0; k < live.size(); ++k) order[pos[cls[k]]++] = live[k];
+        }
+        HIPCHK(e, hipMemcpyAsync(ctx->g_tasks.p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        for (int c = 0; c < ncls + nlong; ++c) {
+            const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
+            if (!k) continue;
+            HIPCHK(e, bsw::launch_global(c, dp, st.d_seq.p, ctx->g_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->g_z.p, ctx->g_cig.p,
+                                         max_cigar, ctx->g_res.p, s));
+        }
+        int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
+        if (rc) return rc;
+        HIPCHK(e, hipMemcpy(gr.data(), ctx->g_res.p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost));
+        /* mem_reg2aln: if (score == last || w2 == w_cap) break; last = score; w2 <<= 1; } while (++i < max_tries && score < min_score) */
+        std::vector<uint32_t> next;
+        for (uint32_t i : live) {
+            cstate &q = cs[i];
+            const bsw_ctask &t = tasks[i];
+            const int score = gr[i].score;
+            ++q.tries;
+            q.live = false;
+            if (score == q.last || q.w2 == q.wcap) continue;
+            q.last = score;
+            const int max_tries = t.max_tries ? t.max_tries : 1;
+            if (!(q.tries < max_tries && score < t.min_score)) continue;
+            q.w2 = std::min(q.w2 << 1, q.wcap);
+            const int band = gen_cigar_band(pp, cd[i].qlen, cd[i].tlen, q.w2);
+            if (band == q.band) {         /* the same alignment again: its score equals `last` and the loop ends there */
+                ++q.tries;
+                continue;
+            }
+            q.band = band;
+            q.live = true;
+            next.push_back(i);
+        }
+        live.swap(next);
+    }
+    HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, ctx->c_tasks.p, (uint32_t)n, ctx->g_cig.p, max_cigar, ctx->g_res.p,
+                                   md ? ctx->c_md.p : nullptr, max_md, ctx->c_res.p, s));
+    int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpy(res, ctx->c_res.p, n * sizeof(bsw_cresult), hipMemcpyDeviceToHost));
+    if (cigars) HIPCHK(e, hipMemcpy(cigars, ctx->g_cig.p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (md) HIPCHK(e, hipMemcpy(md, ctx->c_md.p, n * (size_t)max_md, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        bsw_cresult &r = res[i];
+        if (cd[i].flags & BSW_CD_STATUS) {
+            r = bsw_cresult{0, 0, -1, 0, cs[i].w2, 1, 1, 0};
+            continue;
+        }
+        r.w = cs[i].w2;
+        if (!(cd[i].flags & BSW_CD_NOGAP)) r.tries = cs[i].tries;
+        r.status = 0;
+        r._pad = 0;
+    }
+    return BSW_OK;
+}
+
+extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ctask *tasks, size_t n,
+                                   int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res)
+{
+    if (!ctx) return BSW_E_INVAL;
+    errs &e = ctx->err;
+    if (!p || !ref || (!tasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1))
+        return fail(e, BSW_E_INVAL, "bsw_cigar_ref_batch: bad argument");
+    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
+        return fail(e, BSW_E_INVAL, "bsw_cigar_ref_batch: the reference was uploaded through another context");
+    int rc = busy_check(ctx, "bsw_cigar_ref_batch");
+    if (rc) return rc;
+    bsw_params pp = *p;
+    pp.w = 0;                                         /* the band is per task here */
+    bsw_dparams dp;
+    rc = check_params(e, &pp, &dp);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_ctask &t = tasks[i];
+        if (t.l_query < 0 || t.w < 0 || t.w_cap < 0 || t.max_tries < 0 || t.max_tries > 3)
+            return fail(e, BSW_E_INVAL, "cigar task %zu: negative length or band, or max_tries outside 0..3", i);
+        if (t.l_query && !t.query) return fail(e, BSW_E_INVAL, "cigar task %zu: NULL read", i);
+        if (t.l_query > BSW_GLOBAL_MAX_QLEN || t.w > BSW_MAX_TLEN || t.w_cap > BSW_MAX_TLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
+            return fail(e, BSW_E_LIMIT, "cigar task %zu: beyond BSW_GLOBAL_MAX_QLEN / BSW_MAX_TLEN", i);
+    }
+    HIPCHK(e, hipSetDevice(ctx->device0()));
+    /* sub-batches: bounded backtrack memory (the widest band of any try) and sequence arena, as bsw_global_batch */
+    const uint64_t zcap = 4ull << 30;
+    for (size_t a = 0; a < n;) {
+        size_t b = a;
+        uint64_t zb = 0, sb = 0;
+        while (b < n && b - a < (1u << 20)) {
+            const bsw_ctask &t = tasks[b];
+            uint64_t nz = 0, ns = 0;
+            if (t.l_query > 0 && t.re > t.rb && t.re - t.rb <= BSW_MAX_TLEN) {
+                const int rlen = (int)(t.re - t.rb), wmax = gen_cigar_band(pp, t.l_query, rlen, INT_MAX);
+                nz = (uint64_t)std::min(t.l_query, 2 * wmax + 1) * (uint64_t)rlen;
+                ns = (uint64_t)t.l_query + (uint64_t)rlen;
+            }
+            if (b > a && (zb + nz > zcap || sb + ns > (1ull << 31))) break;
+            zb += nz;
+            sb += ns;
+            ++b;
+        }
+        rc = cigar_chunk(ctx, e, pp, dp, ref, tasks + a, b - a, max_cigar, cigars ? cigars + a * (size_t)max_cigar : nullptr, max_md,
+                         md ? md + a * (size_t)max_md : nullptr, res + a);
+        if (rc) return rc;
+        a = b;
+    }
+    return BSW_OK;
+}

@@ -192,6 +192,7 @@ static void ctx_release(bsw_ctx *ctx)
         ctx->small.release();
         ctx->g_tasks.release(); ctx->g_z.release(); ctx->g_cig.release(); ctx->g_order.release(); ctx->g_res.release();
         ctx->a_tasks.release(); ctx->a_bl.release(); ctx->a_res.release();
+        ctx->c_tasks.release(); ctx->c_res.release(); ctx->c_md.release();
     }
     delete ctx;
 }

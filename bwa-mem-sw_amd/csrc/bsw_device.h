@@ -72,6 +72,20 @@ typedef struct bsw_gdtask {
     uint64_t z_off;           /* byte offset of this alignment's backtrack matrix */
 } bsw_gdtask;
 
+/* one bwa_gen_cigar2 call's NM / MD pass (bsw_cigar_kernel.hip): the packed read and target of its final try, where its
+ * CIGAR and score sit (the global kernels' cigars[] / out[] at the same index), and what the kernel must settle itself */
+#define BSW_CD_REV      1u    /* reverse strand: MD letters from "TGCAN" */
+#define BSW_CD_NOGAP    2u    /* bwa's no-gap shortcut (l_query == re - rb, w_ == 0): the kernel writes the CIGAR and the score */
+#define BSW_CD_STATUS   4u    /* bwa returns no alignment: an empty record */
+typedef struct bsw_cdtask {
+    uint32_t q_off, t_off;    /* word offsets into seq */
+    int32_t  qlen, tlen;
+    uint32_t flags;
+    int32_t  min_score;       /* BSW_CD_NOGAP: a second try (same band, same score) follows when the score is below this ... */
+    int32_t  more;            /* ... and more != 0 (max_tries >= 2 and w_ != w_cap) */
+    uint32_t pad;
+} bsw_cdtask;
+
 /* one local alignment (bsw_align_kernel.hip; SURVEY.md §8f F4: bwa ksw_align2) */
 typedef struct bsw_adtask {
     uint32_t q_off, t_off;    /* word offsets into seq */

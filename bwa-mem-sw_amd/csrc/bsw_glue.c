@@ -106,3 +106,14 @@ int64_t bsw_pac_get_seq(int64_t l_pac, const uint8_t *pac, int64_t beg, int64_t 
     }
     return l;
 }
+
+/* mem_reg2aln's infer_bw (bwamem.c): 0 when equal lengths cannot afford the two gaps an indel pair would cost, else the band
+ * a global alignment needs to keep `score` reachable, at least |l1 - l2| */
+int bsw_infer_bw(int l1, int l2, int score, int a, int q, int r)
+{
+    int w;
+    if (l1 == l2 && l1 * a - score < (q + r - a) << 1) return 0;
+    w = (int)((double)((l1 < l2 ? l1 : l2) * a - score - q) / r + 2.);
+    if (w < (l1 > l2 ? l1 - l2 : l2 - l1)) w = l1 > l2 ? l1 - l2 : l2 - l1;
+    return w;
+}

@@ -7,6 +7,7 @@
  *   bsw_scalar.hip  batched plain ksw_extend2 and the drop-in scalar entry points' shared queue
  *   bsw_wire.hip    the reference's 256 KiB / 16 KiB wire format end to end (F1)
  *   bsw_f4.hip      ksw_global2 / ksw_align2 hosts (F4)
+ *   bsw_cigar.hip   bwa_gen_cigar2 (+ mem_reg2aln's retries) against the resident reference
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
 #ifndef BSW_INTERNAL_H
@@ -288,6 +289,9 @@ struct bsw_ctx {
     dbuf<bsw_adtask> a_tasks;         /* local alignment (bsw_align_batch) */
     dbuf<unsigned long long> a_bl;
     dbuf<bsw_kswr> a_res;
+    dbuf<bsw_cdtask> c_tasks;         /* bwa_gen_cigar2 on the resident reference (bsw_cigar_ref_batch) */
+    dbuf<bsw_cresult> c_res;
+    dbuf<char> c_md;
     std::vector<refbatch_req> ref_queue;
     int device0() const { return devs[0].device; }
     hipStream_t stream0() const { return devs[0].streams[0]; }

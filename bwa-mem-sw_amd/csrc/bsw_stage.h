@@ -72,6 +72,10 @@ inline int global_long_class_of(int n_col)
 }
 hipError_t launch_global_long(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *order, uint32_t n,
                               uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s);
+/* NM and MD of bwa_gen_cigar2 from the device-side CIGARs (bsw_cigar_kernel.hip): one wavefront per task of tasks[0..n);
+ * res[i] gets score, n_cigar, nm, md_len (and tries for BSW_CD_NOGAP tasks); md (may be NULL) a slot of max_md bytes per task */
+hipError_t launch_cigar_md(const bsw_dparams &P, const uint64_t *seq, const bsw_cdtask *tasks, uint32_t n, uint32_t *cigars, int max_cigar,
+                           const bsw_gresult *gres, char *md, int max_md, bsw_cresult *res, hipStream_t s);
 int align_class_count();
 int align_class_of(int qlen, int byte_mode);                 /* -1: query too long for the mode */
 hipError_t launch_align(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,

@@ -35,6 +35,10 @@ ALNREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), (
                    ("w", "<i4"), ("_pad", "<i4")])
 GTASK = np.dtype([("query", "<u8"), ("target", "<u8"), ("qlen", "<i4"), ("tlen", "<i4"), ("w", "<i4"), ("_pad", "<i4")])
 GRESULT = np.dtype([("score", "<i4"), ("n_cigar", "<i4")])
+CTASK = np.dtype([("query", "<u8"), ("l_query", "<i4"), ("w", "<i4"), ("rb", "<i8"), ("re", "<i8"), ("w_cap", "<i4"),
+                  ("min_score", "<i4"), ("max_tries", "<i4"), ("_pad", "<i4")])
+CRESULT = np.dtype([("score", "<i4"), ("n_cigar", "<i4"), ("nm", "<i4"), ("md_len", "<i4"), ("w", "<i4"), ("tries", "<i4"),
+                    ("status", "<i4"), ("_pad", "<i4")])
 ATASK = np.dtype([("query", "<u8"), ("target", "<u8"), ("qlen", "<i4"), ("tlen", "<i4"), ("xtra", "<i4"), ("_pad", "<i4")])
 KSWR = np.dtype([("score", "<i4"), ("te", "<i4"), ("qe", "<i4"), ("score2", "<i4"), ("te2", "<i4"), ("tb", "<i4"), ("qb", "<i4")])
 KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
@@ -52,6 +56,7 @@ PAIR = np.dtype([("tag", "<u4"), ("qb", "<i4"), ("qe", "<i4"), ("rb", "<i4"), ("
 RESULT_FULL, RESULT_PAIR = 0, 1
 assert PARAMS.itemsize == 68 and TASK.itemsize == 72 and EXT.itemsize == 32 and RESULT.itemsize == 96
 assert ATASK.itemsize == 32 and KSWR.itemsize == 28
+assert CTASK.itemsize == 48 and CRESULT.itemsize == 32
 assert EXT_TASK.itemsize == 40 and SYNTH.itemsize == 72 and CONFIG.itemsize == 104 and PAIR.itemsize == 32 and REF_TASK.itemsize == 56
 
 REFBATCH_IN_WORDS, REFBATCH_OUT_WORDS, REFBATCH_MAX_TASKS = 65536, 4096, 819
@@ -134,6 +139,8 @@ def lib():
             "bsw_scalar_stats": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
             "bsw_global_batch": (C.c_int, [vp, vp, vp, sz, C.c_int, vp, vp]),
             "bsw_align_batch": (C.c_int, [vp, vp, vp, sz, vp]),
+            "bsw_cigar_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp]),
+            "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "ksw_global2": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp] + [C.c_int] * 5 + [vp, vp]),
             "ksw_global": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp] + [C.c_int] * 3 + [vp, vp]),
             "bsw_ref_upload": (C.c_int, [vp, vp, C.c_int64, C.POINTER(vp)]),
@@ -163,7 +170,7 @@ def lib():
     return _lib
 
 
-EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
+EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
            "bsw_submit_packed", "bsw_upload_packed", "bsw_pack_tasks", "bsw_pack_tasks_bound",
@@ -479,6 +486,21 @@ class BswContext:
                                          res.ctypes.data, cig.ctypes.data if want_cigar else None), "bsw_global_batch")
         return res, cig
 
+    def cigar_ref_batch(self, params, ref, ctasks, max_cigar=64, max_md=256, want_cigar=True, want_md=True):
+        """bwa_gen_cigar2 (+ mem_reg2aln's retries) against a reference from ref_upload.  Returns (CRESULT array,
+        cigars uint32[n, max_cigar] or None, list of MD strings or None)."""
+        n = len(ctasks)
+        res = np.zeros(n, dtype=CRESULT)
+        cig = np.zeros((n, max_cigar), dtype=np.uint32) if want_cigar else None
+        md = np.zeros((n, max_md), dtype=np.uint8) if want_md else None
+        self._chk(lib().bsw_cigar_ref_batch(self.handle, params.ctypes.data, ref, ctasks.ctypes.data, n, max_cigar,
+                                            cig.ctypes.data if want_cigar else None, max_md,
+                                            md.ctypes.data if want_md else None, res.ctypes.data), "bsw_cigar_ref_batch")
+        strings = None
+        if want_md:
+            strings = [bytes(md[i, :max(int(res["md_len"][i]), 0)]).decode("ascii") for i in range(n)]
+        return res, cig, strings
+
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""
         res = np.zeros(len(atasks), dtype=KSWR)
@@ -636,6 +658,11 @@ def pac_get_seq(pac, l_pac, beg, end):
     if n < 0:
         raise BswError(int(n), "bsw_pac_get_seq")
     return dst[:n]
+
+
+def infer_bw(l1, l2, score, a, q, r):
+    """mem_reg2aln's infer_bw (bsw_infer_bw)."""
+    return int(lib().bsw_infer_bw(l1, l2, score, a, q, r))
 
 
 def pack_pac(bases):

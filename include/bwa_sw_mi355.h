@@ -26,6 +26,9 @@
  *                              (batch_manager.v:208-221, :358-739; tbb.v; rbb.v)
  *   bsw_refbatch_*             the exact 256 KiB task batch / 16 KiB result
  *                              batch wire format (bwa_mem_sw.v:163-170)
+ *   bsw_cigar_ref_batch        bwa_gen_cigar2 (+ mem_reg2aln's retries) against the
+ *                              device-resident reference: score, CIGAR, NM, MD
+ *                              (bwa host software, not the RTL)
  *
  * Base codes: 0..3 = A,C,G,T; 4 = N; one base per byte, exactly as bwa passes
  * them to ksw_extend.  Left-extension query/target must already be reversed by
@@ -291,6 +294,48 @@ int ksw_global2(int qlen, const uint8_t *query, int tlen, const uint8_t *target,
                 int o_del, int e_del, int o_ins, int e_ins, int w, int *n_cigar, uint32_t **cigar);
 int ksw_global(int qlen, const uint8_t *query, int tlen, const uint8_t *target, int m, const int8_t *mat,
                int gapo, int gape, int w, int *n_cigar, uint32_t **cigar);
+
+/* ---- bwa_gen_cigar2 against a DEVICE-RESIDENT reference (bwa.c; mem_reg2aln's band-widening loop around it, bwamem.c):
+ * reads plus reference intervals go in, score, CIGAR, NM and MD come back.  The target [rb, re) is fetched on the GPU from
+ * the reference of bsw_ref_upload (reverse strand: the read and the target are both reversed, as bwa does, so indels sit
+ * leftmost and the CIGAR / MD are in that reversed frame), the band follows bwa's formula, ksw_global2 runs on the GPU and
+ * NM / MD are computed there from the CIGAR.  Only the reads cross PCIe.  The whole batch runs on the context's first device.
+ * Retry (mem_reg2aln):  w2 = w; last = -(1 << 30);
+ *     do { w2 = min(w2, w_cap); bwa_gen_cigar2(w_ = w2); if (score == last || w2 == w_cap) break; last = score; w2 <<= 1; }
+ *     while (++i < max_tries && score < min_score);
+ * the outputs are those of the final try. ---- */
+struct bsw_ref;                /* (bsw_ref_upload, below) */
+typedef struct bsw_ctask {
+    const uint8_t *query;    /* read bases [qb, qe) in read order, codes 0..4 (bwa passes &query[qb])                */
+    int32_t  l_query;        /* qe - qb, <= BSW_GLOBAL_MAX_QLEN                                                     */
+    int32_t  w;              /* w_ of the first try (0..BSW_MAX_TLEN)                                               */
+    int64_t  rb, re;         /* reference interval in bwa coordinates [0, 2*l_pac); re - rb <= BSW_MAX_TLEN          */
+    int32_t  w_cap;          /* retries never exceed this band (0: = w, i.e. no widening)                          */
+    int32_t  min_score;      /* retry while score < min_score (truesc - a in bwa); INT32_MIN: never                 */
+    int32_t  max_tries;      /* 1..3 (0 = 1 = plain bwa_gen_cigar2)                                                 */
+    int32_t  _pad;
+} bsw_ctask;                 /* 48 bytes */
+typedef struct bsw_cresult {
+    int32_t score;           /* global score of the final try (0 when status != 0)                                  */
+    int32_t n_cigar;         /* ops written; < 0: -n ops did not fit max_cigar (as bsw_global_batch)                 */
+    int32_t nm;              /* edit distance as bwa computes it; -1 when there is no CIGAR (status, CIGAR overflow)  */
+    int32_t md_len;          /* MD bytes written without the NUL; < 0: -(bytes needed, NUL included) did not fit max_md
+                                (the slot then holds ""); 0 with nm == -1.  md == NULL: the MD's length, nothing written */
+    int32_t w;               /* w_ of the final try                                                                 */
+    int32_t tries;           /* bwa_gen_cigar2 calls made, 1..max_tries                                             */
+    int32_t status;          /* 0; 1: bwa returns no alignment (l_query == 0, rb >= re, the interval bridges l_pac or
+                                leaves [0, 2*l_pac)) — such a task does not fail the batch                          */
+    int32_t _pad;
+} bsw_cresult;               /* 32 bytes */
+/* Batched bwa_gen_cigar2 (+ retries) on the GPU.  max_cigar >= 1 words per task of CIGAR room on the device and in cigars
+ * (may be NULL: not returned); md (may be NULL) receives a NUL-terminated MD string in a slot of max_md bytes per task.
+ * The first malformed task rejects the batch: negative length or band, NULL query, max_tries outside 0..3 -> BSW_E_INVAL;
+ * l_query > BSW_GLOBAL_MAX_QLEN, re - rb > BSW_MAX_TLEN, w or w_cap > BSW_MAX_TLEN -> BSW_E_LIMIT. */
+int      bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_ctask *tasks, size_t n,
+                             int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res);
+/* mem_reg2aln's infer_bw: the band a global alignment of l1 x l2 bases needs to reach `score` (a = match, q / r = gap
+ * open / extend of one kind; bwa takes the larger of the deletion and the insertion answers) */
+int      bsw_infer_bw(int l1, int l2, int score, int a, int q, int r);
 
 /* ---- local alignment with start / second-best search (second half: bwa ksw.h ksw_align2, the
  * Smith-Waterman of mate rescue, mem_matesw; like ksw_global2 it lives in the reference's host software, the

@@ -72,10 +72,12 @@ __device__ __forceinline__ int base_at(const uint64_t *__restrict__ seq, uint32_
 struct akswr { int score, te, qe, score2, te2, tb, qb; };
 
 /* One run of ksw_u8 (BYTE) / ksw_i16 for the alignment of this 16-lane row.  `on`: the row takes part (row-uniform).
- * Query position k is q[qrev ? qlast - k : k]; target row i is t[i <= trev ? trev - i : i] (trev = -1: forwards). */
+ * Query position k is q[qrev ? qlast - k : k]; target row i is t[i <= trev ? trev - i : i] (trev = -1: forwards).
+ * qrc: q is the reverse complement of the stored sequence s of qn + 1 bases, q[idx] = comp(s[qn - idx]) (mem_matesw's is_rev). */
 template <int SLEN, bool BYTE>
 __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const int tlen, const uint64_t *__restrict__ seq,
-                                            const uint32_t q_off, const int qlast, const bool qrev, const uint32_t t_off, const int trev,
+                                            const uint32_t q_off, const int qlast, const bool qrev, const bool qrc, const int qn,
+                                            const uint32_t t_off, const int trev,
                                             const int xtra, const bsw_dparams &P, const int shift, const int mx,
                                             int8_t (*prof)[SLEN][256], unsigned long long *__restrict__ bl)
 {
@@ -93,7 +95,9 @@ __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const
     for (int j = 0; j < SLEN; ++j) {
         const int k = j + l * slen;
         const bool real = on && lane_on && j < slen && k < qlen;
-        const int qc = real ? base_at(seq, q_off, qrev ? qlast - k : k) : 0;
+        const int idx = qrev ? qlast - k : k;
+        int qc = real ? base_at(seq, q_off, qrc ? qn - idx : idx) : 0;
+        if (qrc) qc = qc < 4 ? 3 - qc : 4;                           /* (a non-real lane's 0 becomes 3: its profile is 0 anyway) */
 #pragma unroll
         for (int a = 0; a < 5; ++a) prof[a][j][tid] = real ? P.mat[a * 5 + qc] : (int8_t)0;
     }
@@ -221,12 +225,14 @@ __global__ __launch_bounds__(256) void bsw_align_kernel(const bsw_dparams P, con
     for (int a = 0; a < 25; ++a) { smin = min(smin, (int)P.mat[a]); smax = max(smax, (int)P.mat[a]); }
     const int shift = (256 - (smin & 0xff)) & 0xff, mx = smax;
     unsigned long long *bl = blist + T.b_off;
-    akswr r = align_pass<SLEN, BYTE>(valid, T.qlen, T.tlen, seq, T.q_off, 0, false, T.t_off, -1, T.xtra, P, shift, mx, prof, bl);
+    const bool qrc = (T.pad & BSW_AD_QRC) != 0;
+    akswr r = align_pass<SLEN, BYTE>(valid, T.qlen, T.tlen, seq, T.q_off, 0, false, qrc, T.qlen - 1, T.t_off, -1, T.xtra, P, shift, mx,
+                                     prof, bl);
     const bool second = valid && !((T.xtra & A_XSTART) == 0 || ((T.xtra & A_XSUBO) && r.score < (T.xtra & 0xffff)));
     if (__builtin_amdgcn_ballot_w64(second) != 0) {
         /* (the profile is rebuilt for the mirrored prefix; every thread owns its column of it: no barrier) */
-        const akswr rr = align_pass<SLEN, BYTE>(second, r.qe + 1, T.tlen, seq, T.q_off, r.qe, true, T.t_off, r.te, A_XSTOP | r.score,
-                                                P, shift, mx, prof, bl);
+        const akswr rr = align_pass<SLEN, BYTE>(second, r.qe + 1, T.tlen, seq, T.q_off, r.qe, true, qrc, T.qlen - 1, T.t_off, r.te,
+                                                A_XSTOP | r.score, P, shift, mx, prof, bl);
         if (second && r.score == rr.score) { r.tb = r.te - rr.te; r.qb = r.qe - rr.qe; }
     }
     if (valid && l == 0) {

@@ -87,10 +87,11 @@ typedef struct bsw_cdtask {
 } bsw_cdtask;
 
 /* one local alignment (bsw_align_kernel.hip; SURVEY.md §8f F4: bwa ksw_align2) */
+#define BSW_AD_QRC      1u    /* the query is the reverse complement of the stored sequence (mem_matesw's is_rev) */
 typedef struct bsw_adtask {
     uint32_t q_off, t_off;    /* word offsets into seq */
     int32_t  qlen, tlen, xtra;
-    uint32_t pad;
+    uint32_t pad;             /* BSW_AD_QRC; 0 for bsw_align_batch */
     uint64_t b_off;           /* first entry of this alignment's slice of the sub-optimal list scratch */
 } bsw_adtask;
 

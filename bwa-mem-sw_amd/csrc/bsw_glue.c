@@ -117,3 +117,37 @@ int bsw_infer_bw(int l1, int l2, int score, int a, int q, int r)
     if (w < (l1 > l2 ? l1 - l2 : l2 - l1)) w = l1 > l2 ? l1 - l2 : l2 - l1;
     return w;
 }
+
+/* mem_infer_dir (bwamem_pair.c): p2 = the mate's leftmost position on the anchor's strand; orientation 0..3 = (strands
+ * differ) ^ (mate not right of the anchor ? 3 : 0) */
+int bsw_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist)
+{
+    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
+    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
+    if (dist) *dist = p2 > b1 ? p2 - b1 : b1 - p2;
+    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
+}
+
+/* mem_matesw's windows: the mate lies pes[r].low .. pes[r].high to the right of the anchor (is_larger) or to its left; on the
+ * anchor's strand the window gains l_ms bases at its far end, on the other strand at its near end */
+int bsw_matesw_windows(int64_t anchor_rb, int l_ms, int64_t l_pac, const int32_t low[4], const int32_t high[4],
+                       const int32_t failed[4], int64_t rb[4], int64_t re[4], int32_t is_rev[4], int32_t skip[4])
+{
+    int r;
+    if (!low || !high || !failed || !rb || !re || !is_rev || !skip || l_pac < 1 || l_ms < 0) return BSW_E_INVAL;
+    for (r = 0; r < 4; ++r) {
+        const int rev = (r >> 1) != (r & 1), larger = !(r >> 1);
+        if (!rev) {
+            rb[r] = larger ? anchor_rb + low[r] : anchor_rb - high[r];
+            re[r] = (larger ? anchor_rb + high[r] : anchor_rb - low[r]) + l_ms;
+        } else {
+            rb[r] = (larger ? anchor_rb + low[r] : anchor_rb - high[r]) - l_ms;
+            re[r] = larger ? anchor_rb + high[r] : anchor_rb - low[r];
+        }
+        if (rb[r] < 0) rb[r] = 0;
+        if (re[r] > l_pac << 1) re[r] = l_pac << 1;
+        is_rev[r] = rev;
+        skip[r] = failed[r] ? 1 : 0;
+    }
+    return BSW_OK;
+}

@@ -1,0 +1,184 @@
+/*
+ * bsw_matesw.hip — host of bsw_matesw_ref_batch: mem_matesw's ksw_align2 (bwamem_pair.c) against the device-resident
+ * reference (part of the host side of libbwasw_mi355.so; shared types: bsw_internal.h).
+ *
+ * Per chunk of tasks:
+ *   1. the mates cross PCIe as the caller holds them, in read order (registered memory is DMA'd as it lies, anything else is
+ *      gathered into pinned staging, neither reversed nor complemented) and bsw_pack_kernel packs them next to the windows it
+ *      fetches from the resident pac: every task is a right-side-only seed, the mate read forwards and the target fetched
+ *      upwards from rb, which is bns_get_seq on both strands;
+ *   2. bsw_align_kernel (unchanged launch, bsw_align_batch's classes) runs once per class; a task with is_rev carries
+ *      BSW_AD_QRC and the kernel builds its query profile from the reverse complement of the stored mate, in the main pass
+ *      and in the KSW_XSTART pass, so one launch per class serves both orientations;
+ *   3. mem_matesw's mapping of kswr_t to the region and its keep decision run here on the copied-back results.
+ */
+#include "bsw_internal.h"
+
+/* the pack kernel reads a word of a sequence as 20 bytes from the dword below its first byte: forwards up to 16 + 3 bytes past
+ * a mate's end */
+static_assert(RAW_FRONT >= 4 && RAW_SLACK >= 20, "raw slack of the mates");
+
+/* bwa: nothing is aligned for an empty mate, an empty window, or one bns_get_seq cannot return whole */
+static bool mtask_runs(const bsw_mtask &t, int64_t l_pac)
+{
+    return t.l_ms > 0 && t.rb < t.re && !(t.rb < l_pac && t.re > l_pac) && t.rb >= 0 && t.re <= 2 * l_pac;
+}
+
+static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                        bsw_mresult *res)
+{
+    stage_t &st = ctx->small;
+    hipStream_t s = ctx->stream0();
+    hipError_t he;
+    const int64_t l_pac = ref->l_pac;
+    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
+        (he = st.h_desc.reserve(n + 1)) != hipSuccess)
+        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    std::vector<bsw_adtask> at(n);
+    std::vector<uint8_t> runs(n);
+    const int ncls = bsw::align_class_count();
+    std::vector<uint32_t> order, cnt((size_t)ncls + 1, 0), cls(n);
+    uint64_t acc = 0, accb = 0, bacc = 0;
+    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_mtask &t = tasks[i];
+        bsw_dtask &d = st.h_tasks.p[i];
+        bsw_rawoff &r = st.h_roff.p[i];
+        bsw_refx &x = st.h_desc.p[i];
+        memset(&d, 0, sizeof(d));
+        memset(&r, 0, sizeof(r));
+        x = bsw_refx{0, 0};
+        runs[i] = mtask_runs(t, l_pac) ? 1 : 0;
+        if (!runs[i]) continue;
+        const int tlen = (int)(t.re - t.rb);
+        d.rq_off = (uint32_t)acc; acc += nwords(t.l_ms);
+        d.rt_off = (uint32_t)acc; acc += nwords(tlen);
+        d.rqlen = (uint16_t)t.l_ms; d.rtlen = (uint16_t)tlen;
+        r.rq = (uint32_t)accb; accb += (uint64_t)t.l_ms;
+        x.xr = t.rb;
+        if (t.mate < lo) lo = t.mate;
+        if (t.mate + t.l_ms > hi) hi = t.mate + t.l_ms;
+        bsw_adtask &a = at[i];
+        a.q_off = d.rq_off; a.t_off = d.rt_off; a.qlen = t.l_ms; a.tlen = tlen; a.xtra = t.xtra;
+        a.pad = t.is_rev ? BSW_AD_QRC : 0u;
+        a.b_off = bacc;
+        if (t.xtra & KSW_XSUBO) bacc += (uint64_t)tlen;
+        const int c = bsw::align_class_of(t.l_ms, (t.xtra & KSW_XBYTE) != 0);
+        cls[i] = (uint32_t)c;
+        ++cnt[(size_t)c + 1];
+    }
+    for (int c = 0; c < ncls; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
+    order.assign(cnt[(size_t)ncls], 0u);
+    {
+        std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
+        for (size_t i = 0; i < n; ++i) if (runs[i]) order[pos[cls[i]]++] = (uint32_t)i;
+    }
+    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
+    const bool direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * accb + (1u << 20) && is_registered(lo, spanb);
+    if (direct) {
+        for (size_t i = 0; i < n; ++i) if (runs[i]) st.h_roff.p[i].rq = (uint32_t)(tasks[i].mate - lo);
+    } else if (accb) {
+        if ((he = st.h_raw.reserve((size_t)accb + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+        for (size_t i = 0; i < n; ++i)
+            if (runs[i]) memcpy(st.h_raw.p + st.h_roff.p[i].rq, tasks[i].mate, (size_t)tasks[i].l_ms);
+    }
+    const size_t rawb = direct ? spanb : (size_t)accb;
+    if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
+        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
+        (he = st.d_desc.reserve(n + 1)) != hipSuccess ||
+        (he = ctx->a_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
+        (he = ctx->a_res.reserve(n + 1)) != hipSuccess || (he = ctx->a_bl.reserve((size_t)bacc + 64)) != hipSuccess)
+        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    std::vector<bsw_kswr> aln(n);
+    if (!order.empty()) {
+        if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(ctx->a_tasks.p, at.data(), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, ref->d_pac[0], l_pac, st.d_desc.p,
+                                   st.d_seq.p, nullptr, s));
+        for (int c = 0; c < ncls; ++c) {
+            const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
+            if (!k) continue;
+            HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, ctx->a_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->a_bl.p, ctx->a_res.p, s));
+        }
+        int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
+        if (rc) return rc;
+        HIPCHK(e, hipMemcpy(aln.data(), ctx->a_res.p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
+    }
+    /* mem_matesw: if (aln.score >= opt->min_seed_len && aln.qb >= 0) { b.qb = is_rev? l_ms - (aln.qe + 1) : aln.qb; ... } */
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_mtask &t = tasks[i];
+        bsw_mresult &m = res[i];
+        memset(&m, 0, sizeof(m));
+        if (!runs[i]) {
+            m.aln = bsw_kswr{0, -1, -1, -1, -1, -1, -1};
+            m.status = 1;
+            continue;
+        }
+        const bsw_kswr &a = aln[i];
+        m.aln = a;
+        if (!(a.score >= t.min_score && a.qb >= 0)) {
+            m.status = 2;
+            continue;
+        }
+        const bool rev = t.is_rev != 0;
+        m.qb = rev ? t.l_ms - (a.qe + 1) : a.qb;
+        m.qe = rev ? t.l_ms - a.qb : a.qe + 1;
+        m.rb = rev ? (l_pac << 1) - (t.rb + a.te + 1) : t.rb + a.tb;
+        m.re = rev ? (l_pac << 1) - (t.rb + a.tb) : t.rb + a.te + 1;
+        m.score = a.score;
+        m.csub = a.score2;
+        const int64_t rl = m.re - m.rb, ql = m.qe - m.qb;
+        m.seedcov = (int32_t)((rl < ql ? rl : ql) >> 1);
+    }
+    return BSW_OK;
+}
+
+extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                                    bsw_mresult *res)
+{
+    if (!ctx) return BSW_E_INVAL;
+    errs &e = ctx->err;
+    if (!p || !ref || (!tasks && n) || (!res && n)) return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: NULL argument");
+    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
+        return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: the reference was uploaded through another context");
+    int rc = busy_check(ctx, "bsw_matesw_ref_batch");
+    if (rc) return rc;
+    bsw_params pp = *p;
+    pp.w = 0; pp.variant = BSW_VARIANT_H;
+    bsw_dparams dp;
+    rc = check_params(e, &pp, &dp);
+    if (rc) return rc;
+    int mxs = 0;
+    for (int i = 0; i < 25; ++i) mxs = std::max(mxs, (int)p->mat[i]);
+    if (mxs <= 0) return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: the scoring matrix has no positive score");
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_mtask &t = tasks[i];
+        if (t.l_ms < 0) return fail(e, BSW_E_INVAL, "mate task %zu: negative length", i);
+        if (t.l_ms && !t.mate) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
+        if (t.is_rev != 0 && t.is_rev != 1) return fail(e, BSW_E_INVAL, "mate task %zu: is_rev is neither 0 nor 1", i);
+        if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "mate task %zu: unknown xtra flag", i);
+        if (t.l_ms > BSW_ALIGN_MAX_QLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
+            return fail(e, BSW_E_LIMIT, "mate task %zu: beyond BSW_ALIGN_MAX_QLEN / BSW_MAX_TLEN", i);
+    }
+    HIPCHK(e, hipSetDevice(ctx->device0()));
+    for (size_t a = 0; a < n;) {                      /* sub-batches: bsw_align_batch's bounds on the sequence arena and b[] scratch */
+        size_t b = a;
+        uint64_t sb = 0, bb = 0;
+        while (b < n && b - a < (1u << 20)) {
+            const bsw_mtask &t = tasks[b];
+            const uint64_t tl = t.re > t.rb ? (uint64_t)(t.re - t.rb) : 0;
+            if (b > a && (sb + (uint64_t)t.l_ms + tl > (1ull << 31) || bb + tl > (1ull << 28))) break;
+            sb += (uint64_t)t.l_ms + tl;
+            bb += (t.xtra & KSW_XSUBO) ? tl : 0;
+            ++b;
+        }
+        rc = matesw_chunk(ctx, e, dp, ref, tasks + a, b - a, res + a);
+        if (rc) return rc;
+        a = b;
+    }
+    return BSW_OK;
+}

@@ -42,6 +42,10 @@ CRESULT = np.dtype([("score", "<i4"), ("n_cigar", "<i4"), ("nm", "<i4"), ("md_le
 ATASK = np.dtype([("query", "<u8"), ("target", "<u8"), ("qlen", "<i4"), ("tlen", "<i4"), ("xtra", "<i4"), ("_pad", "<i4")])
 KSWR = np.dtype([("score", "<i4"), ("te", "<i4"), ("qe", "<i4"), ("score2", "<i4"), ("te2", "<i4"), ("tb", "<i4"), ("qb", "<i4")])
 KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
+MTASK = np.dtype([("mate", "<u8"), ("l_ms", "<i4"), ("is_rev", "<i4"), ("rb", "<i8"), ("re", "<i8"), ("xtra", "<i4"),
+                  ("min_score", "<i4")])
+MRESULT = np.dtype([("aln", KSWR), ("status", "<i4"), ("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"),
+                    ("score", "<i4"), ("csub", "<i4"), ("seedcov", "<i4"), ("_pad", "<i4")], align=True)
 REF_TASK = np.dtype([("query", "<u8"), ("l_query", "<i4"), ("init_score", "<i4"), ("seed", SEED),
                      ("rmax0", "<i8"), ("rmax1", "<i8"), ("tag", "<u4"), ("_pad", "<u4")])
 MAX_DEVICES = 16
@@ -57,6 +61,7 @@ RESULT_FULL, RESULT_PAIR = 0, 1
 assert PARAMS.itemsize == 68 and TASK.itemsize == 72 and EXT.itemsize == 32 and RESULT.itemsize == 96
 assert ATASK.itemsize == 32 and KSWR.itemsize == 28
 assert CTASK.itemsize == 48 and CRESULT.itemsize == 32
+assert MTASK.itemsize == 40 and MRESULT.itemsize == 72
 assert EXT_TASK.itemsize == 40 and SYNTH.itemsize == 72 and CONFIG.itemsize == 104 and PAIR.itemsize == 32 and REF_TASK.itemsize == 56
 
 REFBATCH_IN_WORDS, REFBATCH_OUT_WORDS, REFBATCH_MAX_TASKS = 65536, 4096, 819
@@ -141,6 +146,9 @@ def lib():
             "bsw_align_batch": (C.c_int, [vp, vp, vp, sz, vp]),
             "bsw_cigar_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
+            "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
+            "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+            "bsw_matesw_windows": (C.c_int, [C.c_int64, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp]),
             "ksw_global2": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp] + [C.c_int] * 5 + [vp, vp]),
             "ksw_global": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp] + [C.c_int] * 3 + [vp, vp]),
             "bsw_ref_upload": (C.c_int, [vp, vp, C.c_int64, C.POINTER(vp)]),
@@ -170,7 +178,8 @@ def lib():
     return _lib
 
 
-EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
+EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
+           "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
            "bsw_submit_packed", "bsw_upload_packed", "bsw_pack_tasks", "bsw_pack_tasks_bound",
@@ -501,6 +510,14 @@ class BswContext:
             strings = [bytes(md[i, :max(int(res["md_len"][i]), 0)]).decode("ascii") for i in range(n)]
         return res, cig, strings
 
+    def matesw_ref_batch(self, params, ref, mtasks):
+        """mem_matesw's ksw_align2 against a reference from ref_upload: the windows are fetched and the mates
+        reverse-complemented (is_rev) on the GPU.  Returns an MRESULT array."""
+        res = np.zeros(len(mtasks), dtype=MRESULT)
+        self._chk(lib().bsw_matesw_ref_batch(self.handle, params.ctypes.data, ref, mtasks.ctypes.data, len(mtasks), res.ctypes.data),
+                  "bsw_matesw_ref_batch")
+        return res
+
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""
         res = np.zeros(len(atasks), dtype=KSWR)
@@ -663,6 +680,27 @@ def pac_get_seq(pac, l_pac, beg, end):
 def infer_bw(l1, l2, score, a, q, r):
     """mem_reg2aln's infer_bw (bsw_infer_bw)."""
     return int(lib().bsw_infer_bw(l1, l2, score, a, q, r))
+
+
+def infer_dir(l_pac, b1, b2):
+    """mem_infer_dir (bsw_infer_dir): (orientation 0..3, distance)."""
+    d = C.c_int64(0)
+    r = lib().bsw_infer_dir(l_pac, b1, b2, C.byref(d))
+    return int(r), int(d.value)
+
+
+def matesw_windows(anchor_rb, l_ms, l_pac, low, high, failed):
+    """mem_matesw's windows for the four orientations (bsw_matesw_windows).  low / high / failed: four values each.
+    Returns dict of int arrays rb, re, is_rev, skip (index = orientation)."""
+    lo, hi, fa = (np.ascontiguousarray(x, dtype=np.int32) for x in (low, high, failed))
+    assert lo.size == hi.size == fa.size == 4
+    rb, re = np.zeros(4, np.int64), np.zeros(4, np.int64)
+    is_rev, skip = np.zeros(4, np.int32), np.zeros(4, np.int32)
+    rc = lib().bsw_matesw_windows(anchor_rb, l_ms, l_pac, lo.ctypes.data, hi.ctypes.data, fa.ctypes.data, rb.ctypes.data,
+                                  re.ctypes.data, is_rev.ctypes.data, skip.ctypes.data)
+    if rc:
+        raise BswError(rc, "bsw_matesw_windows")
+    return {"rb": rb, "re": re, "is_rev": is_rev, "skip": skip}
 
 
 def pack_pac(bases):

@@ -29,6 +29,8 @@
  *   bsw_cigar_ref_batch        bwa_gen_cigar2 (+ mem_reg2aln's retries) against the
  *                              device-resident reference: score, CIGAR, NM, MD
  *                              (bwa host software, not the RTL)
+ *   bsw_matesw_ref_batch       mem_matesw's ksw_align2 against the device-resident
+ *                              reference (bwa host software, not the RTL)
  *
  * Base codes: 0..3 = A,C,G,T; 4 = N; one base per byte, exactly as bwa passes
  * them to ksw_extend.  Left-extension query/target must already be reversed by
@@ -369,6 +371,47 @@ kswr_t ksw_align2(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, co
                   int o_del, int e_del, int o_ins, int e_ins, int xtra, void **qry);
 kswr_t ksw_align(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, const int8_t *mat,
                  int gapo, int gape, int xtra, void **qry);
+
+/* ---- mate rescue against a DEVICE-RESIDENT reference (bwa's mem_matesw, bwamem_pair.c): one ksw_align2 per window,
+ * the window [rb, re) fetched on the GPU from the reference of bsw_ref_upload (bns_get_seq semantics, both strands), the
+ * mate complemented and reversed on the GPU when is_rev.  Only the mates cross PCIe.  The whole batch runs on the context's
+ * first device.  mem_matesw's bookkeeping (which orientations to try, its order dependency) stays with the caller:
+ * bsw_infer_dir and bsw_matesw_windows below, INTEGRATION.md "Mate rescue".  Kept (status 0) exactly when bwa keeps the
+ * region: aln.score >= min_score && aln.qb >= 0. ---- */
+typedef struct bsw_mtask {
+    const uint8_t *mate;     /* the mate in READ order, codes 0..4 (bwa's ms)                                       */
+    int32_t  l_ms;           /* 0..BSW_ALIGN_MAX_QLEN (0: status 1, nothing run)                                     */
+    int32_t  is_rev;         /* 0 / 1: align the reverse complement of the mate (mem_matesw: r>>1 != (r&1))          */
+    int64_t  rb, re;         /* the window in bwa coordinates [0, 2*l_pac), as the caller would fetch it; re - rb <=
+                                BSW_MAX_TLEN                                                                          */
+    int32_t  xtra;           /* ksw_align2 flags | threshold, as mem_matesw builds them                              */
+    int32_t  min_score;      /* keep the region when score >= min_score && qb >= 0 (bwa: opt->min_seed_len)          */
+} bsw_mtask;                 /* 40 bytes */
+typedef struct bsw_mresult {
+    bsw_kswr aln;            /* ksw_align2's outputs in the window's frame (query = the mate as aligned, reverse-
+                                complemented when is_rev), bit for bit; status 1: {0, -1, -1, -1, -1, -1, -1}          */
+    int32_t  status;         /* 0 kept; 1 not run (l_ms == 0, rb >= re, the window bridges l_pac or leaves
+                                [0, 2*l_pac)) -- such a task does not fail the batch; 2 run, not kept                */
+    int64_t  rb, re;         /* mem_matesw's b.rb / b.re (bwa coordinates); status 0 only, else 0                      */
+    int32_t  qb, qe;         /* b.qb / b.qe in the mate's read order; status 0 only, else 0                           */
+    int32_t  score, csub;    /* b.score = aln.score, b.csub = aln.score2; status 0 only, else 0                        */
+    int32_t  seedcov;        /* min(re - rb, qe - qb) >> 1; status 0 only, else 0                                     */
+    int32_t  _pad;
+} bsw_mresult;               /* 72 bytes */
+/* Batched mem_matesw Smith-Waterman on the GPU (m = 5; p supplies mat and the four gap penalties).  The first malformed task
+ * rejects the batch: negative l_ms, NULL mate, is_rev other than 0 / 1, an unknown xtra flag -> BSW_E_INVAL;
+ * l_ms > BSW_ALIGN_MAX_QLEN or re - rb > BSW_MAX_TLEN -> BSW_E_LIMIT. */
+int      bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                              bsw_mresult *res);
+/* mem_infer_dir: the orientation (0..3) of a pair whose leftmost positions are b1 (anchor) and b2 (mate), and in *dist the
+ * distance between them on the anchor's strand */
+int      bsw_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist);
+/* mem_matesw's windows for the four orientations r of an anchor at anchor_rb and a mate of l_ms bases, from the insert size
+ * bounds low[r] / high[r] of bwa's mem_pestat_t: rb[r], re[r] clamped to [0, 2*l_pac) (the window may come out empty),
+ * is_rev[r] = r>>1 != (r&1), skip[r] = failed[r] != 0.  The contig clamp of newer bwa's bns_fetch_seq and its rid check stay
+ * with the caller.  Returns BSW_OK, or BSW_E_INVAL for NULL arrays, l_pac < 1 or l_ms < 0. */
+int      bsw_matesw_windows(int64_t anchor_rb, int l_ms, int64_t l_pac, const int32_t low[4], const int32_t high[4],
+                            const int32_t failed[4], int64_t rb[4], int64_t re[4], int32_t is_rev[4], int32_t skip[4]);
 
 /* ---- device-resident batches (inputs in HBM before the timed region) ------- */
 int      bsw_upload(bsw_ctx *ctx, const bsw_params *p, const bsw_task *tasks, size_t n, bsw_dev_batch **out);

@@ -909,6 +909,63 @@ static int stage_device(errs &e, stage_t &st, hipStream_t s, const chunk_info &c
     return BSW_OK;
 }
 
+/* The device's rules (bsw_bin_count/scan/scatter) replayed on the host: lists by class, lane sides by (class, query with /
+ * without an N, query length descending, left sides: h0 bucket ascending); the order inside one bin is task order here,
+ * arbitrary there.  dt: the chunk's task records; nflag[i] bit 0 / 1: the left / right query of seed i holds an N; order:
+ * bsw_plan_order_capacity(n) words.  Returns the length of the N list (bsw_binparams.nsplit; 0 without it).  One function for
+ * bsw_plan_batch and for the tests' CPU stand-in of launch_bin. */
+BSW_LOCAL uint32_t plan_fill_order(const bsw_binparams &bp, const bsw_dtask *dt, size_t n, const uint8_t *nflag, uint32_t *order)
+{
+    std::vector<uint32_t> cur(BSW_BIN_WORDS, 0), hist(BSW_BIN_WAVE0, 0);
+    auto keys = [&](size_t i, int &k0, int &k1, int &k2) {
+        const bsw_dtask &T = dt[i];
+        const int nl = nflag[i] & 1, nr = (nflag[i] >> 1) & 1;
+        k1 = k2 = -1;
+        const int bits = bsw_seed_lane_bits(&bp, T.lqlen, T.rqlen, T.h0);
+        if (!bits) { k0 = BSW_BIN_WAVE0 + bsw_wave_class_of(&bp, std::max(T.lqlen, T.rqlen)); return; }
+        k0 = BSW_BIN_LANEALL;
+        if (bp.nsplit && bits == 8 && (nl | nr)) { k0 = BSW_BIN_NLIST; return; }
+        const bool fz = bp.fused && bits == 8;
+        if (fz) k1 = BSW_BIN_L(0, nl | (bp.fused == 1 ? nr : 0), bsw_h0_bucket(&bp, T.h0), T.lqlen);
+        else if (T.lqlen) k1 = BSW_BIN_L(bits == 16, nl, bsw_h0_bucket(&bp, T.h0), T.lqlen);
+        if (T.rqlen && !fz) k2 = BSW_BIN_R(bits == 16, nr, T.rqlen);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        int k0, k1, k2;
+        keys(i, k0, k1, k2);
+        if (k1 >= 0) ++hist[(size_t)k1];
+        if (k2 >= 0) ++hist[(size_t)k2];
+    }
+    for (int side = 0; side < 2; ++side)
+        for (int c = 0; c < bp.n_lane; ++c) {
+            uint32_t run = side ? bp.laneR_off[c] : bp.laneL_off[c];
+            const int bits = bp.lane_bits[c], b16 = bits == 16;
+            for (int hn = 1; hn >= 0; --hn)
+                for (int q = BSW_LANE_QBINS - 1; q >= 0; --q) {
+                    if (bsw_side_lane_class(&bp, bits, q) != c) continue;
+                    for (int hb = 0; hb < (side ? 1 : BSW_H0_BUCKETS); ++hb) {
+                        const size_t idx = (size_t)(side ? BSW_BIN_R(b16, hn, q) : BSW_BIN_L(b16, hn, hb, q));
+                        cur[idx] = run;
+                        run += hist[idx];
+                    }
+                }
+        }
+    for (int c = 0; c < bp.n_wave; ++c) cur[(size_t)(BSW_BIN_WAVE0 + c)] = bp.wave_start[c];
+    cur[BSW_BIN_LANEALL] = bp.lane_all_off;
+    cur[BSW_BIN_NLIST] = bp.nlist_off;
+    if (bp.nsplit) for (uint32_t q = 0; q < bp.fill_len; ++q) order[bp.fill_off + q] = BSW_ORDER_NONE;
+    for (size_t i = 0; i < n; ++i) {
+        int k0, k1, k2;
+        keys(i, k0, k1, k2);
+        order[cur[(size_t)k0]++] = (uint32_t)i;
+        if (k1 >= 0) order[cur[(size_t)k1]++] = (uint32_t)i;
+        if (k2 >= 0) order[cur[(size_t)k2]++] = (uint32_t)i;
+    }
+    return bp.nsplit ? cur[BSW_BIN_NLIST] - bp.nlist_off : 0u;
+}
+
+extern "C" size_t bsw_plan_order_capacity(size_t n) { return order_capacity(n); }
+
 /* ---- batch plan export (host only) ---------------------------------------------------------- */
 static void plan_segments(const batch_plan &pl, uint32_t *seg)
 {
@@ -937,67 +994,35 @@ extern "C" int64_t bsw_plan_batch(const bsw_params *p, const bsw_task *tasks, si
     if (rc) return rc;
     plan_segments(ci.plan, seg);
     if (order) {
-        /* the device's rules (bsw_bin_count/scan/scatter) replayed on the host: lists by class, lane sides by
-         * (class, query with / without an N, query length descending, left sides: h0 bucket ascending); the order inside one
-         * bin is task order here, arbitrary there */
-        const bsw_binparams &bp = ci.bp;
-        std::vector<uint32_t> cur(BSW_BIN_WORDS, 0), hist(BSW_BIN_WAVE0, 0);
+        /* which queries hold an N, read from the caller's bases (the device reads them off the packed words) */
+        std::vector<uint8_t> nflag(n ? n : 1);
         auto has_n = [](const uint8_t *q, int len) {
             for (int j = 0; j < len; ++j)
                 if (q[j] >= 4) return 1;
             return 0;
         };
-        auto keys = [&](size_t i, int &k0, int &k1, int &k2) {
-            const bsw_dtask &T = dt[i];
-            k1 = k2 = -1;
-            const int bits = bsw_seed_lane_bits(&bp, T.lqlen, T.rqlen, T.h0);
-            if (!bits) { k0 = BSW_BIN_WAVE0 + bsw_wave_class_of(&bp, std::max(T.lqlen, T.rqlen)); return; }
-            k0 = BSW_BIN_LANEALL;
-            if (bp.nsplit && bits == 8 && (has_n(tasks[i].lquery, T.lqlen) | has_n(tasks[i].rquery, T.rqlen))) { k0 = BSW_BIN_NLIST; return; }
-            const bool fz = bp.fused && bits == 8;
-            if (fz) k1 = BSW_BIN_L(0, has_n(tasks[i].lquery, T.lqlen) | (bp.fused == 1 ? has_n(tasks[i].rquery, T.rqlen) : 0), bsw_h0_bucket(&bp, T.h0), T.lqlen);
-            else if (T.lqlen) k1 = BSW_BIN_L(bits == 16, has_n(tasks[i].lquery, T.lqlen), bsw_h0_bucket(&bp, T.h0), T.lqlen);
-            if (T.rqlen && !fz) k2 = BSW_BIN_R(bits == 16, has_n(tasks[i].rquery, T.rqlen), T.rqlen);
-        };
-        for (size_t i = 0; i < n; ++i) {
-            int k0, k1, k2;
-            keys(i, k0, k1, k2);
-            if (k1 >= 0) ++hist[(size_t)k1];
-            if (k2 >= 0) ++hist[(size_t)k2];
-        }
-        for (int side = 0; side < 2; ++side)
-            for (int c = 0; c < bp.n_lane; ++c) {
-                uint32_t run = side ? bp.laneR_off[c] : bp.laneL_off[c];
-                const int bits = bp.lane_bits[c], b16 = bits == 16;
-                for (int hn = 1; hn >= 0; --hn)
-                    for (int q = BSW_LANE_QBINS - 1; q >= 0; --q) {
-                        if (bsw_side_lane_class(&bp, bits, q) != c) continue;
-                        for (int hb = 0; hb < (side ? 1 : BSW_H0_BUCKETS); ++hb) {
-                            const size_t idx = (size_t)(side ? BSW_BIN_R(b16, hn, q) : BSW_BIN_L(b16, hn, hb, q));
-                            cur[idx] = run;
-                            run += hist[idx];
-                        }
-                    }
-            }
-        for (int c = 0; c < bp.n_wave; ++c) cur[(size_t)(BSW_BIN_WAVE0 + c)] = bp.wave_start[c];
-        cur[BSW_BIN_LANEALL] = bp.lane_all_off;
-        cur[BSW_BIN_NLIST] = bp.nlist_off;
-        if (bp.nsplit) for (uint32_t q = 0; q < bp.fill_len; ++q) order[bp.fill_off + q] = BSW_ORDER_NONE;
-        for (size_t i = 0; i < n; ++i) {
-            int k0, k1, k2;
-            keys(i, k0, k1, k2);
-            order[cur[(size_t)k0]++] = (uint32_t)i;
-            if (k1 >= 0) order[cur[(size_t)k1]++] = (uint32_t)i;
-            if (k2 >= 0) order[cur[(size_t)k2]++] = (uint32_t)i;
-        }
+        for (size_t i = 0; i < n; ++i) nflag[i] = (uint8_t)(has_n(tasks[i].lquery, tasks[i].lqlen) | (has_n(tasks[i].rquery, tasks[i].rqlen) << 1));
+        (void)plan_fill_order(ci.bp, dt.data(), n, nflag.data(), order);
     }
     return (int64_t)ci.words;
 }
 
 /* ---- device-resident batches ------------------------------------------------ */
+/* batches of a context that is dead: kept, not freed (see bsw_free_batch) */
+static std::mutex g_grave_mu;
+static std::vector<bsw_dev_batch *> *g_graveyard = new std::vector<bsw_dev_batch *>();      /* (never destroyed, so never freed behind a DMA at exit either) */
+
 extern "C" void bsw_free_batch(bsw_ctx *ctx, bsw_dev_batch *b)
 {
     if (!b) return;
+    if (ctx && ctx->dead) {
+        /* a wait for the GPU timed out: copies and kernels that address these buffers may still be queued.  Freeing them would hand
+         * their memory to someone else under a DMA, and hipFree waits for the device, which is exactly what did not come back.  The
+         * batch is kept for the life of the process, as bsw_destroy keeps the dead context's streams and staging. */
+        std::lock_guard<std::mutex> lk(g_grave_mu);
+        g_graveyard->push_back(b);
+        return;
+    }
     if (ctx) (void)hipSetDevice(ctx->device0());
     b->st.release();
     delete b->ci;
@@ -1538,7 +1563,8 @@ struct pipeline {
     std::condition_variable cv_work, cv_done;
     std::vector<std::unique_ptr<dev_pipe>> devs;
     std::vector<std::thread> threads;
-    std::deque<std::unique_ptr<ticket_t>> live; /* submits not collected by a wait yet, oldest first */
+    std::deque<std::shared_ptr<ticket_t>> live; /* submits not collected by a wait yet, oldest first (shared: a thread blocked in
+                                                   bsw_wait_ticket keeps its ticket alive while bsw_wait collects it) */
     uint64_t next_id = 1;
     bool stop = false;
     /* what the host side costs (bsw_host_stats): CPU time of the slot threads and of the gather helpers they start, volume */
@@ -1547,7 +1573,7 @@ struct pipeline {
 
 static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
 {
-    pipeline &pp = *ctx->pipe;
+    pipeline &pp = *ctx->pipe.load();
     dev_pipe &dq = *pp.devs[d];
     dev_state &dev = ctx->devs[d];
     stage_t &st = dev.slots[s];
@@ -1557,7 +1583,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
     /* the slot's thread (and the gather threads it starts, which inherit the mask) next to its GPU: the host pass streams the
      * caller's task array into write-combined pinned staging, and that staging is allocated — first touched — from here */
     pin_this_thread(dev);
-    const hipError_t dev_err = hipSetDevice(dev.device);
+    hipError_t dev_err = hipSetDevice(dev.device);
     /* BSW_RESULT_PAIR: `out` addresses bsw_pair[n]; the dense 32-byte records come from their own device array */
     const bool pairs = ctx->cfg.result_format == BSW_RESULT_PAIR;
     const size_t rec = pairs ? sizeof(bsw_pair) : sizeof(bsw_result);
@@ -1602,6 +1628,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
     auto process = [&](const chunk_job &job) {
         ticket_t *t = job.t;
         const size_t n = job.span.cnt, base = job.span.base;
+        const uint64_t tid = t->id;                  /* (read while the ticket is certainly alive: see chunk_done below) */
         const bsw_params &p = t->p;
         const bsw_task *ct = t->tasks ? t->tasks + base : nullptr;
         errs e;
@@ -1616,7 +1643,11 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
          * pack_threads spread over its slots, at least two */
         const int pass_threads = std::max(2, ctx->cfg.pack_threads / (int)dev.slots.size() + 1);
         do {
-            if (dev_err != hipSuccess) { rc = fail(e, BSW_E_HIP, "hipSetDevice: %s", hipGetErrorString(dev_err)); break; }
+            if (dev_err != hipSuccess) {            /* this chunk fails; the slot tries again for its next one instead of failing every chunk it is ever given */
+                rc = fail(e, BSW_E_HIP, "hipSetDevice: %s", hipGetErrorString(dev_err));
+                dev_err = hipSetDevice(dev.device);
+                break;
+            }
             if (t->abort) { rc = fail(e, BSW_E_HIP, "aborted: another chunk failed"); break; }
             if (pend.active && (rc = wait_event(ctx, e, dev.h2d_done[s]))) break;           /* pinned host staging is free again */
             t1 = dbg ? tnow() : 0;
@@ -1699,10 +1730,10 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
             }
             if (queued) { errs quiet; (void)sync_stream(ctx, quiet, stream, dev.events[s]); }
             ticket_fail(t, rc, e);
-            chunk_done(t);
+            chunk_done(t);                          /* (the ticket may be collected and freed from here on: tid was copied above) */
         }
         if (dbg) fprintf(stderr, "[bsw] slot %zu.%zu ticket %llu chunk @%zu n=%zu: wait staging %.3f ms, host pass %.3f, wait prev results %.3f, DMA turn + enqueue %.3f (t0=%.3f)%s\n",
-                         d, s, (unsigned long long)t->id, base, n, t1 - t0, t2 - t1, t3 - t2, tnow() - t3, t0, rc ? " FAILED" : "");
+                         d, s, (unsigned long long)tid, base, n, t1 - t0, t2 - t1, t3 - t2, tnow() - t3, t0, rc ? " FAILED" : "");
     };
 
     std::unique_lock<std::mutex> lk(pp.mu);
@@ -1731,6 +1762,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
 
 static int pipeline_start(bsw_ctx *ctx)
 {
+    std::lock_guard<std::mutex> lk(ctx->pipe_mu);    /* (the first submits of several threads may arrive together) */
     if (ctx->pipe) return BSW_OK;
     pipeline *pp = new pipeline();
     const size_t G = ctx->devs.size(), S = (size_t)ctx->cfg.streams;
@@ -1743,9 +1775,10 @@ static int pipeline_start(bsw_ctx *ctx)
 
 BSW_LOCAL bool pipeline_busy(bsw_ctx *ctx)
 {
-    if (!ctx->pipe) return false;
-    std::lock_guard<std::mutex> lk(ctx->pipe->mu);
-    return !ctx->pipe->live.empty();
+    pipeline *pp = ctx->pipe;
+    if (!pp) return false;
+    std::lock_guard<std::mutex> lk(pp->mu);
+    return !pp->live.empty();
 }
 
 BSW_LOCAL void pipeline_shutdown(bsw_ctx *ctx)
@@ -1768,14 +1801,15 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
                          size_t n, bsw_result *out, bool packed, bsw_ticket *ticket, const char *what)
 {
     if (ticket) *ticket = 0;
-    if (ctx->dead) return fail(ctx->err, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what);
+    errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
     bsw_dparams dp;
-    int rc = check_params(ctx->err, p, &dp);
-    if (rc) return rc;
+    int rc = check_params(e, p, &dp);
+    if (rc) return ctx_fail(ctx, e, rc);
     if ((rc = pipeline_start(ctx))) return rc;
-    pipeline &pp = *ctx->pipe;
+    pipeline &pp = *ctx->pipe.load();
     const size_t G = ctx->devs.size();
-    std::unique_ptr<ticket_t> t(new ticket_t());
+    std::shared_ptr<ticket_t> t(new ticket_t());
     t->p = *p; t->dp = dp; t->tasks = tasks; t->ref = ref; t->rtasks = rtasks; t->out = out; t->packed = packed; t->n = n;
     /* chunk_tasks = 0 (the default): sized by WORK, not by seeds.  A chunk's launches must fill the machine — 128 Ki seeds of
      * the 150 bp single bin (131-base sides) do; PE seeds with their two shorter sides hold half the cells per seed and want
@@ -1814,7 +1848,7 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
     {
         std::lock_guard<std::mutex> lk(pp.mu);
         if (pp.live.size() >= BSW_MAX_INFLIGHT)
-            return fail(ctx->err, BSW_E_BUSY, "%s: %d submits in flight already (BSW_MAX_INFLIGHT); wait for one first", what, BSW_MAX_INFLIGHT);
+            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "%s: %d submits in flight already (BSW_MAX_INFLIGHT); wait for one first", what, BSW_MAX_INFLIGHT));
         t->id = pp.next_id++;
         if (ticket) *ticket = t->id;
         /* chunk c of the submit -> device c mod G; the devices' queues are filled in the submit's own chunk order */
@@ -1871,7 +1905,7 @@ extern "C" int bsw_wait(bsw_ctx *ctx)
     pp->cv_done.wait(lk, [&]() { for (auto &t : pp->live) if (!t->done) return false; return true; });
     int rc = BSW_OK;
     for (auto &t : pp->live)
-        if (t->rc && !rc) { rc = t->rc; ctx->err = t->err; }
+        if (t->rc && !rc) { rc = t->rc; ctx_fail(ctx, t->err, rc); }
     pp->live.clear();
     return rc;
 }
@@ -1879,17 +1913,22 @@ extern "C" int bsw_wait(bsw_ctx *ctx)
 extern "C" int bsw_wait_ticket(bsw_ctx *ctx, bsw_ticket ticket)
 {
     if (!ctx) return BSW_E_INVAL;
+    errs e;
     pipeline *pp = ctx->pipe;
-    if (!pp) return fail(ctx->err, BSW_E_INVAL, "bsw_wait_ticket: no such ticket");
+    if (!pp) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_wait_ticket: no such ticket"));
     std::unique_lock<std::mutex> lk(pp->mu);
     auto find = [&]() { for (size_t i = 0; i < pp->live.size(); ++i) if (pp->live[i]->id == ticket) return (long)i; return -1L; };
     long i = find();
-    if (i < 0) return fail(ctx->err, BSW_E_INVAL, "bsw_wait_ticket: no such ticket (%llu)", (unsigned long long)ticket);
-    ticket_t *t = pp->live[(size_t)i].get();
+    if (i < 0) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_wait_ticket: no such ticket (%llu)", (unsigned long long)ticket));
+    /* the list may change while this thread sleeps (other tickets collected, this one collected by a bsw_wait or by a second
+     * bsw_wait_ticket on the same ticket): the ticket is held, and looked up again, not remembered by position */
+    const std::shared_ptr<ticket_t> t = pp->live[(size_t)i];
     pp->cv_done.wait(lk, [&]() { return t->done; });
+    i = find();
+    if (i < 0) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_wait_ticket: ticket %llu was collected by another wait", (unsigned long long)ticket));
     const int rc = t->rc;
-    if (rc) ctx->err = t->err;
-    pp->live.erase(pp->live.begin() + find());
+    if (rc) ctx_fail(ctx, t->err, rc);
+    pp->live.erase(pp->live.begin() + i);
     return rc;
 }
 
@@ -1904,15 +1943,17 @@ extern "C" int bsw_test(bsw_ctx *ctx, bsw_ticket ticket)
         for (auto &t : pp->live)
             if (t->id == ticket) return t->done ? 1 : 0;
     }
-    return fail(ctx->err, BSW_E_INVAL, "bsw_test: no such ticket (%llu)", (unsigned long long)ticket);
+    errs e;
+    return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_test: no such ticket (%llu)", (unsigned long long)ticket));
 }
 
 extern "C" int bsw_inflight(bsw_ctx *ctx)
 {
     if (!ctx) return BSW_E_INVAL;
-    if (!ctx->pipe) return 0;
-    std::lock_guard<std::mutex> lk(ctx->pipe->mu);
-    return (int)ctx->pipe->live.size();
+    pipeline *pp = ctx->pipe;
+    if (!pp) return 0;
+    std::lock_guard<std::mutex> lk(pp->mu);
+    return (int)pp->live.size();
 }
 
 extern "C" int bsw_host_stats(bsw_ctx *ctx, bsw_stats *out, size_t out_size)
@@ -1920,7 +1961,7 @@ extern "C" int bsw_host_stats(bsw_ctx *ctx, bsw_stats *out, size_t out_size)
     if (!ctx || !out || out_size < sizeof(uint64_t)) return BSW_E_INVAL;
     bsw_stats s;
     memset(&s, 0, sizeof(s));
-    if (pipeline *pp = ctx->pipe) {
+    if (pipeline *pp = ctx->pipe.load()) {
         s.slot_cpu_ns = pp->slot_cpu_ns; s.helper_cpu_ns = pp->helper_cpu_ns; s.seeds = pp->seeds; s.chunks = pp->chunks;
         s.h2d_bytes = pp->h2d_bytes; s.d2h_bytes = pp->d2h_bytes; s.submits = pp->submits; s.slot_threads = pp->threads.size();
     }

@@ -277,8 +277,11 @@ struct bsw_ctx {
     size_t hist_used = 0;
     hipEvent_t ev_last0 = nullptr, ev_last1 = nullptr;
     errs err;
+    /* the ticket calls (bsw_submit*_t, bsw_wait_ticket, bsw_test, bsw_wait, bsw_inflight) may come from several threads at once:
+     * THEY set err under err_mu (ctx_fail); every other call belongs to one thread at a time and writes it directly */
+    std::mutex err_mu, pipe_mu;
     /* async submits: persistent slot threads behind a chunk queue (bsw_batch.hip), started by the first submit */
-    struct pipeline *pipe = nullptr;
+    std::atomic<struct pipeline *> pipe{nullptr};
     /* small synchronous batches (bsw_extend_batch, scalar ABI, wire format) */
     stage_t small;
     /* banded global alignment (F4) */
@@ -296,6 +299,14 @@ struct bsw_ctx {
     int device0() const { return devs[0].device; }
     hipStream_t stream0() const { return devs[0].streams[0]; }
 };
+
+/* the context's error text from a call that other threads may be making too; returns rc */
+inline int ctx_fail(bsw_ctx *ctx, const errs &e, int rc)
+{
+    std::lock_guard<std::mutex> lk(ctx->err_mu);
+    ctx->err = e;
+    return rc;
+}
 
 struct chunk_info;
 struct bsw_dev_batch {
@@ -356,6 +367,7 @@ struct gate_turn {                    /* this chunk's place in its device's inpu
     bool *passed = nullptr;           /* set once the turn has been passed on */
 };
 BSW_LOCAL size_t order_capacity(size_t n);
+BSW_LOCAL uint32_t plan_fill_order(const bsw_binparams &bp, const bsw_dtask *dt, size_t n, const uint8_t *nflag, uint32_t *order);
 /* AUTO policy of a chunk once its seeds are counted: lane bins (128 seeds per wavefront), the group kernel (16 per wavefront;
  * returns true — the 16-bit seeds then leave the lane lists for the general kernel: cw16 = their count per wave class, n16
  * their number) or no lane launches at all (bp.lane_on = 0).  group_ok: the scoring parameters allow the packed kernels. */

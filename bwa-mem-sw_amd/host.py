@@ -157,6 +157,7 @@ def lib():
             "bsw_extend_ref": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_submit_ref": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_plan_batch": (C.c_int64, [vp, vp, sz, C.c_int, C.c_int, vp, vp]),
+            "bsw_plan_order_capacity": (sz, [sz]),
             "bsw_pack_bases": (C.c_int, [vp, C.c_int, vp]),
             "bsw_cal_max_gap": (C.c_int, [vp, C.c_int]),
             "bsw_chain_window": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int64, vp]),
@@ -189,7 +190,7 @@ EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch
            "bsw_last_run_ms", "bsw_run_history", "bsw_free_batch", "bsw_refbatch_encode", "bsw_refbatch_decode",
            "bsw_refbatch_encode_results", "bsw_refbatch_decode_results", "bsw_refbatch_run",
            "bsw_ref_upload", "bsw_ref_free", "bsw_upload_ref", "bsw_extend_ref", "bsw_submit_ref",
-           "bsw_plan_batch", "bsw_pack_bases", "bsw_cal_max_gap", "bsw_chain_window", "bsw_seed_scratch_bytes", "bsw_seed_to_task",
+           "bsw_plan_batch", "bsw_plan_order_capacity", "bsw_pack_bases", "bsw_cal_max_gap", "bsw_chain_window", "bsw_seed_scratch_bytes", "bsw_seed_to_task",
            "bsw_result_to_alnreg", "bsw_pac_get_seq", "bsw_synth_generate", "bsw_synth_arena_bound", "bsw_synth_ref_generate"]
 
 
@@ -526,7 +527,7 @@ class BswContext:
 
     def batch_order(self, batch):
         """Launch order the device-side binning produced (order, seg) — same layout as plan_batch."""
-        order = np.zeros(4 * batch.n + 16, dtype=np.uint32)
+        order = np.zeros(int(lib().bsw_plan_order_capacity(batch.n)), dtype=np.uint32)
         seg = np.zeros(PLAN_SEGS + 1, dtype=np.uint32)
         self._chk(lib().bsw_batch_order(self.handle, batch.handle, order.ctypes.data, seg.ctypes.data), "bsw_batch_order")
         return order, seg
@@ -650,7 +651,7 @@ PLAN_SEGS = 26
 def plan_batch(params, tasks, kernel=KERNEL_AUTO, pack_threads=1):
     """Batch manager's launch plan for a task batch (host only; the order is the host replay of the device's
     binning rules).  Returns (order, seg, seq_words)."""
-    order = np.zeros(5 * len(tasks) + 32, dtype=np.uint32)
+    order = np.zeros(int(lib().bsw_plan_order_capacity(len(tasks))), dtype=np.uint32)
     seg = np.zeros(PLAN_SEGS + 1, dtype=np.uint32)
     w = lib().bsw_plan_batch(params.ctypes.data, tasks.ctypes.data, len(tasks), kernel, pack_threads, order.ctypes.data, seg.ctypes.data)
     if w < 0:

@@ -235,7 +235,18 @@ int      bsw_host_unregister(void *p);
  * Up to BSW_MAX_INFLIGHT submits may be in flight per context (the reference's manager keeps four task batches
  * going: batch_manager.v:343-348 request bits, :434-435 busy bitmap); their chunks run through the context's slots in
  * submit order, so the tail of one overlaps the head of the next.  One more than that answers BSW_E_BUSY.
- * bsw_wait waits for ALL of them and returns the first failure in submit order. */
+ * bsw_wait waits for ALL of them and returns the first failure in submit order.
+ *
+ * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called
+ * on ONE context from several threads at once, the first submit included; every other call that takes the context
+ * (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free, bsw_host_stats) needs it to itself.
+ *   - A ticket belongs to whoever collects it first.  bsw_wait collects every submit in flight when it is called, other threads'
+ *     too; a thread blocked in bsw_wait_ticket on a ticket that bsw_wait (or a second bsw_wait_ticket) collects meanwhile returns
+ *     BSW_E_INVAL once that submit is complete: its results are in out[], its error code went to the collector.
+ *     bsw_test answers < 0 for a collected ticket.
+ *   - BSW_E_BUSY from a submit (BSW_MAX_INFLIGHT in flight) changes nothing: collect a ticket and submit again.
+ *   - bsw_last_error is one text per context: with several threads it describes the last failure of ANY of them, and the
+ *     pointer is good until the next failing call; read it only while no other thread is inside a call on the context. */
 #define BSW_MAX_INFLIGHT 4
 typedef uint64_t bsw_ticket;            /* names one submit; never 0 */
 int      bsw_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_task *tasks, size_t n, bsw_result *out);
@@ -429,8 +440,9 @@ int      bsw_run_history2(bsw_ctx *ctx, float *total_ms, float *staging_ms /* ma
 int      bsw_sync(bsw_ctx *ctx);                            /* hipStreamSynchronize        */
 int      bsw_download(bsw_ctx *ctx, bsw_dev_batch *b, bsw_result *out); /* task order      */
 int      bsw_batch_info(const bsw_dev_batch *b, uint64_t *n_tasks, uint64_t *in_bytes, uint64_t *out_bytes, uint64_t *n_launches);
-/* the launch order the device-side binning produced for a resident batch (same layout as bsw_plan_batch:
- * order[] capacity 4*n+16, seg[BSW_PLAN_SEGS+1]); for tests and tools */
+/* the launch order the device-side binning produced for a resident batch (same layout as bsw_plan_batch, up to the redo
+ * list: seg[25] <= 4*n words are written; order[] of bsw_plan_order_capacity(n) words always holds them; seg[BSW_PLAN_SEGS+1]);
+ * for tests and tools */
 int      bsw_batch_order(bsw_ctx *ctx, const bsw_dev_batch *b, uint32_t *order, uint32_t *seg);
 /* time of the kernels of the last bsw_run, measured with hipEvents on the
  * library's own stream; valid after bsw_sync.                                  */
@@ -442,7 +454,9 @@ void     bsw_free_batch(bsw_ctx *ctx, bsw_dev_batch *b);
 
 /* ---- batch plan (host only, no GPU needed): how the batch manager cuts tasks[0..n) into launches.
  * The device sorts the seeds (bsw_stage_kernel.hip); the host only counts them per class, with the same
- * class functions, to size the launches.  order[] (capacity 4*n+16, may be NULL) receives a launch order
+ * class functions, to size the launches.  order[] (capacity bsw_plan_order_capacity(n) words = 5*n+32, may be NULL: behind the
+ * redo space a chunk that does not fill the machine keeps a list of its lane seeds with an N in a query, n more words that
+ * seg[] does not describe; an array of 4*n+16 words, the size this header used to give, is overrun by such a plan) receives a launch order
  * built on the host with the device's rules (lane sides: queries with an N first, each part longest first, left
  * sides of one length by h0 bucket — 8 buckets over the chunk's h0 range; inside one bin the device's order is arbitrary);
  * seg[] receives BSW_PLAN_SEGS+1 offsets into order[]:
@@ -452,6 +466,8 @@ void     bsw_free_batch(bsw_ctx *ctx, bsw_dev_batch *b);
 #define BSW_PLAN_SEGS 26
 int64_t  bsw_plan_batch(const bsw_params *p, const bsw_task *tasks, size_t n, int kernel, int pack_threads,
                         uint32_t *order, uint32_t *seg /*[BSW_PLAN_SEGS+1]*/);
+/* words of order[] that bsw_plan_batch / bsw_batch_order may write for a batch of n tasks */
+size_t   bsw_plan_order_capacity(size_t n);
 
 /* ---- reference wire format (bwa_mem_sw.v:163-170) ----------- */
 #define BSW_REFBATCH_IN_WORDS   65536   /* 256 KiB task batch (tbb.v:59)         */

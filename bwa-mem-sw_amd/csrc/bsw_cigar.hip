@@ -146,6 +146,13 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
         (he = ctx->c_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->c_res.reserve(n + 1)) != hipSuccess ||
         (md && (he = ctx->c_md.reserve(n * (size_t)max_md + 1)) != hipSuccess))
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    /* what the tries need (declared here: the guard behind them is destroyed first) */
+    const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
+    const bool force_long = cigar_force_long();
+    std::vector<bsw_gresult> gr(n);
+    std::vector<uint32_t> order, cnt((size_t)(ncls + nlong) + 1), cls;
+    std::vector<uint32_t> live;
+    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
     if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
@@ -155,11 +162,6 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
                                st.d_seq.p, nullptr, s));
 
     /* the tries: each launches the global kernels on the tasks still in the loop, then reads their scores */
-    const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
-    const bool force_long = cigar_force_long();
-    std::vector<bsw_gresult> gr(n);
-    std::vector<uint32_t> order, cnt((size_t)(ncls + nlong) + 1), cls;
-    std::vector<uint32_t> live;
     for (size_t i = 0; i < n; ++i) if (cs[i].live) live.push_back((uint32_t)i);
     while (!live.empty()) {
         std::fill(cnt.begin(), cnt.end(), 0u);
@@ -236,6 +238,7 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
         r.status = 0;
         r._pad = 0;
     }
+    drain.done();
     return BSW_OK;
 }
 

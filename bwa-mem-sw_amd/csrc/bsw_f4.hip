@@ -80,6 +80,7 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
         (he = ctx->g_res.reserve(n + 1)) != hipSuccess || (cigars && (he = ctx->g_z.reserve((size_t)zacc + 64)) != hipSuccess) ||
         (cigars && (he = ctx->g_cig.reserve(n * (size_t)max_cigar + 1)) != hipSuccess))
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
     if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
@@ -96,6 +97,7 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
     if (rc) return rc;
     HIPCHK(e, hipMemcpy(res, ctx->g_res.p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost));
     if (cigars) HIPCHK(e, hipMemcpy(cigars, ctx->g_cig.p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    drain.done();
     return BSW_OK;
 }
 
@@ -241,6 +243,7 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
         (he = ctx->a_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
         (he = ctx->a_res.reserve(n + 1)) != hipSuccess || (he = ctx->a_bl.reserve((size_t)bacc + 64)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
     if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
@@ -255,6 +258,7 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
     int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
     if (rc) return rc;
     HIPCHK(e, hipMemcpy(out, ctx->a_res.p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
+    drain.done();
     return BSW_OK;
 }
 

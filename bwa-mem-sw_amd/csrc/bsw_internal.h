@@ -331,6 +331,25 @@ BSW_LOCAL int parse_cpulist(const char *text, cpu_set_t *out);
 BSW_LOCAL int wait_event(bsw_ctx *ctx, errs &e, hipEvent_t ev);
 BSW_LOCAL int sync_stream(bsw_ctx *ctx, errs &e, hipStream_t st, hipEvent_t ev);
 BSW_LOCAL bool is_registered(const void *p, size_t len);
+/* A synchronous batch call that fails after it has queued work must not return while that work is pending: the queued copies
+ * read the caller's registered memory and host vectors of the failing function, the queued kernels write buffers the next call
+ * reuses.  Declare it behind every host array the queued copies read (it must be destroyed before them) and call done() on
+ * the way out of a call that has waited for its work itself.  The wait is sync_stream's, watchdog included; it keeps the
+ * failure's own error text. */
+struct drain_on_failure {
+    bsw_ctx *ctx;
+    hipStream_t s;
+    hipEvent_t ev;
+    bool armed = true;
+    drain_on_failure(bsw_ctx *c, hipStream_t st, hipEvent_t e) : ctx(c), s(st), ev(e) {}
+    drain_on_failure(const drain_on_failure &) = delete;
+    void done() { armed = false; }
+    ~drain_on_failure()
+    {
+        errs quiet;
+        if (armed) (void)sync_stream(ctx, quiet, s, ev);
+    }
+};
 BSW_LOCAL int check_params(errs &e, const bsw_params *p, bsw_dparams *dp);
 BSW_LOCAL int mat_max(const int8_t *mat);
 BSW_LOCAL int gap_limit(const bsw_params *p, int mx, int qlen, int end_bonus);

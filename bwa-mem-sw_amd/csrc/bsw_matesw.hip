@@ -90,6 +90,7 @@ static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
         (he = ctx->a_res.reserve(n + 1)) != hipSuccess || (he = ctx->a_bl.reserve((size_t)bacc + 64)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
     std::vector<bsw_kswr> aln(n);
+    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
     if (!order.empty()) {
         if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
@@ -134,6 +135,7 @@ static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
         const int64_t rl = m.re - m.rb, ql = m.qe - m.qb;
         m.seedcov = (int32_t)((rl < ql ? rl : ql) >> 1);
     }
+    drain.done();
     return BSW_OK;
 }
 

@@ -19,7 +19,7 @@ SAN = {
 }
 HOST_HIP = ["bsw_ctx", "bsw_batch", "bsw_scalar", "bsw_wire", "bsw_f4", "bsw_cigar", "bsw_matesw"]
 HOST_C = ["bsw_synth", "bsw_glue", "bsw_refbatch"]
-PROGRAMS = ["host_parity", "host_faults", "host_watchdog", "host_tickets", "asan_plan"]
+PROGRAMS = ["host_parity", "host_f4", "host_faults", "host_watchdog", "host_tickets", "asan_plan"]
 
 _built = {}
 
@@ -54,11 +54,12 @@ def build(san):
         src = os.path.join(ROOT, "tests", "asan_plan.cpp") if n == "asan_plan" else os.path.join(DBL, n + ".cpp")
         jobs.append(hip + ["-I", DBL, "-c", src, "-o", obj(n)])
     # the oracle is the yardstick, not the code under test: optimised, not instrumented (tests/asan_host.c runs it under ASan)
-    jobs.append([CLANG, "-O2", "-std=gnu11"] + inc + ["-c", os.path.join(ROOT, "oracle", "ksw_extend_ref.c"), "-o", obj("oracle_extend")])
+    for src, name in (("ksw_extend_ref.c", "oracle_extend"), ("ksw_global_ref.c", "oracle_global"), ("ksw_align_ref.c", "oracle_align")):
+        jobs.append([CLANG, "-O2", "-std=gnu11"] + inc + ["-c", os.path.join(ROOT, "oracle", src), "-o", obj(name)])
     jobs.append([CLANG, "-O2", "-std=gnu11"] + inc + ["-c", os.path.join(ROOT, "tests", "ksw_extend_rtl_ref.c"), "-o", obj("oracle_rtl")])
     with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
         list(ex.map(_cc, jobs))
-    shared = [objs[n] for n in HOST_HIP + HOST_C + ["hip_double", "launchers", "oracle_extend", "oracle_rtl"]]
+    shared = [objs[n] for n in HOST_HIP + HOST_C + ["hip_double", "launchers", "oracle_extend", "oracle_global", "oracle_align", "oracle_rtl"]]
     res = {"dir": out, "objs": objs}
     for n in PROGRAMS:
         exe = os.path.join(out, n)

@@ -1,0 +1,922 @@
+/* host_f4.cpp — the hosts of bsw_global_batch, bsw_align_batch, bsw_cigar_ref_batch and bsw_matesw_ref_batch (bsw_f4.hip,
+ * bsw_cigar.hip, bsw_matesw.hip) and the scalar queue's ksw_align2 / ksw_global2 groups on the host-memory HIP stand-in, under
+ * ASan / UBSan or TSan (TEST INFRASTRUCTURE; tests/test_host_double_cpu.py).
+ *
+ *   host_f4 f4 FILE              the four batch calls over n x memory kind on a workload that reaches every class and branch
+ *   host_f4 f4split WHICH FILE   WHICH = count | z | b: batches that cross one bound of the hosts' sub-batch loops
+ *   host_f4 f4scalar             ksw_global2 / ksw_global / ksw_align2 / ksw_align / ksw_extend2 from 12 threads and an offender
+ *   host_f4 faults CALL          CALL = global | align | cigar | matesw: every single HIP failure inside that batch call
+ *
+ * Expected values do not travel the path under test.  The stand-ins compute from the words the host staged; for the global and
+ * the local alignment this program calls the oracle on the caller's byte-per-base sequences.  For CIGAR / NM / MD / retries and
+ * for mate rescue it writes inputs and results to FILE and the Python test compares them with tests/_gencigar_ref.reg2aln and
+ * tests/_matesw_ref.matesw.
+ */
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <climits>
+#include "host_common.h"
+
+extern "C" void ksw_align2_ref(int qlen, const uint8_t *query, int tlen, const uint8_t *target, int m, const int8_t *mat, int o_del, int e_del,
+                               int o_ins, int e_ins, int xtra, int32_t *out, uint64_t *cells);
+
+struct rng_t {
+    uint64_t s;
+    explicit rng_t(uint64_t seed) : s(seed * 0x9e3779b97f4a7c15ull + 1) {}
+    uint64_t next() { uint64_t z = (s += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
+    int below(int n) { return (int)(next() % (uint64_t)n); }
+    int in(int lo, int hi) { return lo + below(hi - lo + 1); }           /* inclusive */
+    double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
+};
+
+/* a genome and its 2-bit pac (bwa's layout: base x in bits ((~x & 3) << 1) of byte x >> 2) */
+struct genome_t {
+    int64_t l_pac = 0;
+    std::vector<uint8_t> bases, pac;
+    void make(int64_t n, uint64_t seed)
+    {
+        rng_t r(seed);
+        l_pac = n;
+        bases.resize((size_t)n);
+        for (auto &b : bases) b = (uint8_t)r.below(4);
+        pac.assign((size_t)((n + 3) >> 2), 0);
+        for (int64_t x = 0; x < n; ++x) pac[(size_t)(x >> 2)] |= (uint8_t)(bases[(size_t)x] << ((~x & 3) << 1));
+    }
+    /* bns_get_seq for an interval that lies on one strand */
+    std::vector<uint8_t> seq(int64_t rb, int64_t re) const
+    {
+        std::vector<uint8_t> out;
+        for (int64_t x = rb; x < re; ++x) out.push_back(x >= l_pac ? (uint8_t)(3 - bases[(size_t)(2 * l_pac - 1 - x)]) : bases[(size_t)x]);
+        return out;
+    }
+};
+
+static std::vector<uint8_t> mutate(rng_t &r, const std::vector<uint8_t> &src, double sub, double indel, double nrate = 0.0)
+{
+    std::vector<uint8_t> out;
+    for (size_t i = 0; i < src.size(); ++i) {
+        const double u = r.unit();
+        if (u < indel / 2) continue;                                       /* deletion from the read */
+        if (u < indel) out.push_back((uint8_t)r.below(4));                 /* insertion */
+        uint8_t b = src[i];
+        if (r.unit() < sub) b = (uint8_t)((b + 1 + r.below(3)) & 3);
+        if (nrate > 0 && r.unit() < nrate) b = 4;
+        out.push_back(b);
+    }
+    if (out.empty()) out.push_back(src.empty() ? 0 : src[0]);
+    return out;
+}
+
+static std::vector<uint8_t> revcomp(const std::vector<uint8_t> &s)
+{
+    std::vector<uint8_t> o(s.rbegin(), s.rend());
+    for (auto &c : o) c = c < 4 ? (uint8_t)(3 - c) : (uint8_t)4;
+    return o;
+}
+
+/* the caller's sequence bytes: one arena, registered (bsw_host_alloc: the hosts' `direct` branch) or pageable (the gather branch) */
+struct arena_t {
+    uint8_t *p = nullptr;
+    size_t cap = 0, at = 0;
+    bool registered = false;
+    arena_t(size_t bytes, bool reg) : cap(bytes + 64), registered(reg)
+    {
+        p = (uint8_t *)(reg ? bsw_host_alloc(cap) : malloc(cap));
+        CHECK(p, "arena of %zu bytes", cap);
+        memset(p, 0, cap);
+    }
+    ~arena_t() { if (registered) bsw_host_free(p); else free(p); }
+    arena_t(const arena_t &) = delete;
+    const uint8_t *put(const std::vector<uint8_t> &s)
+    {
+        CHECK(at + s.size() <= cap, "arena full");
+        uint8_t *q = p + at;
+        if (!s.empty()) memcpy(q, s.data(), s.size());
+        at += s.size();
+        return q;
+    }
+};
+
+static bsw_params default_params()
+{
+    bsw_params p;
+    bsw_default_params(&p);
+    return p;
+}
+
+static std::string digits(const uint8_t *s, int n)
+{
+    std::string o;
+    for (int i = 0; i < n; ++i) o += (char)('0' + s[i]);
+    return o.empty() ? "-" : o;
+}
+
+static void write_genome(FILE *f, const genome_t &g, const bsw_params &p)
+{
+    fprintf(f, "genome %lld ", (long long)g.l_pac);
+    for (uint8_t b : g.pac) fprintf(f, "%02x", b);
+    fprintf(f, "\nparams");
+    for (int i = 0; i < 25; ++i) fprintf(f, " %d", p.mat[i]);
+    fprintf(f, " %d %d %d %d\n", p.o_del, p.e_del, p.o_ins, p.e_ins);
+}
+
+/* ---- global ---- */
+struct gwork {
+    std::vector<bsw_gtask> t;
+    std::vector<std::vector<uint8_t>> q, tg;
+};
+
+static const int G_LONG[] = {63, 64, 127, 128, 255, 256, 400, 511, 512, 700, 1023, 1024, 1100, 1500};
+
+static void make_global(gwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        int tl = (i % 23 == 5) ? G_LONG[(i / 23) % (sizeof(G_LONG) / sizeof(int))] : r.in(1, 62);
+        const int64_t at = r.below((int)(g.l_pac - tl - 1));
+        std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl);
+        std::vector<uint8_t> q = mutate(r, tg, 0.05, tl > 300 ? 0.01 : 0.04, 0.01);
+        if (tl > 62 && (int)q.size() != tl && tl != 400 && tl != 700 && tl != 1100 && tl != 1500) q.resize((size_t)tl, 1);   /* (class edges: the query length decides) */
+        w.q.push_back(q);
+        w.tg.push_back(tg);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        bsw_gtask t;
+        memset(&t, 0, sizeof(t));
+        t.qlen = (int)w.q[i].size(); t.tlen = (int)w.tg[i].size();
+        t.query = ar.put(w.q[i]); t.target = ar.put(w.tg[i]);
+        const int d = abs(t.qlen - t.tlen);
+        t.w = d + 3 + (int)(i % 17);
+        if (t.tlen == 1100) t.w = 200;                                    /* ring classes 0 (narrow bands), 1 (n_col 401) and 3 (1201) */
+        if (t.tlen == 1500) t.w = 600;
+        w.t.push_back(t);
+    }
+}
+
+static void check_global(bsw_ctx *ctx, const bsw_params &p, const gwork &w, int max_cigar, bool want_cigar, const char *what)
+{
+    const size_t n = w.t.size();
+    std::vector<bsw_gresult> res(n + 1);
+    std::vector<uint32_t> cig(n * (size_t)max_cigar + 1, 0xdeadbeefu);
+    memset(res.data(), 0x5a, res.size() * sizeof(bsw_gresult));
+    const int rc = bsw_global_batch(ctx, &p, w.t.data(), n, max_cigar, res.data(), want_cigar ? cig.data() : nullptr);
+    CHECK(rc == BSW_OK, "%s: bsw_global_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
+    for (size_t i = 0; i < n; ++i) {
+        int nc = 0;
+        uint32_t *cg = nullptr;
+        const int score = ksw_global2_ref(w.t[i].qlen, w.q[i].data(), w.t[i].tlen, w.tg[i].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, w.t[i].w, &nc, &cg, nullptr);
+        CHECK(res[i].score == score, "%s: task %zu of %zu (%d x %d, w %d): score %d, the oracle's %d", what, i, n, w.t[i].qlen, w.t[i].tlen, w.t[i].w, res[i].score, score);
+        if (want_cigar) {
+            CHECK(res[i].n_cigar == (nc <= max_cigar ? nc : -nc), "%s: task %zu of %zu: n_cigar %d, the oracle's %d (room %d)", what, i, n, res[i].n_cigar, nc, max_cigar);
+            if (nc <= max_cigar)
+                for (int k = 0; k < nc; ++k) CHECK(cig[i * (size_t)max_cigar + (size_t)k] == cg[k], "%s: task %zu of %zu: CIGAR word %d differs", what, i, n, k);
+        } else
+            CHECK(res[i].n_cigar == 0, "%s: task %zu: n_cigar %d without a CIGAR buffer", what, i, res[i].n_cigar);
+        free(cg);
+    }
+}
+
+/* ---- local alignment ---- */
+struct awork {
+    std::vector<bsw_atask> t;
+    std::vector<std::vector<uint8_t>> q, tg;
+};
+
+static const int A_LONG[] = {128, 129, 160, 161, 256, 257, 512, 513, 1024};
+
+static int xtra_for(size_t i, int qlen)
+{
+    int x = (i & 1) ? KSW_XBYTE : 0;
+    if (i % 5 != 4) x |= KSW_XSUBO | (qlen > 30 ? 19 : 3);
+    if (i % 3 != 2) x |= KSW_XSTART;
+    if (i % 11 == 10) x = (x & KSW_XBYTE) | KSW_XSTOP | 12;
+    return x;
+}
+
+static void make_align(awork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const int ql = (i % 19 == 3) ? A_LONG[(i / 19) % (sizeof(A_LONG) / sizeof(int))] : r.in(1, 128);
+        const int tl = ql + r.in(0, 200);
+        const int64_t at = r.below((int)(g.l_pac - tl - 1));
+        std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl);
+        const int off = r.below(tl - ql + 1);
+        std::vector<uint8_t> piece(tg.begin() + off, tg.begin() + off + ql);
+        std::vector<uint8_t> q = mutate(r, piece, 0.05, 0.02, 0.01);
+        q.resize((size_t)ql, 2);
+        if (i % 7 == 0 && tl >= 2 * ql + 4) std::copy(piece.begin(), piece.end(), tg.begin() + (tl - ql));       /* a planted repeat: score2 */
+        w.q.push_back(q);
+        w.tg.push_back(tg);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        bsw_atask t;
+        memset(&t, 0, sizeof(t));
+        t.qlen = (int)w.q[i].size(); t.tlen = (int)w.tg[i].size();
+        t.query = ar.put(w.q[i]); t.target = ar.put(w.tg[i]);
+        t.xtra = xtra_for(i, t.qlen);
+        w.t.push_back(t);
+    }
+}
+
+static void check_align(bsw_ctx *ctx, const bsw_params &p, const awork &w, const char *what)
+{
+    const size_t n = w.t.size();
+    std::vector<bsw_kswr> res(n + 1);
+    memset(res.data(), 0x5a, res.size() * sizeof(bsw_kswr));
+    const int rc = bsw_align_batch(ctx, &p, w.t.data(), n, res.data());
+    CHECK(rc == BSW_OK, "%s: bsw_align_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
+    for (size_t i = 0; i < n; ++i) {
+        int32_t want[7];
+        ksw_align2_ref(w.t[i].qlen, w.q[i].data(), w.t[i].tlen, w.tg[i].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, w.t[i].xtra, want, nullptr);
+        CHECK(memcmp(&res[i], want, sizeof(want)) == 0, "%s: task %zu of %zu (%d x %d, xtra 0x%x): score %d te %d qe %d score2 %d te2 %d tb %d qb %d, the oracle's %d %d %d %d %d %d %d",
+              what, i, n, w.t[i].qlen, w.t[i].tlen, (unsigned)w.t[i].xtra, res[i].score, res[i].te, res[i].qe, res[i].score2, res[i].te2, res[i].tb, res[i].qb,
+              want[0], want[1], want[2], want[3], want[4], want[5], want[6]);
+    }
+}
+
+/* ---- bwa_gen_cigar2 on the resident reference ---- */
+struct cwork {
+    std::vector<bsw_ctask> t;
+    std::vector<std::vector<uint8_t>> q;
+};
+
+/* a read of [rb, re) (in the strand's own order) whose path leaves the diagonal by `off` bases between two indels */
+static std::vector<uint8_t> offset_read(rng_t &r, const std::vector<uint8_t> &rs, int off)
+{
+    std::vector<uint8_t> o(rs.begin(), rs.begin() + 40);
+    o.insert(o.end(), rs.begin() + 40 + off, rs.begin() + 100);            /* a deletion of `off` bases ... */
+    for (int k = 0; k < off; ++k) o.push_back((uint8_t)r.below(4));        /* ... and an insertion of as many */
+    o.insert(o.end(), rs.begin() + 100, rs.end());
+    return o;
+}
+
+static void make_cigar(cwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
+{
+    const int64_t L = g.l_pac;
+    for (size_t i = 0; i < n; ++i) {
+        bsw_ctask t;
+        memset(&t, 0, sizeof(t));
+        t.min_score = INT_MIN; t.max_tries = 1; t.w = 100;
+        const int kind = (int)(i % 13);
+        const bool rev = (i / 13) % 2 == 1;
+        int rl = r.in(60, 150);
+        if (kind == 11) rl = (i % 3 == 0) ? 1100 : r.in(200, 600);
+        if (kind >= 7 && kind <= 9) rl = 150;
+        int64_t rb = (rev ? L : 0) + r.below((int)(L - rl - 1));
+        int64_t re = rb + rl;
+        std::vector<uint8_t> q;
+        if (kind == 2) { rb = L - 30; re = L + 40; q = g.seq(100, 170); }                 /* bridges l_pac: status 1 */
+        else if (kind == 3) { re = rb - (i % 2); q = g.seq(100, 170); }                   /* empty interval: status 1 */
+        else if (kind == 4) {
+            if (i % 2) { rb = 2 * L - 20; re = 2 * L + 30; q = g.seq(100, 150); }         /* leaves [0, 2 l_pac): status 1 */
+            else q.clear();                                                              /* an empty read: status 1 */
+        } else {
+            const std::vector<uint8_t> rs = g.seq(rb, re);                               /* (reverse strand: bwa reverses both) */
+            std::vector<uint8_t> fw;
+            if (kind == 5 || kind == 6) {                                                /* the no-gap shortcut */
+                fw = mutate(r, rs, kind == 6 ? 0.2 : 0.03, 0.0, 0.01);
+                fw.resize(rs.size(), 0);
+                t.w = 0;
+                if (kind == 6) { t.w_cap = 50; t.max_tries = 2 + (int)(i % 2); t.min_score = (i % 4 < 2) ? rl : -1000; }
+            } else if (kind >= 7 && kind <= 9) {                                         /* retries: 1, 2 and 3 tries */
+                const std::vector<uint8_t> rr = rev ? std::vector<uint8_t>(rs.rbegin(), rs.rend()) : rs;
+                std::vector<uint8_t> o = offset_read(r, rr, kind == 7 ? 2 : kind == 8 ? 4 : 8);
+                fw = rev ? std::vector<uint8_t>(o.rbegin(), o.rend()) : o;
+                t.w = 2; t.w_cap = 64; t.max_tries = 3; t.min_score = 100;
+                if (i % 5 == 0) t.max_tries = 2;
+            } else
+                fw = mutate(r, rs, 0.03, kind == 10 ? 0.06 : 0.01, kind == 1 ? 0.02 : 0.0);
+            /* a reverse-strand read arrives in READ order: the reverse of what aligns to bns_get_seq(rb, re) reversed */
+            q = fw;
+            if ((kind == 0 || kind == 12) && i % 4 == 0) t.w = 5;
+        }
+        w.q.push_back(q);
+        t.l_query = (int)q.size(); t.rb = rb; t.re = re;
+        w.t.push_back(t);
+    }
+    for (size_t i = 0; i < n; ++i) w.t[i].query = w.q[i].empty() ? nullptr : ar.put(w.q[i]);
+}
+
+static void run_cigar(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const cwork &w, int max_cigar, int max_md, bool want_cigar, bool want_md,
+                      FILE *f, const char *what, size_t emit_first = SIZE_MAX, std::vector<bsw_cresult> *res_out = nullptr,
+                      std::vector<uint32_t> *cig_out = nullptr, std::vector<char> *md_out = nullptr)
+{
+    const size_t n = w.t.size();
+    std::vector<bsw_cresult> res(n + 1);
+    std::vector<uint32_t> cig(n * (size_t)max_cigar + 1, 0xdeadbeefu);
+    std::vector<char> md(n * (size_t)max_md + 1, '#');
+    memset(res.data(), 0x5a, res.size() * sizeof(bsw_cresult));
+    const int rc = bsw_cigar_ref_batch(ctx, &p, ref, w.t.data(), n, max_cigar, want_cigar ? cig.data() : nullptr, max_md, want_md ? md.data() : nullptr, res.data());
+    CHECK(rc == BSW_OK, "%s: bsw_cigar_ref_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
+    CHECK(cig[n * (size_t)max_cigar] == 0xdeadbeefu && md[n * (size_t)max_md] == '#', "%s: a write behind the caller's arrays", what);
+    if (f) {
+        const size_t m = std::min(n, emit_first);
+        fprintf(f, "cigarcase %zu %d %d %d %d %s\n", m, max_cigar, max_md, want_cigar ? 1 : 0, want_md ? 1 : 0, what);
+        for (size_t i = 0; i < m; ++i) {
+            const bsw_ctask &t = w.t[i];
+            const bsw_cresult &r = res[i];
+            fprintf(f, "c %s %lld %lld %d %d %d %d | %d %d %d %d %d %d %d %d |", digits(t.query, t.l_query).c_str(), (long long)t.rb, (long long)t.re, t.w, t.w_cap,
+                    t.min_score, t.max_tries, r.score, r.n_cigar, r.nm, r.md_len, r.w, r.tries, r.status, r._pad);
+            if (want_cigar)
+                for (int k = 0; k < r.n_cigar && k < max_cigar; ++k) fprintf(f, " %u", cig[i * (size_t)max_cigar + (size_t)k]);
+            fprintf(f, " | ");
+            if (want_md) {
+                const char *s = md.data() + i * (size_t)max_md;
+                CHECK(memchr(s, 0, (size_t)max_md) != nullptr, "%s: task %zu: the MD slot holds no NUL", what, i);
+                fprintf(f, "%s", *s ? s : "-");
+            } else
+                fprintf(f, "?");
+            fprintf(f, "\n");
+        }
+    }
+    if (res_out) *res_out = res;
+    if (cig_out) *cig_out = cig;
+    if (md_out) *md_out = md;
+}
+
+/* ---- mate rescue ---- */
+struct mwork {
+    std::vector<bsw_mtask> t;
+    std::vector<std::vector<uint8_t>> m;
+};
+
+static void make_matesw(mwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
+{
+    const int64_t L = g.l_pac;
+    for (size_t i = 0; i < n; ++i) {
+        bsw_mtask t;
+        memset(&t, 0, sizeof(t));
+        const int kind = (int)(i % 11);
+        const bool strand = (i / 11) % 2 == 1;
+        const int lm = (i % 19 == 3) ? A_LONG[(i / 19) % (sizeof(A_LONG) / sizeof(int))] : r.in(8, 150);
+        const int tl = lm + r.in(20, 400);
+        int64_t rb = (strand ? L : 0) + r.below((int)(L - tl - 1)), re = rb + tl;
+        t.is_rev = (int)(i % 2);
+        std::vector<uint8_t> win = g.seq(rb, re);
+        const int off = r.below(tl - lm + 1);
+        std::vector<uint8_t> piece(win.begin() + off, win.begin() + off + lm);
+        std::vector<uint8_t> aligned = mutate(r, piece, kind == 9 ? 0.4 : 0.04, 0.02, 0.01);
+        aligned.resize((size_t)lm, 1);
+        std::vector<uint8_t> ms = t.is_rev ? revcomp(aligned) : aligned;   /* the mate in read order */
+        if (kind == 2) { rb = L - 50; re = L + 60; }                       /* bridges l_pac */
+        if (kind == 3) re = rb;                                           /* empty window */
+        if (kind == 4 && i % 2) { rb = 2 * L - 40; re = 2 * L + 10; }      /* leaves [0, 2 l_pac) */
+        if (kind == 4 && !(i % 2)) ms.clear();                             /* empty mate */
+        t.xtra = KSW_XSUBO | KSW_XSTART | (i % 3 ? KSW_XBYTE : 0) | (i % 4 == 0 ? 5 : 19);
+        if (i % 13 == 7) t.xtra &= ~KSW_XSUBO;
+        t.min_score = i % 6 == 0 ? 60 : 19;
+        t.l_ms = (int)ms.size(); t.rb = rb; t.re = re;
+        w.m.push_back(ms);
+        w.t.push_back(t);
+    }
+    for (size_t i = 0; i < n; ++i) w.t[i].mate = w.m[i].empty() ? nullptr : ar.put(w.m[i]);
+}
+
+static void run_matesw(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const mwork &w, FILE *f, const char *what, size_t emit_first = SIZE_MAX,
+                       std::vector<bsw_mresult> *res_out = nullptr)
+{
+    const size_t n = w.t.size();
+    std::vector<bsw_mresult> res(n + 1);
+    memset(res.data(), 0x5a, res.size() * sizeof(bsw_mresult));
+    const int rc = bsw_matesw_ref_batch(ctx, &p, ref, w.t.data(), n, res.data());
+    CHECK(rc == BSW_OK, "%s: bsw_matesw_ref_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
+    if (f) {
+        const size_t m = std::min(n, emit_first);
+        fprintf(f, "matecase %zu %s\n", m, what);
+        for (size_t i = 0; i < m; ++i) {
+            const bsw_mtask &t = w.t[i];
+            const bsw_mresult &r = res[i];
+            fprintf(f, "m %s %d %lld %lld %d %d | %d %d %d %d %d %d %d | %d %lld %lld %d %d %d %d %d %d\n", digits(t.mate, t.l_ms).c_str(), t.is_rev, (long long)t.rb,
+                    (long long)t.re, t.xtra, t.min_score, r.aln.score, r.aln.te, r.aln.qe, r.aln.score2, r.aln.te2, r.aln.tb, r.aln.qb, r.status, (long long)r.rb,
+                    (long long)r.re, r.qb, r.qe, r.score, r.csub, r.seedcov, r._pad);
+        }
+    }
+    if (res_out) *res_out = res;
+}
+
+/* ---- f4: parity over n x memory kind ---- */
+static const size_t F4_NS[] = {0, 1, 63, 64, 65, 2600};
+
+static int f4_mode(const char *path)
+{
+    FILE *f = fopen(path, "w");
+    CHECK(f, "cannot write %s", path);
+    const bsw_params p = default_params();
+    genome_t g;
+    g.make(150001, 77);
+    write_genome(f, g, p);
+    size_t cases = 0;
+    for (int reg = 0; reg < 2; ++reg)
+        for (size_t n : F4_NS) {
+            char what[96];
+            snprintf(what, sizeof(what), "%s_n%zu", reg ? "registered" : "pageable", n);
+            fresh(1);
+            {
+                rng_t r(1000 + n + (uint64_t)reg);
+                bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256);
+                bsw_ref *ref = nullptr;
+                CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
+                {
+                    arena_t ar(n * 700 + 8192, reg != 0);
+                    gwork w;
+                    make_global(w, ar, g, r, n);
+                    check_global(ctx, p, w, 48, true, what);
+                    if (n == 65 || n == 2600) { check_global(ctx, p, w, 2, true, what); check_global(ctx, p, w, 48, false, what); }
+                }
+                {
+                    arena_t ar(n * 900 + 8192, reg != 0);
+                    awork w;
+                    make_align(w, ar, g, r, n);
+                    check_align(ctx, p, w, what);
+                }
+                {
+                    arena_t ar(n * 300 + 8192, reg != 0);
+                    cwork w;
+                    make_cigar(w, ar, g, r, n);
+                    run_cigar(ctx, p, ref, w, 64, 512, true, true, f, what);
+                    if (n == 65) {
+                        run_cigar(ctx, p, ref, w, 3, 512, true, true, f, what);       /* CIGAR overflow */
+                        run_cigar(ctx, p, ref, w, 64, 6, true, true, f, what);        /* MD overflow */
+                        run_cigar(ctx, p, ref, w, 64, 512, false, true, f, what);     /* cigars == NULL */
+                        run_cigar(ctx, p, ref, w, 64, 512, true, false, f, what);     /* md == NULL */
+                    }
+                }
+                {
+                    arena_t ar(n * 400 + 8192, reg != 0);
+                    mwork w;
+                    make_matesw(w, ar, g, r, n);
+                    run_matesw(ctx, p, ref, w, f, what);
+                }
+                bsw_ref_free(ctx, ref);
+                bsw_destroy(ctx);
+            }
+            CHECK(hipdbl::live_objects() == 0, "%s: %zu HIP objects left alive after bsw_destroy", what, hipdbl::live_objects());
+            ++cases;
+        }
+    fclose(f);
+    printf("f4: %zu cases, %llu launch rounds checked, %llu tasks computed by the stand-ins\n", cases, (unsigned long long)standin::f4_rounds(), (unsigned long long)standin::f4_tasks());
+    return 0;
+}
+
+/* ---- f4split: one bound of the sub-batch loops per invocation ---- */
+template <class T>
+static void cycle(std::vector<T> &v, size_t n)
+{
+    const size_t d = v.size();
+    v.reserve(n);
+    for (size_t k = d; k < n; ++k) v.push_back(v[k % d]);
+}
+
+static uint64_t packs() { return hipdbl::calls("launch_pack"); }
+
+static void same_cycle_g(const std::vector<bsw_gresult> &res, const std::vector<uint32_t> &cig, int max_cigar, size_t n, size_t D, const char *what)
+{
+    for (size_t k = D; k < n; ++k) {
+        CHECK(memcmp(&res[k], &res[k % D], sizeof(bsw_gresult)) == 0, "%s: result %zu differs from result %zu of the same task (score %d / %d, n_cigar %d / %d)", what, k, k % D,
+              res[k].score, res[k % D].score, res[k].n_cigar, res[k % D].n_cigar);
+        const int nc = std::min(std::max(res[k].n_cigar, 0), max_cigar);
+        CHECK(nc == 0 || memcmp(&cig[k * (size_t)max_cigar], &cig[(k % D) * (size_t)max_cigar], (size_t)nc * 4) == 0, "%s: the CIGAR of result %zu differs from that of result %zu", what, k, k % D);
+    }
+}
+
+static void global_split(bsw_ctx *ctx, const bsw_params &p, gwork &w, size_t n, int max_cigar, const char *what, uint64_t *sub)
+{
+    const size_t D = w.t.size();
+    cycle(w.t, n);
+    std::vector<bsw_gresult> res(n);
+    std::vector<uint32_t> cig(n * (size_t)max_cigar);
+    const uint64_t p0 = packs();
+    const int rc = bsw_global_batch(ctx, &p, w.t.data(), n, max_cigar, res.data(), cig.data());
+    CHECK(rc == BSW_OK, "%s: bsw_global_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
+    *sub = packs() - p0;
+    for (size_t i = 0; i < D; ++i) {
+        int nc = 0;
+        uint32_t *cg = nullptr;
+        const int score = ksw_global2_ref(w.t[i].qlen, w.q[i].data(), w.t[i].tlen, w.tg[i].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, w.t[i].w, &nc, &cg, nullptr);
+        CHECK(nc <= max_cigar, "%s: distinct task %zu needs %d CIGAR words", what, i, nc);
+        CHECK(res[i].score == score && res[i].n_cigar == nc, "%s: distinct task %zu: score %d n_cigar %d, the oracle's %d %d", what, i, res[i].score, res[i].n_cigar, score, nc);
+        CHECK(memcmp(&cig[i * (size_t)max_cigar], cg, (size_t)nc * 4) == 0, "%s: distinct task %zu: the CIGAR differs from the oracle's", what, i);
+        free(cg);
+    }
+    same_cycle_g(res, cig, max_cigar, n, D, what);
+}
+
+static void align_split(bsw_ctx *ctx, const bsw_params &p, awork &w, size_t n, const char *what, uint64_t *sub)
+{
+    const size_t D = w.t.size();
+    cycle(w.t, n);
+    std::vector<bsw_kswr> res(n);
+    const uint64_t p0 = packs();
+    const int rc = bsw_align_batch(ctx, &p, w.t.data(), n, res.data());
+    CHECK(rc == BSW_OK, "%s: bsw_align_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
+    *sub = packs() - p0;
+    for (size_t i = 0; i < D; ++i) {
+        int32_t want[7];
+        ksw_align2_ref(w.t[i].qlen, w.q[i].data(), w.t[i].tlen, w.tg[i].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, w.t[i].xtra, want, nullptr);
+        CHECK(memcmp(&res[i], want, sizeof(want)) == 0, "%s: distinct task %zu: score %d te %d score2 %d tb %d, the oracle's %d %d %d %d", what, i, res[i].score, res[i].te, res[i].score2,
+              res[i].tb, want[0], want[1], want[3], want[5]);
+    }
+    for (size_t k = D; k < n; ++k)
+        CHECK(memcmp(&res[k], &res[k % D], sizeof(bsw_kswr)) == 0, "%s: result %zu differs from result %zu of the same task (score %d / %d, te %d / %d, score2 %d / %d)", what, k, k % D,
+              res[k].score, res[k % D].score, res[k].te, res[k % D].te, res[k].score2, res[k % D].score2);
+}
+
+static void cigar_split(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, cwork &w, size_t n, int max_cigar, int max_md, FILE *f, const char *what, uint64_t *sub)
+{
+    const size_t D = w.t.size();
+    cycle(w.t, n);
+    std::vector<bsw_cresult> res;
+    std::vector<uint32_t> cig;
+    std::vector<char> md;
+    const uint64_t p0 = packs();
+    run_cigar(ctx, p, ref, w, max_cigar, max_md, true, true, f, what, D, &res, &cig, &md);
+    *sub = packs() - p0;
+    for (size_t k = D; k < n; ++k) {
+        CHECK(memcmp(&res[k], &res[k % D], sizeof(bsw_cresult)) == 0, "%s: result %zu differs from result %zu of the same task (score %d / %d, nm %d / %d, tries %d / %d)", what, k, k % D,
+              res[k].score, res[k % D].score, res[k].nm, res[k % D].nm, res[k].tries, res[k % D].tries);
+        const int nc = std::min(std::max(res[k].n_cigar, 0), max_cigar);
+        CHECK(nc == 0 || memcmp(&cig[k * (size_t)max_cigar], &cig[(k % D) * (size_t)max_cigar], (size_t)nc * 4) == 0, "%s: the CIGAR of result %zu differs from that of result %zu", what, k, k % D);
+        CHECK(strcmp(&md[k * (size_t)max_md], &md[(k % D) * (size_t)max_md]) == 0, "%s: the MD of result %zu differs from that of result %zu", what, k, k % D);
+    }
+}
+
+static void matesw_split(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, mwork &w, size_t n, FILE *f, const char *what, uint64_t *sub)
+{
+    const size_t D = w.t.size();
+    cycle(w.t, n);
+    std::vector<bsw_mresult> res;
+    const uint64_t p0 = packs();
+    run_matesw(ctx, p, ref, w, f, what, D, &res);
+    *sub = packs() - p0;
+    for (size_t k = D; k < n; ++k)
+        CHECK(memcmp(&res[k], &res[k % D], sizeof(bsw_mresult)) == 0, "%s: result %zu differs from result %zu of the same task (score %d / %d, status %d / %d, rb %lld / %lld)", what, k, k % D,
+              res[k].aln.score, res[k % D].aln.score, res[k].status, res[k % D].status, (long long)res[k].rb, (long long)res[k % D].rb);
+}
+
+/* D distinct tiny tasks, D odd, neighbours of different lengths */
+static void tiny_global(gwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D)
+{
+    for (size_t i = 0; i < D; ++i) {
+        const int ql = 1 + (int)((i * 3) % 8), tl = 1 + (int)((i * 5 + 2) % 10);
+        const int64_t at = r.below((int)(g.l_pac - 40));
+        std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl), q(g.bases.begin() + at + (i % 2), g.bases.begin() + at + (i % 2) + ql);
+        if (i % 3 == 0) q[q.size() / 2] = (uint8_t)((q[q.size() / 2] + 1) & 3);
+        w.q.push_back(q); w.tg.push_back(tg);
+    }
+    for (size_t i = 0; i < D; ++i) {
+        bsw_gtask t;
+        memset(&t, 0, sizeof(t));
+        t.qlen = (int)w.q[i].size(); t.tlen = (int)w.tg[i].size(); t.query = ar.put(w.q[i]); t.target = ar.put(w.tg[i]);
+        t.w = abs(t.qlen - t.tlen) + 3;
+        w.t.push_back(t);
+    }
+}
+
+static void tiny_align(awork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D, int tlen_fixed, int no_subo_every)
+{
+    for (size_t i = 0; i < D; ++i) {
+        const int ql = 1 + (int)((i * 3) % 8), tl = tlen_fixed ? tlen_fixed - (int)(i % 2) * 7 : 9 + (int)((i * 7) % 30);
+        const int64_t at = r.below((int)(g.l_pac - tl - 1));
+        std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl);
+        const int off = r.below(tl - ql + 1);
+        std::vector<uint8_t> q(tg.begin() + off, tg.begin() + off + ql);
+        for (int c = 0; c < 6; ++c) std::copy(q.begin(), q.end(), tg.begin() + r.below(tl - ql + 1));      /* planted repeats of the query */
+        w.q.push_back(q); w.tg.push_back(tg);
+    }
+    for (size_t i = 0; i < D; ++i) {
+        bsw_atask t;
+        memset(&t, 0, sizeof(t));
+        t.qlen = (int)w.q[i].size(); t.tlen = (int)w.tg[i].size(); t.query = ar.put(w.q[i]); t.target = ar.put(w.tg[i]);
+        t.xtra = KSW_XSUBO | KSW_XSTART | ((i & 1) ? KSW_XBYTE : 0) | (t.qlen > 4 ? 4 : 1);
+        if (no_subo_every && i % (size_t)no_subo_every == 1) t.xtra &= ~KSW_XSUBO;
+        w.t.push_back(t);
+    }
+}
+
+static void tiny_cigar(cwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D)
+{
+    const int64_t L = g.l_pac;
+    for (size_t i = 0; i < D; ++i) {
+        bsw_ctask t;
+        memset(&t, 0, sizeof(t));
+        t.min_score = INT_MIN; t.max_tries = 1; t.w = 10;
+        const bool rev = i % 2 == 1;
+        const int rl = 3 + (int)((i * 3) % 8);
+        int64_t rb = (rev ? L : 0) + r.below((int)(L - 20)), re = rb + rl;
+        std::vector<uint8_t> q = g.seq(rb, re);
+        if (i % 4 == 0 && q.size() > 4) q.erase(q.begin() + 2);                       /* a deletion from the read */
+        if (i % 4 == 1) q[q.size() / 2] = (uint8_t)((q[q.size() / 2] + 2) & 3);       /* a mismatch */
+        if (i % 4 == 2 && q.size() > 3) q.insert(q.begin() + 1, (uint8_t)r.below(4));
+        if (i % 4 == 3) { q[0] = (uint8_t)((q[0] + 1) & 3); t.w = 0; }                 /* the no-gap shortcut */
+        if (i == 5) { rb = L - 3; re = L + 4; }                                       /* status 1 */
+        if (q.size() > 8) q.resize(8);
+        w.q.push_back(q);
+        t.l_query = (int)q.size(); t.rb = rb; t.re = re;
+        w.t.push_back(t);
+    }
+    for (size_t i = 0; i < D; ++i) w.t[i].query = ar.put(w.q[i]);
+}
+
+static void tiny_matesw(mwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D, int tlen_fixed, int no_subo_every)
+{
+    const int64_t L = g.l_pac;
+    for (size_t i = 0; i < D; ++i) {
+        bsw_mtask t;
+        memset(&t, 0, sizeof(t));
+        const int lm = 2 + (int)((i * 3) % 7), tl = tlen_fixed ? tlen_fixed - (int)(i % 2) * 5 : 12 + (int)((i * 7) % 30);
+        const bool strand = i % 3 == 1;
+        int64_t rb = (strand ? L : 0) + r.below((int)(L - tl - 1)), re = rb + tl;
+        t.is_rev = (int)(i % 2);
+        std::vector<uint8_t> win = g.seq(rb, re);
+        const int off = r.below(tl - lm + 1);
+        std::vector<uint8_t> aligned(win.begin() + off, win.begin() + off + lm);
+        std::vector<uint8_t> ms = t.is_rev ? revcomp(aligned) : aligned;
+        if (!tlen_fixed && i == 4) re = rb;                                           /* status 1 */
+        t.xtra = KSW_XSUBO | KSW_XSTART | ((i & 1) ? KSW_XBYTE : 0) | (lm > 4 ? 4 : 2);
+        if (no_subo_every && i % (size_t)no_subo_every == 1) t.xtra &= ~KSW_XSUBO;
+        t.min_score = lm > 4 ? 4 : 2;
+        t.l_ms = lm; t.rb = rb; t.re = re;
+        w.m.push_back(ms);
+        w.t.push_back(t);
+    }
+    for (size_t i = 0; i < D; ++i) w.t[i].mate = ar.put(w.m[i]);
+}
+
+static int f4split_mode(const std::string &which, const char *path)
+{
+    FILE *f = fopen(path, "w");
+    CHECK(f, "cannot write %s", path);
+    const bsw_params p = default_params();
+    genome_t g;
+    g.make(which == "b" ? 700001 : 150001, 91);
+    write_genome(f, g, p);
+    uint64_t sub[4] = {0, 0, 0, 0};
+    fresh(1);
+    {
+        rng_t r(4711);
+        bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256, 2, 280000);      /* (the oracle computes a sub-batch for a minute: no watchdog) */
+        bsw_ref *ref = nullptr;
+        CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
+        arena_t ar(1 << 20, true);
+        if (which == "count") {                               /* 2^20 + 37 tasks per call */
+            const size_t n = (1u << 20) + 37;
+            { gwork w; tiny_global(w, ar, g, r, 11); global_split(ctx, p, w, n, 8, "count_global", &sub[0]); }
+            { awork w; tiny_align(w, ar, g, r, 11, 0, 0); align_split(ctx, p, w, n, "count_align", &sub[1]); }
+            { cwork w; tiny_cigar(w, ar, g, r, 13); cigar_split(ctx, p, ref, w, n, 6, 24, f, "count_cigar", &sub[2]); }
+            { mwork w; tiny_matesw(w, ar, g, r, 9, 0, 0); matesw_split(ctx, p, ref, w, n, f, "count_matesw", &sub[3]); }
+        } else if (which == "z") {                            /* more than 4 GiB of backtrack bytes in about 140 tasks */
+            const size_t n = 141, D = 5;
+            gwork gw;
+            cwork cw;
+            for (size_t i = 0; i < D; ++i) {
+                const int tl = 8000 - (int)i * 3;
+                const int64_t at = r.below((int)(g.l_pac - tl - 1));
+                std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl), q = mutate(r, tg, 0.01, 0.002);
+                if (q.size() > 8000) q.resize(8000);
+                gw.q.push_back(q); gw.tg.push_back(tg);
+                const bool rev = i % 2 == 1;
+                const int64_t rb = (rev ? g.l_pac : 0) + r.below((int)(g.l_pac - tl - 1));
+                std::vector<uint8_t> rd = mutate(r, g.seq(rb, rb + tl), 0.01, 0.002);
+                if (rd.size() > 8000) rd.resize(8000);
+                cw.q.push_back(rd);
+                bsw_ctask t;
+                memset(&t, 0, sizeof(t));
+                t.l_query = (int)rd.size(); t.w = 3000; t.rb = rb; t.re = rb + tl; t.min_score = INT_MIN; t.max_tries = 1;
+                cw.t.push_back(t);
+            }
+            arena_t big(D * 2 * 8200 * 2, false);
+            for (size_t i = 0; i < D; ++i) {
+                bsw_gtask t;
+                memset(&t, 0, sizeof(t));
+                t.qlen = (int)gw.q[i].size(); t.tlen = (int)gw.tg[i].size(); t.query = big.put(gw.q[i]); t.target = big.put(gw.tg[i]); t.w = 2000;
+                gw.t.push_back(t);
+                cw.t[i].query = big.put(cw.q[i]);
+            }
+            global_split(ctx, p, gw, n, 512, "z_global", &sub[0]);
+            cigar_split(ctx, p, ref, cw, n, 512, 2048, f, "z_cigar", &sub[2]);
+            sub[1] = sub[3] = 2;                              /* (not part of this invocation) */
+        } else if (which == "b") {                            /* more than 2^28 target bases under KSW_XSUBO */
+            /* 9 distinct windows, one of them without KSW_XSUBO (the loops count its bases towards the bound and give it no
+             * slice): 4 134 of the 4 651 tasks carry a slice, 270.9 M entries */
+            const size_t n = 4651;
+            arena_t big(10 * 65600, false);
+            { awork w; tiny_align(w, big, g, r, 9, 65535, 9); align_split(ctx, p, w, n, "b_align", &sub[1]); }
+            { mwork w; tiny_matesw(w, big, g, r, 9, 65535, 9); matesw_split(ctx, p, ref, w, n, f, "b_matesw", &sub[3]); }
+            sub[0] = sub[2] = 2;
+        } else
+            CHECK(false, "f4split count|z|b");
+        bsw_ref_free(ctx, ref);
+        bsw_destroy(ctx);
+    }
+    CHECK(hipdbl::live_objects() == 0, "f4split: %zu HIP objects left alive after bsw_destroy", hipdbl::live_objects());
+    fclose(f);
+    printf("f4split %s: sub-batches global %llu align %llu cigar %llu matesw %llu\n", which.c_str(), (unsigned long long)sub[0], (unsigned long long)sub[1],
+           (unsigned long long)sub[2], (unsigned long long)sub[3]);
+    return 0;
+}
+
+/* ---- f4scalar: the scalar queue's three kinds at once ---- */
+static int f4scalar_mode()
+{
+    fresh(1);
+    genome_t g;
+    g.make(60001, 5);
+    const int T = 12, ROUNDS = 40;
+    struct scoring { int8_t mat[25]; int od, ed, oi, ei; };
+    scoring sc[3];
+    const int ab[3][2] = {{1, 4}, {2, 3}, {1, 2}};
+    const int gp[3][4] = {{6, 1, 6, 1}, {5, 2, 7, 1}, {4, 1, 4, 1}};
+    for (int s = 0; s < 3; ++s) {
+        for (int i = 0; i < 5; ++i)
+            for (int j = 0; j < 5; ++j) sc[s].mat[i * 5 + j] = (int8_t)((i == 4 || j == 4) ? -1 : i == j ? ab[s][0] : -ab[s][1]);
+        sc[s].od = gp[s][0]; sc[s].ed = gp[s][1]; sc[s].oi = gp[s][2]; sc[s].ei = gp[s][3];
+    }
+    std::vector<int> bad(T, 0);
+    std::atomic<int> offender_bad{0}, done{0};
+    std::vector<std::thread> th;
+    for (int k = 0; k < T; ++k)
+        th.emplace_back([&, k]() {
+            rng_t r(300 + (uint64_t)k);
+            for (int round = 0; round < ROUNDS; ++round) {
+                const scoring &S = sc[(k + round) % 3];
+                const int tl = r.in(40, 200);
+                const int64_t at = r.below((int)(g.l_pac - tl - 1));
+                std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl), q = mutate(r, tg, 0.05, 0.03);
+                const int ql = (int)q.size(), w = abs(ql - tl) + 5;
+                const int call = (k + round) % 5;
+                if (call == 0 || call == 1) {
+                    int nc = 0, wnc = 0;
+                    uint32_t *cg = nullptr, *wcg = nullptr;
+                    int got, want;
+                    if (call == 0) {
+                        got = ksw_global2(ql, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.oi, S.ei, w, &nc, &cg);
+                        want = ksw_global2_ref(ql, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.oi, S.ei, w, &wnc, &wcg, nullptr);
+                    } else {
+                        got = ksw_global(ql, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, w, &nc, &cg);
+                        want = ksw_global2_ref(ql, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.od, S.ed, w, &wnc, &wcg, nullptr);
+                    }
+                    if (got != want || nc != wnc || (nc && memcmp(cg, wcg, (size_t)nc * 4) != 0)) ++bad[(size_t)k];
+                    free(cg); free(wcg);
+                } else if (call == 2 || call == 3) {
+                    const int ql2 = std::min(ql, 120);
+                    const int xtra = KSW_XSUBO | KSW_XSTART | (round % 2 ? KSW_XBYTE : 0) | 10;
+                    int32_t want[7];
+                    kswr_t got;
+                    if (call == 2) {
+                        got = ksw_align2(ql2, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.oi, S.ei, xtra, nullptr);
+                        ksw_align2_ref(ql2, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.oi, S.ei, xtra, want, nullptr);
+                    } else {
+                        got = ksw_align(ql2, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, xtra, nullptr);
+                        ksw_align2_ref(ql2, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.od, S.ed, xtra, want, nullptr);
+                    }
+                    const int32_t g7[7] = {got.score, got.te, got.qe, got.score2, got.te2, got.tb, got.qb};
+                    if (memcmp(g7, want, sizeof(want)) != 0) ++bad[(size_t)k];
+                } else {
+                    int gg[6], rr[6];
+                    gg[0] = ksw_extend2(ql, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.oi, S.ei, 100, 5, 100, 30, &gg[1], &gg[2], &gg[3], &gg[4], &gg[5]);
+                    rr[0] = ksw_extend2_ref(ql, q.data(), tl, tg.data(), 5, S.mat, S.od, S.ed, S.oi, S.ei, 100, 5, 100, 30, &rr[1], &rr[2], &rr[3], &rr[4], &rr[5], BSW_VARIANT_H, nullptr);
+                    if (memcmp(gg, rr, sizeof(gg)) != 0) ++bad[(size_t)k];
+                }
+            }
+            ++done;
+        });
+    int offender_calls = 0;
+    std::thread off([&]() {                                    /* one caller's over-limit task: only its own call fails */
+        std::vector<uint8_t> q(g.bases.begin(), g.bases.begin() + 2000), tg(g.bases.begin() + 10, g.bases.begin() + 2300);
+        while (done.load() < T || offender_calls < 3) {
+            const kswr_t a = ksw_align2(2000, q.data(), 2290, tg.data(), 5, sc[offender_calls % 3].mat, 6, 1, 6, 1, KSW_XSTART, nullptr);
+            if (a.score != -1) ++offender_bad;
+            ++offender_calls;
+            std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        }
+    });
+    for (auto &t : th) t.join();
+    off.join();
+    for (int k = 0; k < T; ++k) CHECK(bad[(size_t)k] == 0, "f4scalar: thread %d got %d answers that differ from the oracle's", k, bad[(size_t)k]);
+    CHECK(offender_bad.load() == 0, "f4scalar: %d of the offender's %d over-limit calls did not answer score -1", offender_bad.load(), offender_calls);
+    uint64_t calls = 0, trips = 0;
+    bsw_scalar_stats(&calls, &trips);
+    CHECK(calls == (uint64_t)(T * ROUNDS + offender_calls), "bsw_scalar_stats: %llu calls, made %d", (unsigned long long)calls, T * ROUNDS + offender_calls);
+    CHECK(trips >= 1 && trips < calls, "bsw_scalar_stats: %llu trips for %llu calls: nothing was coalesced", (unsigned long long)trips, (unsigned long long)calls);
+    printf("f4scalar: %llu calls in %llu trips, offender calls %d\n", (unsigned long long)calls, (unsigned long long)trips, offender_calls);
+    return 0;
+}
+
+/* ---- faults: call k of a clean run's C fails, for every k ---- */
+struct f4_outputs {
+    std::vector<bsw_gresult> g; std::vector<uint32_t> gc;
+    std::vector<bsw_kswr> a;
+    std::vector<bsw_cresult> c; std::vector<uint32_t> cc; std::vector<char> cm;
+    std::vector<bsw_mresult> m;
+    bool operator==(const f4_outputs &o) const
+    {
+        if (g.size() != o.g.size() || a.size() != o.a.size() || c.size() != o.c.size() || m.size() != o.m.size()) return false;
+        if (!g.empty() && memcmp(g.data(), o.g.data(), g.size() * sizeof(bsw_gresult)) != 0) return false;
+        for (size_t i = 0; i < g.size(); ++i)
+            for (int k = 0; k < g[i].n_cigar; ++k) if (gc[i * 48 + (size_t)k] != o.gc[i * 48 + (size_t)k]) return false;
+        if (!a.empty() && memcmp(a.data(), o.a.data(), a.size() * sizeof(bsw_kswr)) != 0) return false;
+        if (!c.empty() && memcmp(c.data(), o.c.data(), c.size() * sizeof(bsw_cresult)) != 0) return false;
+        for (size_t i = 0; i < c.size(); ++i) {
+            for (int k = 0; k < c[i].n_cigar; ++k) if (cc[i * 64 + (size_t)k] != o.cc[i * 64 + (size_t)k]) return false;
+            if (strcmp(&cm[i * 512], &o.cm[i * 512]) != 0) return false;
+        }
+        if (!m.empty() && memcmp(m.data(), o.m.data(), m.size() * sizeof(bsw_mresult)) != 0) return false;
+        return true;
+    }
+};
+
+static int f4faults_mode(const std::string &call)
+{
+    const bsw_params p = default_params();
+    genome_t g;
+    g.make(90001, 13);
+    const size_t n = 180;
+    uint64_t Csum = 0, failed = 0, ignored = 0;
+    for (int reg = 0; reg < 2; ++reg) {                        /* both memory kinds: the gather and the direct branch */
+    f4_outputs clean;
+    uint64_t C = 0;
+    for (uint64_t k = 0;; ++k) {
+        bool made = true;
+        fresh(1);
+        {
+            rng_t r(31);
+            arena_t ar(n * 900 + 8192, reg != 0);
+            gwork gw; awork aw; cwork cw; mwork mw;
+            if (call == "global") make_global(gw, ar, g, r, n);
+            else if (call == "align") make_align(aw, ar, g, r, n);
+            else if (call == "cigar") make_cigar(cw, ar, g, r, n);
+            else if (call == "matesw") make_matesw(mw, ar, g, r, n);
+            else CHECK(false, "faults global|align|cigar|matesw");
+            bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256, 2, 3000);
+            bsw_ref *ref = nullptr;
+            CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
+            auto run = [&](f4_outputs &o) {
+                o = f4_outputs();
+                if (call == "global") { o.g.assign(n, bsw_gresult{0, 0}); o.gc.assign(n * 48, 0); return bsw_global_batch(ctx, &p, gw.t.data(), n, 48, o.g.data(), o.gc.data()); }
+                if (call == "align") { o.a.resize(n); memset(o.a.data(), 0, n * sizeof(bsw_kswr)); return bsw_align_batch(ctx, &p, aw.t.data(), n, o.a.data()); }
+                if (call == "cigar") {
+                    o.c.resize(n); memset(o.c.data(), 0, n * sizeof(bsw_cresult)); o.cc.assign(n * 64, 0); o.cm.assign(n * 512, 0);
+                    return bsw_cigar_ref_batch(ctx, &p, ref, cw.t.data(), n, 64, o.cc.data(), 512, o.cm.data(), o.c.data());
+                }
+                o.m.resize(n); memset(o.m.data(), 0, n * sizeof(bsw_mresult));
+                return bsw_matesw_ref_batch(ctx, &p, ref, mw.t.data(), n, o.m.data());
+            };
+            hipdbl::reset_counters();
+            if (k) hipdbl::fail_overall(k);
+            f4_outputs first, again;
+            const int rc = run(first);
+            const char *f = hipdbl::fired();
+            const std::string fname = f ? f : "";
+            hipdbl::clear_failures();
+            if (k == 0) {
+                C = hipdbl::overall_calls();
+                CHECK(rc == BSW_OK, "the clean %s call -> %d (%s)", call.c_str(), rc, bsw_last_error(ctx));
+                clean = first;
+                if (call == "cigar") {
+                    int two = 0;
+                    for (const bsw_cresult &c : clean.c) two += c.tries >= 2 && c.status == 0;
+                    CHECK(two >= 10 && hipdbl::calls("launch_global") + hipdbl::calls("launch_global_long") >= 3, "the cigar batch of the fault sweep needs no second try");
+                }
+                Csum += C;
+                printf("faults %s, %s memory: C = %llu\n", call.c_str(), reg ? "registered" : "pageable", (unsigned long long)C);
+            } else if (!f) {
+                CHECK(k > C, "call %llu of the %s batch was never made (C = %llu)", (unsigned long long)k, call.c_str(), (unsigned long long)C);
+                CHECK(rc == BSW_OK && first == clean, "k=%llu: no failure happened and the results differ", (unsigned long long)k);
+                made = false;
+            } else if (rc != BSW_OK) {
+                ++failed;
+                const char *msg = bsw_last_error(ctx);
+                const bool alloc = fname == "hipMalloc" || fname == "hipHostMalloc";
+                CHECK(rc == (alloc ? BSW_E_NOMEM : BSW_E_HIP), "k=%llu: %s failed and the %s call answered %d (%s)", (unsigned long long)k, fname.c_str(), call.c_str(), rc, msg);
+                CHECK(msg && *msg, "k=%llu: %s failed, the call answered %d without a text", (unsigned long long)k, fname.c_str(), rc);
+            } else {
+                ++ignored;                                     /* (a release whose return code is ignored by design) */
+                CHECK(fname == "hipFree" || fname == "hipHostFree" || fname == "hipGetLastError", "k=%llu: %s failed and the %s call reported success", (unsigned long long)k, fname.c_str(), call.c_str());
+                CHECK(first == clean, "k=%llu: %s failed, the call reported success and its results differ", (unsigned long long)k, fname.c_str());
+            }
+            const int rc2 = run(again);                         /* the same call on the same context */
+            CHECK(rc2 == BSW_OK, "k=%llu (%s failed): the same call repeated -> %d (%s)", (unsigned long long)k, fname.c_str(), rc2, bsw_last_error(ctx));
+            CHECK(again == clean, "k=%llu (%s failed): the same call repeated is not bit-exact", (unsigned long long)k, fname.c_str());
+            bsw_ref_free(ctx, ref);
+            bsw_destroy(ctx);
+        }
+        CHECK(hipdbl::live_objects() == 0, "k=%llu: %zu HIP objects left alive after bsw_destroy", (unsigned long long)k, hipdbl::live_objects());
+        if (!made) break;
+    }
+    }
+    printf("faults %s: C = %llu, injection points visited = %llu, failed calls %llu, ignored releases %llu, skipped 0\n", call.c_str(), (unsigned long long)Csum,
+           (unsigned long long)(failed + ignored), (unsigned long long)failed, (unsigned long long)ignored);
+    CHECK(failed + ignored == Csum, "visited %llu of %llu", (unsigned long long)(failed + ignored), (unsigned long long)Csum);
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    const std::string mode = argc > 1 ? argv[1] : "";
+    if (mode == "f4" && argc > 2) return f4_mode(argv[2]);
+    if (mode == "f4split" && argc > 3) return f4split_mode(argv[2], argv[3]);
+    if (mode == "f4scalar") return f4scalar_mode();
+    if (mode == "faults" && argc > 2) return f4faults_mode(argv[2]);
+    fprintf(stderr, "usage: host_f4 f4 FILE | f4split count|z|b FILE | f4scalar | faults global|align|cigar|matesw\n");
+    return 2;
+}

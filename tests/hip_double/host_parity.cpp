@@ -6,7 +6,8 @@
  *   host_parity scalar    the drop-in ksw_extend2 from 8 threads
  *   host_parity devices   2, 3 and 8 devices, and one ordinal listed twice
  *   host_parity big K     120 000 two-sided 250 bp seeds as a resident batch under kernel mode K (0 AUTO, 1 WAVE, 2 LANE)
- *   host_parity tables    the class of probe seeds under this program's class tables (compared with the built library's)
+ *   host_parity tables    the class of probe seeds under this program's class tables (compared with the built library's), and
+ *                         the stand-ins' align and global class tables (compared with the kernel sources' initialisers)
  */
 #include <algorithm>
 #include <set>
@@ -352,7 +353,7 @@ static int big_mode(int kernel)
         workload w;
         make_workload(w, n, 250, 4242, false, false, 0.0001);      /* (a sequencer's N rate, 2 - 3 % of the reads: the host's sample then lets the N list pay) */
         const std::vector<bsw_result> want = expected(p, w.tasks.data(), n);
-        bsw_ctx *ctx = make_ctx(kernel, 1, 0, 4);
+        bsw_ctx *ctx = make_ctx(kernel, 1, 0, 4, 280000);     /* (one worker computes 120 000 seeds with the oracle: no watchdog; LIMIT is the bound) */
         run_resident(ctx, p, w, want, "big resident batch");
         bsw_destroy(ctx);
         beyond = standin::bins_beyond_4n16();
@@ -381,6 +382,13 @@ static int tables_mode()
                 if (s != 8 && seg[s + 1] > seg[s]) { at = s; break; }
             printf("table %d %d %d\n", kernel, q, at);
         }
+    printf("alignclasses %d\n", standin::align_class_count());
+    for (int byte = 0; byte < 2; ++byte)
+        for (int q = 0; q <= BSW_ALIGN_MAX_QLEN + 1; ++q) printf("alignclass %d %d %d\n", byte, q, standin::align_class_of(q, byte));
+    printf("globalclasses %d\n", standin::global_class_count());
+    for (int c = 0; c < standin::global_class_count(); ++c) printf("globalclass %d %d\n", c, standin::global_class_cols(c));
+    printf("globallongclasses %d\n", standin::global_long_class_count());
+    for (int c = 0; c < standin::global_long_class_count(); ++c) printf("globallong %d %d\n", c, standin::global_long_ring(c));
     return 0;
 }
 

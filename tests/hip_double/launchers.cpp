@@ -12,8 +12,14 @@
  *             the kernels' redo protocol is not mimicked.  What the lists must get right is kept in a LEDGER per chunk (which
  *             seed, which side, how often) and checked when the chunk's results are copied out: every side listed exactly once,
  *             no index >= n, no slice behind bsw_plan_order_capacity(n).
- *   not here  launch_global, launch_global_long, launch_align, launch_cigar_md answer hipErrorNotSupported: the global, align,
- *             CIGAR and mate-rescue hosts are outside what these stand-ins cover, and a test that reaches them fails loudly.
+ *   F4        launch_global / launch_global_long (oracle/ksw_global_ref.c), launch_align (oracle/ksw_align_ref.c; the query
+ *             reverse-complemented first under BSW_AD_QRC) and launch_cigar_md (a plain restatement of the contract in the head
+ *             comment of bsw_cigar_kernel.hip) serve bsw_global_batch, bsw_align_batch, bsw_cigar_ref_batch and
+ *             bsw_matesw_ref_batch.  They walk exactly order[0..n), read the task records and packed words the host staged, and
+ *             keep a ledger per result array and launch round (a round ends when the results are copied out): no index >= the
+ *             task count of the chunk's pack launch, no task listed twice, every task inside its launch's class, the slices
+ *             [z_off, +n_col * tlen) / [b_off, +tlen) of a round disjoint.  The first and the last byte / entry of every
+ *             slice are written, so ASan is the witness that it lies inside the host's reservation.
  * The class tables below restate the kernels' (bsw_wave_kernel.hip kWaveClasses, bsw_lane_kernel.hip kLaneClassesAll, ...);
  * tests/test_host_double_cpu.py compares the plans they lead to with the built library's.
  */
@@ -22,9 +28,13 @@
 #include "hip_double.h"
 #include "launchers.h"
 
+#include <algorithm>
 #include <map>
+#include <string>
 
 extern "C" void rtl_ref_pair_batch(const bsw_params *p, const bsw_task *tasks, size_t n, bsw_result *out);
+extern "C" void ksw_align2_ref(int qlen, const uint8_t *query, int tlen, const uint8_t *target, int m, const int8_t *mat, int o_del, int e_del,
+                               int o_ins, int e_ins, int xtra, int32_t *out, uint64_t *cells);
 
 namespace {
 
@@ -40,6 +50,11 @@ struct book_t {
     std::map<const void *, const void *> owner;      /* result array (bsw_result or bsw_pair) -> the chunk's task records */
     std::map<int, std::vector<uint32_t>> tags;
     uint64_t checked = 0, beyond = 0, max_end = 0, waits = 0;
+    /* the global / align / CIGAR hosts: one launch round per result array, the task count of the last pack launch per seq[] */
+    struct round_t { const void *seq = nullptr; std::vector<uint8_t> seen; std::vector<std::pair<uint64_t, uint64_t>> slices; };
+    std::map<const void *, round_t> f4;
+    std::map<const void *, uint32_t> pack_n;
+    uint64_t f4_rounds = 0, f4_tasks = 0;
 };
 book_t &B()
 {
@@ -55,8 +70,42 @@ std::shared_ptr<ledger_t> ledger_of(const void *tasks)
 }
 
 /* the chunk's results leave the device: every side must have been listed exactly once */
+void f4_round_ends(const void *src)
+{
+    book_t::round_t r;
+    {
+        std::lock_guard<std::mutex> lk(B().mu);
+        auto it = B().f4.find(src);
+        if (it == B().f4.end()) return;
+        r = std::move(it->second);
+        B().f4.erase(it);
+        ++B().f4_rounds;
+    }
+    std::sort(r.slices.begin(), r.slices.end());
+    for (size_t k = 1; k < r.slices.size(); ++k)
+        if (r.slices[k].first < r.slices[k - 1].first + r.slices[k - 1].second)
+            hipdbl::die("stand-in ledger: the scratch slices [%llu, +%llu) and [%llu, +%llu) of one launch round overlap", (unsigned long long)r.slices[k - 1].first,
+                        (unsigned long long)r.slices[k - 1].second, (unsigned long long)r.slices[k].first, (unsigned long long)r.slices[k].second);
+}
+
+/* a launch of the global / align stand-ins lists task idx, with the scratch slice [off, +len) (len 0: none) */
+void f4_note(const void *out, const void *seq, uint32_t idx, uint64_t off, uint64_t len, const char *who)
+{
+    std::lock_guard<std::mutex> lk(B().mu);
+    auto pn = B().pack_n.find(seq);
+    if (pn == B().pack_n.end()) hipdbl::die("stand-in %s: no pack launch has filled the seq[] it reads", who);
+    if (idx >= pn->second) hipdbl::die("stand-in %s: list entry %u >= the chunk's %u tasks", who, idx, pn->second);
+    book_t::round_t &r = B().f4[out];
+    r.seq = seq;
+    if (r.seen.size() < pn->second) r.seen.resize(pn->second, 0);
+    if (r.seen[idx]++) hipdbl::die("stand-in %s: task %u is listed twice in one launch round", who, idx);
+    if (len) r.slices.emplace_back(off, len);
+    ++B().f4_tasks;
+}
+
 void on_d2h(const void *src, size_t)
 {
+    f4_round_ends(src);
     std::shared_ptr<ledger_t> lg;
     const bsw_dtask *tasks = nullptr;
     {
@@ -151,14 +200,26 @@ namespace standin {
 void reset()
 {
     std::lock_guard<std::mutex> lk(B().mu);
-    B().by_tasks.clear(); B().owner.clear(); B().tags.clear();
-    B().checked = B().beyond = B().max_end = B().waits = 0;
+    B().by_tasks.clear(); B().owner.clear(); B().tags.clear(); B().f4.clear(); B().pack_n.clear();
+    B().checked = B().beyond = B().max_end = B().waits = B().f4_rounds = B().f4_tasks = 0;
 }
+uint64_t f4_rounds() { std::lock_guard<std::mutex> lk(B().mu); return B().f4_rounds; }
+uint64_t f4_tasks() { std::lock_guard<std::mutex> lk(B().mu); return B().f4_tasks; }
 std::vector<uint32_t> device_tags(int dev) { std::lock_guard<std::mutex> lk(B().mu); return B().tags[dev]; }
 uint64_t chunks_checked() { std::lock_guard<std::mutex> lk(B().mu); return B().checked; }
 uint64_t bins_beyond_4n16() { std::lock_guard<std::mutex> lk(B().mu); return B().beyond; }
 uint64_t max_order_end() { std::lock_guard<std::mutex> lk(B().mu); return B().max_end; }
 uint64_t chain_waits() { std::lock_guard<std::mutex> lk(B().mu); return B().waits; }
+}  // namespace standin
+
+static int long_ring(int cls) { return 256 << cls; }
+namespace standin {
+int align_class_count() { return bsw::align_class_count(); }
+int align_class_of(int qlen, int byte_mode) { return bsw::align_class_of(qlen, byte_mode); }
+int global_class_count() { return bsw::global_class_count(); }
+int global_class_cols(int cls) { return bsw::global_class_cols(cls); }
+int global_long_class_count() { return bsw::GLOBAL_LONG_CLASSES; }
+int global_long_ring(int cls) { return long_ring(cls); }
 }  // namespace standin
 
 #define STANDIN_GATE(name)                                  \
@@ -224,6 +285,11 @@ hipError_t launch_pack(const uint8_t *raw, const bsw_dtask *tasks, const bsw_raw
     hipdbl::enqueue(s, [=]() {
         if (pac && n && hipdbl::device_of_ptr(pac, (size_t)((l_pac + 3) >> 2)) != dev)
             hipdbl::die("stand-in launch_pack: the reference copy handed to a chunk of device %d does not live there", dev);
+        {                                               /* a new chunk: a round a failed call left open ends unchecked */
+            std::lock_guard<std::mutex> lk(B().mu);
+            B().pack_n[seq] = n;
+            for (auto it = B().f4.begin(); it != B().f4.end();) it = it->second.seq == seq ? B().f4.erase(it) : std::next(it);
+        }
         for (uint32_t ti = 0; ti < n; ++ti) {
             const bsw_dtask &T = tasks[ti];
             int hasn = 0;
@@ -451,10 +517,152 @@ hipError_t launch_pairs_from_results(const uint32_t *order, uint32_t n, const ui
     return hipSuccess;
 }
 
-/* ---- not covered (see the file header) ---- */
-hipError_t launch_global(int, const bsw_dparams &, const uint64_t *, const bsw_gdtask *, const uint32_t *, uint32_t, uint8_t *, uint32_t *, int, bsw_gresult *, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_global_long(int, const bsw_dparams &, const uint64_t *, const bsw_gdtask *, const uint32_t *, uint32_t, uint8_t *, uint32_t *, int, bsw_gresult *, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_align(int, const bsw_dparams &, const uint64_t *, const bsw_adtask *, const uint32_t *, uint32_t, unsigned long long *, bsw_kswr *, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_cigar_md(const bsw_dparams &, const uint64_t *, const bsw_cdtask *, uint32_t, uint32_t *, int, const bsw_gresult *, char *, int, bsw_cresult *, hipStream_t) { return hipErrorNotSupported; }
+/* ---- banded global alignment, local alignment, NM / MD (see the file header: F4) ---- */
+static hipError_t global_standin(const char *who, int cols, int ring, const bsw_dparams &P_, const uint64_t *seq, const bsw_gdtask *tasks,
+                                 const uint32_t *order, uint32_t n, uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
+{
+    const bsw_dparams P = P_;
+    hipdbl::enqueue(s, [=]() {
+        std::vector<uint8_t> q, t;
+        for (uint32_t slot = 0; slot < n; ++slot) {
+            const uint32_t idx = order[slot];
+            const bsw_gdtask &T = tasks[idx];
+            const int n_col = T.qlen < 2 * T.w + 1 ? T.qlen : 2 * T.w + 1;
+            if (cols && T.qlen + 1 > cols) hipdbl::die("stand-in %s: task %u (%d query bases) does not fit a class of %d columns", who, idx, T.qlen, cols);
+            if (ring && n_col + 1 > ring) hipdbl::die("stand-in %s: task %u (band of %d columns) does not fit a ring of %d records", who, idx, n_col, ring);
+            const uint64_t zlen = z ? (uint64_t)(n_col > 0 ? n_col : 0) * (uint64_t)T.tlen : 0;
+            f4_note(out, seq, idx, T.z_off, zlen, who);
+            if (zlen) { z[T.z_off] = 0; z[T.z_off + zlen - 1] = 0; }
+            unpack(seq, T.q_off, T.qlen, q);
+            unpack(seq, T.t_off, T.tlen, t);
+            int nc = 0;
+            uint32_t *cg = nullptr;
+            bsw_gresult r;
+            r.score = ksw_global2_ref(T.qlen, q.data(), T.tlen, t.data(), 5, P.mat, P.o_del, P.e_del, P.o_ins, P.e_ins, T.w, z ? &nc : nullptr, z ? &cg : nullptr, nullptr);
+            r.n_cigar = nc <= max_cigar ? nc : -nc;
+            if (z && cigars)
+                for (int k = 0; k < nc && k < max_cigar; ++k) cigars[(size_t)idx * (size_t)max_cigar + (size_t)k] = cg[k];
+            free(cg);
+            out[idx] = r;
+        }
+    });
+    return hipSuccess;
+}
+
+hipError_t launch_global_long(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *order, uint32_t n, uint8_t *z,
+                              uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
+{
+    STANDIN_GATE("launch_global_long");
+    if (n == 0) return hipSuccess;
+    if (cls < 0 || cls >= GLOBAL_LONG_CLASSES) return hipErrorInvalidValue;
+    return global_standin("launch_global_long", 0, long_ring(cls), P, seq, tasks, order, n, z, cigars, max_cigar, out, s);
+}
+
+hipError_t launch_global(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *order, uint32_t n, uint8_t *z,
+                         uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
+{
+    if (n && cls >= global_class_count()) return launch_global_long(cls - global_class_count(), P, seq, tasks, order, n, z, cigars, max_cigar, out, s);
+    STANDIN_GATE("launch_global");
+    if (n == 0) return hipSuccess;
+    if (cls < 0) return hipErrorInvalidValue;
+    return global_standin("launch_global", global_class_cols(cls), 0, P, seq, tasks, order, n, z, cigars, max_cigar, out, s);
+}
+
+hipError_t launch_align(int cls, const bsw_dparams &P_, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,
+                        unsigned long long *blist, bsw_kswr *out, hipStream_t s)
+{
+    STANDIN_GATE("launch_align");
+    if (n == 0) return hipSuccess;
+    if (cls < 0 || cls >= align_class_count()) return hipErrorInvalidValue;
+    const bsw_dparams P = P_;
+    hipdbl::enqueue(s, [=]() {
+        std::vector<uint8_t> q, t;
+        for (uint32_t slot = 0; slot < n; ++slot) {
+            const uint32_t idx = order[slot];
+            const bsw_adtask &T = tasks[idx];
+            const int want = align_class_of(T.qlen, (T.xtra & KSW_XBYTE) != 0);
+            if (want != cls) hipdbl::die("stand-in launch_align: task %u (%d query bases, xtra 0x%x) belongs to class %d and is listed for class %d", idx, T.qlen, (unsigned)T.xtra, want, cls);
+            const uint64_t blen = (T.xtra & KSW_XSUBO) ? (uint64_t)T.tlen : 0;
+            f4_note(out, seq, idx, T.b_off, blen, "launch_align");
+            if (blen) { blist[T.b_off] = 0; blist[T.b_off + blen - 1] = 0; }
+            unpack(seq, T.q_off, T.qlen, q);
+            unpack(seq, T.t_off, T.tlen, t);
+            if (T.pad & BSW_AD_QRC) {
+                std::reverse(q.begin(), q.end());
+                for (uint8_t &c : q) c = c < 4 ? (uint8_t)(3 - c) : (uint8_t)4;
+            }
+            int32_t r[7];
+            ksw_align2_ref(T.qlen, q.data(), T.tlen, t.data(), 5, P.mat, P.o_del, P.e_del, P.o_ins, P.e_ins, T.xtra, r, nullptr);
+            memcpy(&out[idx], r, sizeof(bsw_kswr));
+        }
+    });
+    return hipSuccess;
+}
+
+hipError_t launch_cigar_md(const bsw_dparams &P_, const uint64_t *seq, const bsw_cdtask *tasks, uint32_t n, uint32_t *cigars, int max_cigar,
+                           const bsw_gresult *gres, char *md, int max_md, bsw_cresult *res, hipStream_t s)
+{
+    STANDIN_GATE("launch_cigar_md");
+    if (n == 0) return hipSuccess;
+    const bsw_dparams P = P_;
+    hipdbl::enqueue(s, [=]() {
+        std::vector<uint8_t> q, t;
+        for (uint32_t ti = 0; ti < n; ++ti) {
+            const bsw_cdtask &T = tasks[ti];
+            char *slot = md ? md + (size_t)ti * (size_t)max_md : nullptr;
+            uint32_t *cg = cigars + (size_t)ti * (size_t)max_cigar;
+            bsw_cresult r;
+            memset(&r, 0, sizeof(r));
+            const bool nogap = (T.flags & BSW_CD_NOGAP) != 0;
+            int n_cigar;
+            if (T.flags & BSW_CD_STATUS) n_cigar = -1;
+            else if (nogap) { n_cigar = 1; cg[0] = (uint32_t)T.qlen << 4; }
+            else { r.score = gres[ti].score; n_cigar = gres[ti].n_cigar; }
+            if (n_cigar < 0) {                               /* no alignment, or a CIGAR that did not fit: no NM, no MD */
+                if (!(T.flags & BSW_CD_STATUS)) r.n_cigar = n_cigar;
+                r.nm = -1;
+                if (slot) slot[0] = 0;
+                res[ti] = r;
+                continue;
+            }
+            unpack(seq, T.q_off, T.qlen, q);
+            unpack(seq, T.t_off, T.tlen, t);
+            const char *letters = (T.flags & BSW_CD_REV) ? "TGCAN" : "ACGTN";
+            std::string m;
+            int x = 0, y = 0, u = 0, nm = 0, sc = 0;
+            for (int k = 0; k < n_cigar; ++k) {
+                const int op = (int)(cg[k] & 0xf), len = (int)(cg[k] >> 4);
+                if (op == 0) {
+                    for (int i = 0; i < len; ++i) {
+                        const int qb = q[(size_t)(x + i)] < 4 ? q[(size_t)(x + i)] : 4, tb = t[(size_t)(y + i)] < 4 ? t[(size_t)(y + i)] : 4;
+                        sc += P.mat[tb * 5 + qb];
+                        if (qb != tb) { m += std::to_string(u); m += letters[tb]; u = 0; ++nm; }
+                        else ++u;
+                    }
+                    x += len; y += len;
+                } else if (op == 2) {
+                    if (k > 0 && k < n_cigar - 1) {          /* a leading or trailing D is in neither MD nor NM */
+                        m += std::to_string(u); m += '^';
+                        for (int i = 0; i < len; ++i) m += letters[t[(size_t)(y + i)] < 4 ? t[(size_t)(y + i)] : 4];
+                        u = 0; nm += len;
+                    }
+                    y += len;
+                } else if (op == 1) { x += len; nm += len; }
+            }
+            m += std::to_string(u);
+            if (nogap) r.score = sc;
+            r.n_cigar = n_cigar;
+            r.nm = nm;
+            r.md_len = (int32_t)m.size();
+            if (slot) {
+                if ((int)m.size() < max_md) memcpy(slot, m.c_str(), m.size() + 1);
+                else { slot[0] = 0; r.md_len = -((int32_t)m.size() + 1); }
+            }
+            r.tries = nogap ? ((T.more && r.score < T.min_score) ? 2 : 1) : 0;
+            res[ti] = r;
+        }
+    });
+    return hipSuccess;
+}
 
 }  // namespace bsw

@@ -1487,10 +1487,6 @@ BSW_LOCAL int run_chunk(bsw_ctx *ctx, errs &e, stage_t &st, hipStream_t s, hipEv
 
 /* ---- streaming submit: one host thread per (device, slot); chunk k -> device k mod G, slot (k / G) mod S —
  * the round-robin of the reference's four TBB/RBB pairs over its PE arrays (batch_manager.v:343-348,418,745-773) ---- */
-struct chunk_span {
-    size_t base, cnt;
-};
-
 /* tasks[0..n) -> per-device chunk lists.  Chunks are equal-sized (a short tail chunk would fall below the lane
  * kernel's minimum batch), chunk c of the plan belongs to device c mod G, and every device's first
  * chunk is cut in two so that its first DMA — the only one no kernel overlaps — is short. */
@@ -1525,7 +1521,10 @@ static std::vector<std::vector<chunk_span>> plan_chunks(size_t n, size_t chunk, 
  * One slot = one host thread + one stream + one set of staging buffers.  Per chunk: host pass (validate, lay out, count) ->
  * wait for the slot's previous chunk -> input DMAs in the device's chunk order -> pack, bin, DP kernels -> result DMA.  The
  * host pass of the slot's next chunk runs while its previous one is still on the GPU: it only needs the pinned host staging,
- * which is free again as soon as that chunk's input DMAs are done. */
+ * which is free again as soon as that chunk's input DMAs are done.
+ * A ticket has a KIND: seed extension (above), or one of the two stages behind it against the resident reference — CIGAR
+ * (bsw_cigar_ref_submit_t) and mate rescue (bsw_matesw_ref_submit_t) — whose chunks run cigar_chunk / matesw_chunk on the slot's
+ * lane (process_f4 in slot_main).  All kinds share the ticket space, BSW_MAX_INFLIGHT and the devices' queues. */
 struct ticket_t {
     uint64_t id = 0;
     bsw_params p{};
@@ -1536,6 +1535,8 @@ struct ticket_t {
     bsw_result *out = nullptr;
     bool packed = false;
     size_t n = 0;
+    int kind = 0;                               /* 0 seed extension; 1 CIGAR, 2 mate rescue (f4: bsw_cigar_ref_submit_t / bsw_matesw_ref_submit_t) */
+    f4_submit f4;
     std::atomic<size_t> remaining{0};           /* chunks whose results have not been handed over yet */
     size_t nchunks = 0;                         /* chunks the submit was cut into */
     std::atomic<int> abort{0};                  /* a chunk failed: the others do nothing any more */
@@ -1549,7 +1550,8 @@ struct ticket_t {
 struct chunk_job {
     ticket_t *t = nullptr;
     chunk_span span{0, 0};
-    size_t seq = 0;                             /* the chunk's place in its device's input-DMA order */
+    size_t seq = 0;                             /* the chunk's place in its device's input-DMA order (extension chunks only: a
+                                                   CIGAR or rescue chunk gets no number and never waits at, or holds up, the gate) */
 };
 
 struct dev_pipe {
@@ -1736,13 +1738,50 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
                          d, s, (unsigned long long)tid, base, n, t1 - t0, t2 - t1, t3 - t2, tnow() - t3, t0, rc ? " FAILED" : "");
     };
 
+    /* A CIGAR or mate-rescue chunk: the whole of cigar_chunk / matesw_chunk on the slot's lane — its stage_t, its stream, its
+     * watchdog event, its own scratch, the reference copy of its device.  The chunk function waits for its own work (read-backs
+     * into pinned memory in front of sync_stream) and drains the stream itself when it fails, so nothing of the chunk is queued
+     * when it reports; it takes no turn at the input-DMA gate. */
+    f4_lane lane;
+    lane.dev = d; lane.st = &st; lane.s = stream; lane.ev = dev.events[s];
+    lane.bind(dev.f4[s]);
+    lane.h_back = &dev.f4[s].h_back;
+    lane.h_in = &dev.f4[s].h_in;
+    auto process_f4 = [&](const chunk_job &job) {
+        ticket_t *t = job.t;
+        const f4_submit &f = t->f4;
+        const size_t n = job.span.cnt, base = job.span.base;
+        const uint64_t tid = t->id;
+        const double t0 = dbg ? tnow() : 0;
+        finish();                                   /* the slot's extension chunk in flight owns the stage_t until it is handed over */
+        errs e;
+        int rc = BSW_OK;
+        lane.abort = &t->abort;
+        lane.h2d = lane.d2h = 0;
+        if (dev_err != hipSuccess) {
+            rc = fail(e, BSW_E_HIP, "hipSetDevice: %s", hipGetErrorString(dev_err));
+            dev_err = hipSetDevice(dev.device);
+        } else if (ctx->dead) rc = fail(e, BSW_E_HIP, "context is dead (an earlier wait for the GPU timed out)");      /* nothing more is queued on a hung device */
+        else if (t->abort) rc = fail(e, BSW_E_HIP, "aborted: another chunk failed");
+        else if (f.kind == 1)
+            rc = cigar_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ctasks + base, n, f.max_cigar, f.cigars ? f.cigars + base * (size_t)f.max_cigar : nullptr,
+                             f.max_md, f.md ? f.md + base * (size_t)f.max_md : nullptr, f.cres + base);
+        else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks + base, n, f.mres + base);
+        if (rc) ticket_fail(t, rc, e);
+        else { pp.h2d_bytes += lane.h2d; pp.d2h_bytes += lane.d2h; pp.chunks += 1; }
+        chunk_done(t);                              /* (the ticket may be collected and freed from here on) */
+        if (dbg) fprintf(stderr, "[bsw] slot %zu.%zu ticket %llu %s chunk @%zu n=%zu: %.3f ms (t0=%.3f)%s\n", d, s, (unsigned long long)tid,
+                         f.kind == 1 ? "cigar" : "matesw", base, n, tnow() - t0, t0, rc ? " FAILED" : "");
+    };
+
     std::unique_lock<std::mutex> lk(pp.mu);
     for (;;) {
         if (!dq.q.empty()) {
             const chunk_job job = dq.q.front();
             dq.q.pop_front();
             lk.unlock();
-            process(job);
+            if (job.t->kind) process_f4(job);
+            else process(job);
             account();
             lk.lock();
             continue;
@@ -1856,6 +1895,37 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
         for (size_t k = 0; left; ++k)
             for (size_t d = 0; d < G; ++d)
                 if (k < chunks[d].size()) { pp.devs[d]->q.push_back(chunk_job{t.get(), chunks[d][k], pp.devs[d]->next_seq++}); --left; }
+        pp.live.push_back(std::move(t));
+        pp.submits += 1;
+    }
+    pp.cv_work.notify_all();
+    return BSW_OK;
+}
+
+/* a validated CIGAR / mate-rescue submit (bsw_cigar.hip, bsw_matesw.hip) becomes a ticket: one ticket space with the extension
+ * submits, the same BSW_MAX_INFLIGHT, chunk k on device k mod G behind whatever the devices' queues hold already */
+BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket, const char *what)
+{
+    if (ticket) *ticket = 0;
+    errs e;
+    int rc = pipeline_start(ctx);
+    if (rc) return rc;
+    pipeline &pp = *ctx->pipe.load();
+    const size_t G = ctx->devs.size();
+    std::shared_ptr<ticket_t> t(new ticket_t());
+    t->kind = f.kind; t->n = f.n; t->ref = f.ref; t->p = f.pp; t->dp = f.dp;
+    t->f4 = std::move(f);
+    const size_t total = t->f4.spans.size();
+    t->remaining = total;
+    t->nchunks = total;
+    t->done = total == 0;
+    {
+        std::lock_guard<std::mutex> lk(pp.mu);
+        if (pp.live.size() >= BSW_MAX_INFLIGHT)
+            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "%s: %d submits in flight already (BSW_MAX_INFLIGHT); wait for one first", what, BSW_MAX_INFLIGHT));
+        t->id = pp.next_id++;
+        if (ticket) *ticket = t->id;
+        for (size_t k = 0; k < total; ++k) pp.devs[k % G]->q.push_back(chunk_job{t.get(), t->f4.spans[k], 0});
         pp.live.push_back(std::move(t));
         pp.submits += 1;
     }

@@ -12,6 +12,10 @@
  *      the packed sequences stay where they are.  A try whose band (after bwa's formula) equals the previous one's would
  *      return the previous score and end the loop on "score == last": it is counted, not run;
  *   3. bsw_cigar_md_kernel derives NM and MD once per task from its final CIGAR, and settles bwa's no-gap shortcut.
+ *
+ * A chunk runs on a LANE (f4_lane, bsw_internal.h): bsw_cigar_ref_batch passes the context's own — first device, stream 0, blocking
+ * read-backs —, bsw_cigar_ref_submit_t cuts the submit by work and hands the chunks to the slot pipeline (bsw_batch.hip), whose
+ * slots each own a lane on their device and read back into pinned memory in front of the watchdog's wait.
  */
 #include "bsw_internal.h"
 
@@ -46,11 +50,11 @@ struct cstate {                       /* one task's place in mem_reg2aln's loop 
     bool live;                        /* still has a try to run */
 };
 
-static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
-                       size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res)
+BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
+                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res)
 {
-    stage_t &st = ctx->small;
-    hipStream_t s = ctx->stream0();
+    stage_t &st = *L.st;
+    hipStream_t s = L.s;
     hipError_t he;
     const int64_t l_pac = ref->l_pac;
     if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
@@ -140,30 +144,40 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
     if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
         (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
         (he = st.d_desc.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->g_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->g_res.reserve(n + 1)) != hipSuccess || (he = ctx->g_z.reserve((size_t)zmax + 64)) != hipSuccess ||
-        (he = ctx->g_cig.reserve(n * (size_t)max_cigar + 1)) != hipSuccess ||
-        (he = ctx->c_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->c_res.reserve(n + 1)) != hipSuccess ||
-        (md && (he = ctx->c_md.reserve(n * (size_t)max_md + 1)) != hipSuccess))
+        (he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
+        (he = L.g_res->reserve(n + 1)) != hipSuccess || (he = L.g_z->reserve((size_t)zmax + 64)) != hipSuccess ||
+        (he = L.g_cig->reserve(n * (size_t)max_cigar + 1)) != hipSuccess ||
+        (he = L.c_tasks->reserve(n + 1)) != hipSuccess || (he = L.c_res->reserve(n + 1)) != hipSuccess ||
+        (md && (he = L.c_md->reserve(n * (size_t)max_md + 1)) != hipSuccess))
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    /* a slot reads back into pinned memory: the scores of a try, then results | CIGARs | MD slots */
+    const size_t back_cig = n * sizeof(bsw_cresult), back_md = back_cig + (cigars ? n * (size_t)max_cigar * sizeof(uint32_t) : 0),
+                 back_end = back_md + (md ? n * (size_t)max_md : 0);
+    const size_t in_gt = (n + 1) * sizeof(bsw_cdtask), in_order = in_gt + (n + 1) * sizeof(bsw_gdtask);
+    if (L.h_back && ((he = L.h_back->reserve(std::max(back_end, n * sizeof(bsw_gresult)) + 16)) != hipSuccess ||
+                     (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
+        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     /* what the tries need (declared here: the guard behind them is destroyed first) */
     const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
     const bool force_long = cigar_force_long();
-    std::vector<bsw_gresult> gr(n);
+    std::vector<bsw_gresult> gr(L.h_back ? 0 : n);
+    const bsw_gresult *grp = L.h_back ? (const bsw_gresult *)L.h_back->p : gr.data();
     std::vector<uint32_t> order, cnt((size_t)(ncls + nlong) + 1), cls;
     std::vector<uint32_t> live;
-    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
+    drain_on_failure drain(ctx, s, L.ev);
     if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(ctx->c_tasks.p, cd.data(), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
-    HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 1, ref->d_pac[0], l_pac, st.d_desc.p,
+    HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), n * sizeof(bsw_cdtask), 0), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
+    L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_cdtask));
+    HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 1, ref->d_pac[L.dev], l_pac, st.d_desc.p,
                                st.d_seq.p, nullptr, s));
 
     /* the tries: each launches the global kernels on the tasks still in the loop, then reads their scores */
     for (size_t i = 0; i < n; ++i) if (cs[i].live) live.push_back((uint32_t)i);
     while (!live.empty()) {
+        if (L.abort && L.abort->load()) return fail(e, BSW_E_HIP, "aborted: another chunk failed");
         std::fill(cnt.begin(), cnt.end(), 0u);
         cls.assign(live.size(), 0u);
         uint64_t zacc = 0;
@@ -185,23 +199,26 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
             std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
             for (size_t k = 0; k < live.size(); ++k) order[pos[cls[k]]++] = live[k];
         }
-        HIPCHK(e, hipMemcpyAsync(ctx->g_tasks.p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, L.dma_src(gt.data(), n * sizeof(bsw_gdtask), in_gt), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(order.data(), order.size() * sizeof(uint32_t), in_order), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        L.h2d += n * sizeof(bsw_gdtask) + order.size() * sizeof(uint32_t);
         for (int c = 0; c < ncls + nlong; ++c) {
             const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
             if (!k) continue;
-            HIPCHK(e, bsw::launch_global(c, dp, st.d_seq.p, ctx->g_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->g_z.p, ctx->g_cig.p,
-                                         max_cigar, ctx->g_res.p, s));
+            HIPCHK(e, bsw::launch_global(c, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.g_z->p, L.g_cig->p,
+                                         max_cigar, L.g_res->p, s));
         }
-        int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
+        if (L.h_back) HIPCHK(e, hipMemcpyAsync(L.h_back->p, L.g_res->p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost, s));
+        int rc = sync_stream(ctx, e, s, L.ev);
         if (rc) return rc;
-        HIPCHK(e, hipMemcpy(gr.data(), ctx->g_res.p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost));
+        if (!L.h_back) HIPCHK(e, hipMemcpy(gr.data(), L.g_res->p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost));
+        L.d2h += n * sizeof(bsw_gresult);
         /* mem_reg2aln: if (score == last || w2 == w_cap) break; last = score; w2 <<= 1; } while (++i < max_tries && score < min_score) */
         std::vector<uint32_t> next;
         for (uint32_t i : live) {
             cstate &q = cs[i];
             const bsw_ctask &t = tasks[i];
-            const int score = gr[i].score;
+            const int score = grp[i].score;
             ++q.tries;
             q.live = false;
             if (score == q.last || q.w2 == q.wcap) continue;
@@ -220,13 +237,26 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
         }
         live.swap(next);
     }
-    HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, ctx->c_tasks.p, (uint32_t)n, ctx->g_cig.p, max_cigar, ctx->g_res.p,
-                                   md ? ctx->c_md.p : nullptr, max_md, ctx->c_res.p, s));
-    int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
-    if (rc) return rc;
-    HIPCHK(e, hipMemcpy(res, ctx->c_res.p, n * sizeof(bsw_cresult), hipMemcpyDeviceToHost));
-    if (cigars) HIPCHK(e, hipMemcpy(cigars, ctx->g_cig.p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (md) HIPCHK(e, hipMemcpy(md, ctx->c_md.p, n * (size_t)max_md, hipMemcpyDeviceToHost));
+    HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.c_tasks->p, (uint32_t)n, L.g_cig->p, max_cigar, L.g_res->p,
+                                   md ? L.c_md->p : nullptr, max_md, L.c_res->p, s));
+    if (L.h_back) {
+        uint8_t *hb = L.h_back->p;
+        HIPCHK(e, hipMemcpyAsync(hb, L.c_res->p, n * sizeof(bsw_cresult), hipMemcpyDeviceToHost, s));
+        if (cigars) HIPCHK(e, hipMemcpyAsync(hb + back_cig, L.g_cig->p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (md) HIPCHK(e, hipMemcpyAsync(hb + back_md, L.c_md->p, n * (size_t)max_md, hipMemcpyDeviceToHost, s));
+        int rc = sync_stream(ctx, e, s, L.ev);
+        if (rc) return rc;
+        memcpy(res, hb, n * sizeof(bsw_cresult));
+        if (cigars) memcpy(cigars, hb + back_cig, n * (size_t)max_cigar * sizeof(uint32_t));
+        if (md) memcpy(md, hb + back_md, n * (size_t)max_md);
+    } else {
+        int rc = sync_stream(ctx, e, s, L.ev);
+        if (rc) return rc;
+        HIPCHK(e, hipMemcpy(res, L.c_res->p, n * sizeof(bsw_cresult), hipMemcpyDeviceToHost));
+        if (cigars) HIPCHK(e, hipMemcpy(cigars, L.g_cig->p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (md) HIPCHK(e, hipMemcpy(md, L.c_md->p, n * (size_t)max_md, hipMemcpyDeviceToHost));
+    }
+    L.d2h += back_end;
     for (size_t i = 0; i < n; ++i) {
         bsw_cresult &r = res[i];
         if (cd[i].flags & BSW_CD_STATUS) {
@@ -242,6 +272,36 @@ static int cigar_chunk(bsw_ctx *ctx, errs &e, const bsw_params &pp, const bsw_dp
     return BSW_OK;
 }
 
+/* what both entry points check before anything runs or is queued: the parameters (the band is per task: pp gets w = 0), then
+ * the tasks in order — the first malformed one rejects the call */
+static int cigar_validate(errs &e, const bsw_params *p, const bsw_ctask *tasks, size_t n, bsw_params *pp, bsw_dparams *dp)
+{
+    *pp = *p;
+    pp->w = 0;                                        /* the band is per task here */
+    int rc = check_params(e, pp, dp);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_ctask &t = tasks[i];
+        if (t.l_query < 0 || t.w < 0 || t.w_cap < 0 || t.max_tries < 0 || t.max_tries > 3)
+            return fail(e, BSW_E_INVAL, "cigar task %zu: negative length or band, or max_tries outside 0..3", i);
+        if (t.l_query && !t.query) return fail(e, BSW_E_INVAL, "cigar task %zu: NULL read", i);
+        if (t.l_query > BSW_GLOBAL_MAX_QLEN || t.w > BSW_MAX_TLEN || t.w_cap > BSW_MAX_TLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
+            return fail(e, BSW_E_LIMIT, "cigar task %zu: beyond BSW_GLOBAL_MAX_QLEN / BSW_MAX_TLEN", i);
+    }
+    return BSW_OK;
+}
+
+/* backtrack bytes (its widest band) and sequence bytes one task adds to a sub-batch */
+static void cigar_task_cost(const bsw_params &pp, const bsw_ctask &t, uint64_t &nz, uint64_t &ns)
+{
+    nz = ns = 0;
+    if (t.l_query > 0 && t.re > t.rb && t.re - t.rb <= BSW_MAX_TLEN) {
+        const int rlen = (int)(t.re - t.rb), wmax = gen_cigar_band(pp, t.l_query, rlen, INT_MAX);
+        nz = (uint64_t)std::min(t.l_query, 2 * wmax + 1) * (uint64_t)rlen;
+        ns = (uint64_t)t.l_query + (uint64_t)rlen;
+    }
+}
+
 extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ctask *tasks, size_t n,
                                    int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res)
 {
@@ -253,42 +313,82 @@ extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
         return fail(e, BSW_E_INVAL, "bsw_cigar_ref_batch: the reference was uploaded through another context");
     int rc = busy_check(ctx, "bsw_cigar_ref_batch");
     if (rc) return rc;
-    bsw_params pp = *p;
-    pp.w = 0;                                         /* the band is per task here */
+    bsw_params pp;
     bsw_dparams dp;
-    rc = check_params(e, &pp, &dp);
+    rc = cigar_validate(e, p, tasks, n, &pp, &dp);
     if (rc) return rc;
-    for (size_t i = 0; i < n; ++i) {
-        const bsw_ctask &t = tasks[i];
-        if (t.l_query < 0 || t.w < 0 || t.w_cap < 0 || t.max_tries < 0 || t.max_tries > 3)
-            return fail(e, BSW_E_INVAL, "cigar task %zu: negative length or band, or max_tries outside 0..3", i);
-        if (t.l_query && !t.query) return fail(e, BSW_E_INVAL, "cigar task %zu: NULL read", i);
-        if (t.l_query > BSW_GLOBAL_MAX_QLEN || t.w > BSW_MAX_TLEN || t.w_cap > BSW_MAX_TLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
-            return fail(e, BSW_E_LIMIT, "cigar task %zu: beyond BSW_GLOBAL_MAX_QLEN / BSW_MAX_TLEN", i);
-    }
     HIPCHK(e, hipSetDevice(ctx->device0()));
+    f4_lane L = ctx_lane(ctx);
     /* sub-batches: bounded backtrack memory (the widest band of any try) and sequence arena, as bsw_global_batch */
     const uint64_t zcap = 4ull << 30;
     for (size_t a = 0; a < n;) {
         size_t b = a;
         uint64_t zb = 0, sb = 0;
         while (b < n && b - a < (1u << 20)) {
-            const bsw_ctask &t = tasks[b];
-            uint64_t nz = 0, ns = 0;
-            if (t.l_query > 0 && t.re > t.rb && t.re - t.rb <= BSW_MAX_TLEN) {
-                const int rlen = (int)(t.re - t.rb), wmax = gen_cigar_band(pp, t.l_query, rlen, INT_MAX);
-                nz = (uint64_t)std::min(t.l_query, 2 * wmax + 1) * (uint64_t)rlen;
-                ns = (uint64_t)t.l_query + (uint64_t)rlen;
-            }
+            uint64_t nz, ns;
+            cigar_task_cost(pp, tasks[b], nz, ns);
             if (b > a && (zb + nz > zcap || sb + ns > (1ull << 31))) break;
             zb += nz;
             sb += ns;
             ++b;
         }
-        rc = cigar_chunk(ctx, e, pp, dp, ref, tasks + a, b - a, max_cigar, cigars ? cigars + a * (size_t)max_cigar : nullptr, max_md,
+        rc = cigar_chunk(ctx, e, L, pp, dp, ref, tasks + a, b - a, max_cigar, cigars ? cigars + a * (size_t)max_cigar : nullptr, max_md,
                          md ? md + a * (size_t)max_md : nullptr, res + a);
         if (rc) return rc;
         a = b;
     }
     return BSW_OK;
+}
+
+/* The work target of a CIGAR chunk, in cells (min(l_query, 2 w + 1) x (re - rb) with the widest band a try can reach, summed
+ * over its tasks — the chunk's backtrack bytes), from the sweep of tools/f4_stream_rate.py ("sweep_cigar" of
+ * profiles/f4_stream_rate.json): 65 536 alignments of 150 bases take 13.5 / 14.7 / 8.1 / 9.6 / 9.1 / 8.6 / 9.3 ms at
+ * 2^24 .. 2^30, runs of one cut differing by up to 15 %; 2^28 (~25 k alignments a chunk) is on the plateau and two steps from the
+ * cliff at 2^25.  BSW_F4_CIGAR_WORK overrides it (tests, measurements). */
+#define F4_CIGAR_CHUNK_WORK (1ull << 28)
+#define F4_CIGAR_OUT_MAX (1ull << 30)                  /* CIGAR words and MD slots of a chunk: 1 GiB each at the most */
+static uint64_t cigar_chunk_work()
+{
+    static const uint64_t v = getenv("BSW_F4_CIGAR_WORK") && atof(getenv("BSW_F4_CIGAR_WORK")) >= 1.0 ? (uint64_t)atof(getenv("BSW_F4_CIGAR_WORK")) : F4_CIGAR_CHUNK_WORK;
+    return v;
+}
+
+/* bsw_cigar_ref_batch as a ticket of the context's pipeline: the same checks in the caller's thread, then chunks of about
+ * cigar_chunk_work() cells (within the batch call's bounds, and F4_CIGAR_OUT_MAX bytes of CIGAR / MD room) through the slots
+ * of every device, chunk k on device k mod n_devices against that device's copy of the reference. */
+extern "C" int bsw_cigar_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ctask *tasks, size_t n,
+                                      int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
+    if (!p || !ref || (!tasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1))
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_ref_submit: bad argument"));
+    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_ref_submit: the reference was uploaded through another context"));
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "bsw_cigar_ref_submit: context is dead (an earlier wait for the GPU timed out)"));
+    f4_submit f;
+    f.kind = 1;
+    int rc = cigar_validate(e, p, tasks, n, &f.pp, &f.dp);
+    if (rc) return ctx_fail(ctx, e, rc);
+    f.ref = ref; f.ctasks = tasks; f.n = n; f.max_cigar = max_cigar; f.cigars = cigars; f.max_md = max_md; f.md = md; f.cres = res;
+    std::vector<uint64_t> nz(n), ns(n);               /* one walk over the tasks: the band formula is the cost of this pass */
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) { cigar_task_cost(f.pp, tasks[i], nz[i], ns[i]); total += nz[i]; }
+    const uint64_t wcap = std::min<uint64_t>(f4_chunk_work(ctx, total, cigar_chunk_work()), 4ull << 30);
+    const uint64_t per_out = std::max<uint64_t>((uint64_t)max_cigar * sizeof(uint32_t), md ? (uint64_t)max_md : 0);
+    for (size_t a = 0; a < n;) {
+        size_t b = a;
+        uint64_t zb = 0, sb = 0;
+        while (b < n && b - a < (1u << 20)) {
+            /* (a chunk is closed once it HOLDS its share of the work, so no sliver is left over; the 4 GiB of backtrack bytes stay a hard bound) */
+            if (b > a && (zb >= wcap || zb + nz[b] > (4ull << 30) || sb + ns[b] > (1ull << 31) || (uint64_t)(b - a + 1) * per_out > F4_CIGAR_OUT_MAX)) break;
+            zb += nz[b];
+            sb += ns[b];
+            ++b;
+        }
+        f.spans.push_back(chunk_span{a, b - a});
+        a = b;
+    }
+    return pipeline_submit_f4(ctx, std::move(f), ticket, "bsw_cigar_ref_submit");
 }

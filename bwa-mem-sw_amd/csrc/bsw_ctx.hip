@@ -182,6 +182,7 @@ static void ctx_release(bsw_ctx *ctx)
             for (auto ev : d.events) (void)hipEventDestroy(ev);
             for (auto ev : d.h2d_done) (void)hipEventDestroy(ev);
             for (auto &sl : d.slots) sl.release();
+            for (auto &fb : d.f4) fb.release();
         }
     }
     if (!ctx->devs.empty()) (void)hipSetDevice(ctx->device0());
@@ -313,6 +314,7 @@ extern "C" int bsw_create_sized(const bsw_config *cfg, size_t cfg_size, bsw_ctx 
         if (hipSetDevice(d.device) != hipSuccess) { ctx_release(ctx); return BSW_E_HIP; }
         locate_device(d, c.pin_threads);
         d.slots.resize((size_t)c.streams);
+        d.f4.resize((size_t)c.streams);
         for (int s = 0; s < c.streams; ++s) {
             hipStream_t st = nullptr;
             hipEvent_t ev = nullptr;

@@ -7,7 +7,8 @@
  *   bsw_scalar.hip  batched plain ksw_extend2 and the drop-in scalar entry points' shared queue
  *   bsw_wire.hip    the reference's 256 KiB / 16 KiB wire format end to end (F1)
  *   bsw_f4.hip      ksw_global2 / ksw_align2 hosts (F4)
- *   bsw_cigar.hip   bwa_gen_cigar2 (+ mem_reg2aln's retries) against the resident reference
+ *   bsw_cigar.hip   bwa_gen_cigar2 (+ mem_reg2aln's retries) against the resident reference, batch and ticketed submit
+ *   bsw_matesw.hip  mem_matesw's ksw_align2 against the resident reference, batch and ticketed submit
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
 #ifndef BSW_INTERNAL_H
@@ -232,6 +233,32 @@ struct fork_t {
     bool ok = false;
 };
 
+/* Device scratch of the CIGAR and mate-rescue hosts beside a stage_t.  The context owns one set (its members g_* / a_* / c_*,
+ * shared with bsw_global_batch / bsw_align_batch); every pipeline slot owns one of these, reserved on the slot's device by the
+ * first CIGAR or rescue chunk it runs, released by bsw_destroy. */
+struct f4_bufs {
+    dbuf<bsw_gdtask> g_tasks;
+    dbuf<uint8_t> g_z;
+    dbuf<uint32_t> g_cig, g_order;
+    dbuf<bsw_gresult> g_res;
+    dbuf<bsw_adtask> a_tasks;
+    dbuf<unsigned long long> a_bl;
+    dbuf<bsw_kswr> a_res;
+    dbuf<bsw_cdtask> c_tasks;
+    dbuf<bsw_cresult> c_res;
+    dbuf<char> c_md;
+    hbuf<uint8_t> h_back;             /* pinned: what a slot's chunk reads back (scores per try, then results, CIGARs, MD) */
+    hbuf<uint8_t> h_in;               /* pinned: the records a slot's chunk builds on the host (alignment / CIGAR tasks, order lists) —
+                                         the slot's DMAs never read a vector of a function that may return first (watchdog) */
+    void release()
+    {
+        g_tasks.release(); g_z.release(); g_cig.release(); g_order.release(); g_res.release();
+        a_tasks.release(); a_bl.release(); a_res.release();
+        c_tasks.release(); c_res.release(); c_md.release();
+        h_back.release(); h_in.release();
+    }
+};
+
 struct dev_state {
     int device = 0;
     /* where the card sits: PCI address, NUMA node, and the CPUs next to it that this process may use (empty: not known, or
@@ -245,6 +272,7 @@ struct dev_state {
     std::vector<hipEvent_t> events;   /* one per stream, for the watchdog */
     std::vector<hipEvent_t> h2d_done; /* one per stream: the chunk's input DMAs have finished */
     std::vector<stage_t> slots;
+    std::vector<f4_bufs> f4;          /* one per slot (CIGAR / mate-rescue chunks of the pipeline) */
 };
 
 /* Input DMAs of one device run in chunk order, one chunk at a time: chunk k+1's transfer then overlaps chunk k's
@@ -307,6 +335,90 @@ inline int ctx_fail(bsw_ctx *ctx, const errs &e, int rc)
     ctx->err = e;
     return rc;
 }
+
+/* Where one chunk of bsw_cigar_ref_* / bsw_matesw_ref_* runs: the device (index into bsw_config.devices[], and so into
+ * bsw_ref::d_pac), the staging, the stream, the watchdog event and the scratch buffers.  The synchronous calls pass the context's
+ * own lane (ctx_lane); every pipeline slot has one over its own stage_t, stream and f4_bufs. */
+struct f4_lane {
+    size_t dev = 0;
+    stage_t *st = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t ev = nullptr;
+    dbuf<bsw_gdtask> *g_tasks = nullptr;
+    dbuf<uint8_t> *g_z = nullptr;
+    dbuf<uint32_t> *g_cig = nullptr, *g_order = nullptr;
+    dbuf<bsw_gresult> *g_res = nullptr;
+    dbuf<bsw_adtask> *a_tasks = nullptr;
+    dbuf<unsigned long long> *a_bl = nullptr;
+    dbuf<bsw_kswr> *a_res = nullptr;
+    dbuf<bsw_cdtask> *c_tasks = nullptr;
+    dbuf<bsw_cresult> *c_res = nullptr;
+    dbuf<char> *c_md = nullptr;
+    hbuf<uint8_t> *h_back = nullptr;  /* non-NULL (a slot): read-backs are asynchronous copies on `s` into this pinned buffer, in front
+                                         of the sync_stream that carries the watchdog; NULL: the blocking copies of the synchronous calls */
+    hbuf<uint8_t> *h_in = nullptr;    /* with h_back: the host-built records are DMA'd from this pinned buffer */
+    /* where the DMA of a host-built array reads: the array itself (synchronous calls), or its copy at `off` of h_in (a slot) */
+    const void *dma_src(const void *p, size_t bytes, size_t off) const
+    {
+        if (!h_in) return p;
+        if (bytes) memcpy(h_in->p + off, p, bytes);
+        return h_in->p + off;
+    }
+    const std::atomic<int> *abort = nullptr;      /* a slot: the chunk's submit has failed elsewhere — give up between tries */
+    uint64_t h2d = 0, d2h = 0;        /* bytes the chunk moved (bsw_host_stats) */
+    void bind(f4_bufs &b)
+    {
+        g_tasks = &b.g_tasks; g_z = &b.g_z; g_cig = &b.g_cig; g_order = &b.g_order; g_res = &b.g_res;
+        a_tasks = &b.a_tasks; a_bl = &b.a_bl; a_res = &b.a_res;
+        c_tasks = &b.c_tasks; c_res = &b.c_res; c_md = &b.c_md;
+    }
+};
+inline f4_lane ctx_lane(bsw_ctx *ctx)
+{
+    f4_lane L;
+    L.dev = 0; L.st = &ctx->small; L.s = ctx->stream0(); L.ev = ctx->devs[0].events[0];
+    L.g_tasks = &ctx->g_tasks; L.g_z = &ctx->g_z; L.g_cig = &ctx->g_cig; L.g_order = &ctx->g_order; L.g_res = &ctx->g_res;
+    L.a_tasks = &ctx->a_tasks; L.a_bl = &ctx->a_bl; L.a_res = &ctx->a_res;
+    L.c_tasks = &ctx->c_tasks; L.c_res = &ctx->c_res; L.c_md = &ctx->c_md;
+    return L;
+}
+
+/* one chunk of a submit: tasks [base, base + cnt) of the caller's array */
+struct chunk_span {
+    size_t base, cnt;
+};
+
+/* A ticketed CIGAR (kind 1) or mate-rescue (kind 2) submit as its entry point hands it to the pipeline: validated, the band
+ * taken out of the parameters, cut into chunks.  The caller's arrays stay the caller's until the ticket is collected. */
+struct f4_submit {
+    int kind = 0;
+    bsw_params pp{};
+    bsw_dparams dp{};
+    const bsw_ref *ref = nullptr;
+    const bsw_ctask *ctasks = nullptr;
+    const bsw_mtask *mtasks = nullptr;
+    size_t n = 0;
+    int max_cigar = 0, max_md = 0;
+    uint32_t *cigars = nullptr;
+    char *md = nullptr;
+    bsw_cresult *cres = nullptr;
+    bsw_mresult *mres = nullptr;
+    std::vector<chunk_span> spans;    /* chunk k -> device k mod n_devices */
+};
+/* the work one chunk of a submit should hold: the kind's target (a launch of that much fills the machine), less for a submit
+ * that would otherwise leave slots of the context without a chunk, never below an eighth of the target */
+inline uint64_t f4_chunk_work(const bsw_ctx *ctx, uint64_t total, uint64_t target)
+{
+    const uint64_t lanes = (uint64_t)ctx->devs.size() * (uint64_t)std::max(ctx->cfg.streams, 1);
+    return std::min(target, std::max(target / 8, (total + lanes - 1) / lanes));
+}
+/* ---- bsw_batch.hip: queues the chunks of `f` on the devices' queues in submit order; BSW_E_BUSY changes nothing ---- */
+BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket, const char *what);
+/* ---- bsw_cigar.hip / bsw_matesw.hip: one chunk on a lane ---- */
+BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
+                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res);
+BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                           bsw_mresult *res);
 
 struct chunk_info;
 struct bsw_dev_batch {

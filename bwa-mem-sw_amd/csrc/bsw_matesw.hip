@@ -11,6 +11,9 @@
  *      BSW_AD_QRC and the kernel builds its query profile from the reverse complement of the stored mate, in the main pass
  *      and in the KSW_XSTART pass, so one launch per class serves both orientations;
  *   3. mem_matesw's mapping of kswr_t to the region and its keep decision run here on the copied-back results.
+ *
+ * A chunk runs on a LANE (f4_lane, bsw_internal.h): the context's own for bsw_matesw_ref_batch, a pipeline slot's for the chunks
+ * of bsw_matesw_ref_submit_t (bsw_batch.hip: process_f4).
  */
 #include "bsw_internal.h"
 
@@ -24,11 +27,11 @@ static bool mtask_runs(const bsw_mtask &t, int64_t l_pac)
     return t.l_ms > 0 && t.rb < t.re && !(t.rb < l_pac && t.re > l_pac) && t.rb >= 0 && t.re <= 2 * l_pac;
 }
 
-static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                        bsw_mresult *res)
+BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                           bsw_mresult *res)
 {
-    stage_t &st = ctx->small;
-    hipStream_t s = ctx->stream0();
+    stage_t &st = *L.st;
+    hipStream_t s = L.s;
     hipError_t he;
     const int64_t l_pac = ref->l_pac;
     if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
@@ -86,28 +89,35 @@ static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
     if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
         (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
         (he = st.d_desc.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->a_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->a_res.reserve(n + 1)) != hipSuccess || (he = ctx->a_bl.reserve((size_t)bacc + 64)) != hipSuccess)
+        (he = L.a_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
+        (he = L.a_res->reserve(n + 1)) != hipSuccess || (he = L.a_bl->reserve((size_t)bacc + 64)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
-    std::vector<bsw_kswr> aln(n);
-    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
+    const size_t in_order = (n + 1) * sizeof(bsw_adtask);
+    if (L.h_back && ((he = L.h_back->reserve(n * sizeof(bsw_kswr) + 16)) != hipSuccess || (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
+        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    std::vector<bsw_kswr> aln(L.h_back ? 0 : n);
+    const bsw_kswr *alnp = L.h_back ? (const bsw_kswr *)L.h_back->p : aln.data();      /* a slot reads back into pinned memory */
+    drain_on_failure drain(ctx, s, L.ev);
     if (!order.empty()) {
         if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(ctx->a_tasks.p, at.data(), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, ref->d_pac[0], l_pac, st.d_desc.p,
+        HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, L.dma_src(at.data(), n * sizeof(bsw_adtask), 0), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(order.data(), order.size() * sizeof(uint32_t), in_order), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_adtask)) + order.size() * sizeof(uint32_t);
+        HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, ref->d_pac[L.dev], l_pac, st.d_desc.p,
                                    st.d_seq.p, nullptr, s));
         for (int c = 0; c < ncls; ++c) {
             const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
             if (!k) continue;
-            HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, ctx->a_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->a_bl.p, ctx->a_res.p, s));
+            HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.a_bl->p, L.a_res->p, s));
         }
-        int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
+        if (L.h_back) HIPCHK(e, hipMemcpyAsync(L.h_back->p, L.a_res->p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost, s));
+        int rc = sync_stream(ctx, e, s, L.ev);
         if (rc) return rc;
-        HIPCHK(e, hipMemcpy(aln.data(), ctx->a_res.p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
+        if (!L.h_back) HIPCHK(e, hipMemcpy(aln.data(), L.a_res->p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
+        L.d2h += n * sizeof(bsw_kswr);
     }
     /* mem_matesw: if (aln.score >= opt->min_seed_len && aln.qb >= 0) { b.qb = is_rev? l_ms - (aln.qe + 1) : aln.qb; ... } */
     for (size_t i = 0; i < n; ++i) {
@@ -119,7 +129,7 @@ static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
             m.status = 1;
             continue;
         }
-        const bsw_kswr &a = aln[i];
+        const bsw_kswr &a = alnp[i];
         m.aln = a;
         if (!(a.score >= t.min_score && a.qb >= 0)) {
             m.status = 2;
@@ -139,6 +149,29 @@ static int matesw_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
     return BSW_OK;
 }
 
+/* what both entry points check before anything runs or is queued: the parameters (band and variant are the call's own), then
+ * the tasks in order — the first malformed one rejects the call */
+static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks, size_t n, const char *what, bsw_dparams *dp)
+{
+    bsw_params pp = *p;
+    pp.w = 0; pp.variant = BSW_VARIANT_H;
+    int rc = check_params(e, &pp, dp);
+    if (rc) return rc;
+    int mxs = 0;
+    for (int i = 0; i < 25; ++i) mxs = std::max(mxs, (int)p->mat[i]);
+    if (mxs <= 0) return fail(e, BSW_E_INVAL, "%s: the scoring matrix has no positive score", what);
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_mtask &t = tasks[i];
+        if (t.l_ms < 0) return fail(e, BSW_E_INVAL, "mate task %zu: negative length", i);
+        if (t.l_ms && !t.mate) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
+        if (t.is_rev != 0 && t.is_rev != 1) return fail(e, BSW_E_INVAL, "mate task %zu: is_rev is neither 0 nor 1", i);
+        if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "mate task %zu: unknown xtra flag", i);
+        if (t.l_ms > BSW_ALIGN_MAX_QLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
+            return fail(e, BSW_E_LIMIT, "mate task %zu: beyond BSW_ALIGN_MAX_QLEN / BSW_MAX_TLEN", i);
+    }
+    return BSW_OK;
+}
+
 extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
                                     bsw_mresult *res)
 {
@@ -149,24 +182,11 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
         return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: the reference was uploaded through another context");
     int rc = busy_check(ctx, "bsw_matesw_ref_batch");
     if (rc) return rc;
-    bsw_params pp = *p;
-    pp.w = 0; pp.variant = BSW_VARIANT_H;
     bsw_dparams dp;
-    rc = check_params(e, &pp, &dp);
+    rc = matesw_validate(e, p, tasks, n, "bsw_matesw_ref_batch", &dp);
     if (rc) return rc;
-    int mxs = 0;
-    for (int i = 0; i < 25; ++i) mxs = std::max(mxs, (int)p->mat[i]);
-    if (mxs <= 0) return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: the scoring matrix has no positive score");
-    for (size_t i = 0; i < n; ++i) {
-        const bsw_mtask &t = tasks[i];
-        if (t.l_ms < 0) return fail(e, BSW_E_INVAL, "mate task %zu: negative length", i);
-        if (t.l_ms && !t.mate) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
-        if (t.is_rev != 0 && t.is_rev != 1) return fail(e, BSW_E_INVAL, "mate task %zu: is_rev is neither 0 nor 1", i);
-        if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "mate task %zu: unknown xtra flag", i);
-        if (t.l_ms > BSW_ALIGN_MAX_QLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
-            return fail(e, BSW_E_LIMIT, "mate task %zu: beyond BSW_ALIGN_MAX_QLEN / BSW_MAX_TLEN", i);
-    }
     HIPCHK(e, hipSetDevice(ctx->device0()));
+    f4_lane L = ctx_lane(ctx);
     for (size_t a = 0; a < n;) {                      /* sub-batches: bsw_align_batch's bounds on the sequence arena and b[] scratch */
         size_t b = a;
         uint64_t sb = 0, bb = 0;
@@ -178,9 +198,60 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
             bb += (t.xtra & KSW_XSUBO) ? tl : 0;
             ++b;
         }
-        rc = matesw_chunk(ctx, e, dp, ref, tasks + a, b - a, res + a);
+        rc = matesw_chunk(ctx, e, L, dp, ref, tasks + a, b - a, res + a);
         if (rc) return rc;
         a = b;
     }
     return BSW_OK;
+}
+
+/* The work target of a rescue chunk, in cells (l_ms x (re - rb) summed over its tasks), from the sweep of tools/f4_stream_rate.py
+ * ("sweep_matesw" of profiles/f4_stream_rate.json): 262 144 windows of 150 x 550 take 176 / 77 / 66 / 82 / 50.5 /
+ * 47.6 / 51.5 ms at 2^27 .. 2^33; 2^31 is the smallest target of the plateau (~26 k windows a chunk), which leaves the most chunks
+ * for slots and devices.  BSW_F4_MATESW_WORK overrides it (tests, measurements). */
+#define F4_MATESW_CHUNK_WORK (1ull << 31)
+static uint64_t matesw_chunk_work()
+{
+    static const uint64_t v = getenv("BSW_F4_MATESW_WORK") && atof(getenv("BSW_F4_MATESW_WORK")) >= 1.0 ? (uint64_t)atof(getenv("BSW_F4_MATESW_WORK")) : F4_MATESW_CHUNK_WORK;
+    return v;
+}
+
+/* bsw_matesw_ref_batch as a ticket of the context's pipeline: the same checks in the caller's thread, then chunks of about
+ * matesw_chunk_work() cells (and within the batch call's bounds) through the slots of every device, chunk k on device
+ * k mod n_devices against that device's copy of the reference.  Collected by bsw_wait_ticket / bsw_wait. */
+extern "C" int bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                                       bsw_mresult *res, bsw_ticket *ticket)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
+    if (!p || !ref || (!tasks && n) || (!res && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_ref_submit: NULL argument"));
+    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_ref_submit: the reference was uploaded through another context"));
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "bsw_matesw_ref_submit: context is dead (an earlier wait for the GPU timed out)"));
+    f4_submit f;
+    f.kind = 2; f.pp = *p; f.pp.w = 0; f.pp.variant = BSW_VARIANT_H;
+    int rc = matesw_validate(e, p, tasks, n, "bsw_matesw_ref_submit", &f.dp);
+    if (rc) return ctx_fail(ctx, e, rc);
+    f.ref = ref; f.mtasks = tasks; f.n = n; f.mres = res;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (tasks[i].re > tasks[i].rb) total += (uint64_t)tasks[i].l_ms * (uint64_t)(tasks[i].re - tasks[i].rb);
+    const uint64_t wcap = f4_chunk_work(ctx, total, matesw_chunk_work());
+    for (size_t a = 0; a < n;) {                      /* the batch call's bounds, and the work of a chunk */
+        size_t b = a;
+        uint64_t sb = 0, bb = 0, wb = 0;
+        while (b < n && b - a < (1u << 20)) {
+            const bsw_mtask &t = tasks[b];
+            const uint64_t tl = t.re > t.rb ? (uint64_t)(t.re - t.rb) : 0;
+            if (b > a && (sb + (uint64_t)t.l_ms + tl > (1ull << 31) || bb + tl > (1ull << 28) || wb >= wcap)) break;      /* (a chunk is closed once it HOLDS its share: no sliver is left over) */
+            sb += (uint64_t)t.l_ms + tl;
+            bb += (t.xtra & KSW_XSUBO) ? tl : 0;
+            wb += (uint64_t)t.l_ms * tl;
+            ++b;
+        }
+        f.spans.push_back(chunk_span{a, b - a});
+        a = b;
+    }
+    return pipeline_submit_f4(ctx, std::move(f), ticket, "bsw_matesw_ref_submit");
 }

@@ -145,6 +145,8 @@ def lib():
             "bsw_global_batch": (C.c_int, [vp, vp, vp, sz, C.c_int, vp, vp]),
             "bsw_align_batch": (C.c_int, [vp, vp, vp, sz, vp]),
             "bsw_cigar_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp]),
+            "bsw_cigar_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_uint64)]),
+            "bsw_matesw_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -180,6 +182,7 @@ def lib():
 
 
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
+           "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
            "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
@@ -518,6 +521,43 @@ class BswContext:
         self._chk(lib().bsw_matesw_ref_batch(self.handle, params.ctypes.data, ref, mtasks.ctypes.data, len(mtasks), res.ctypes.data),
                   "bsw_matesw_ref_batch")
         return res
+
+    def _keep_alive(self, ticket, *arrays):
+        if self._keep is None:
+            self._keep = {}
+        self._keep[ticket] = arrays                         # the arrays must outlive the submit
+        self.last_ticket = ticket
+
+    def submit_cigar_ref(self, params, ref, ctasks, max_cigar=64, max_md=256, want_cigar=True, want_md=True):
+        """cigar_ref_batch as a ticket of the streaming pipeline (bsw_cigar_ref_submit_t): runs on every device of the context,
+        beside extension submits.  Returns (ticket, CRESULT array, cigars uint32[n, max_cigar] or None, MD slots
+        uint8[n, max_md] or None); the arrays are filled once test(ticket) is true / wait_ticket(ticket) has returned
+        (md_strings() decodes the MD slots then).  The reads that `ctasks` points to must stay alive until then."""
+        n = len(ctasks)
+        res = np.zeros(n, dtype=CRESULT)
+        cig = np.zeros((n, max_cigar), dtype=np.uint32) if want_cigar else None
+        md = np.zeros((n, max_md), dtype=np.uint8) if want_md else None
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_cigar_ref_submit_t(self.handle, params.ctypes.data, ref, ctasks.ctypes.data, n, max_cigar,
+                                               cig.ctypes.data if want_cigar else None, max_md,
+                                               md.ctypes.data if want_md else None, res.ctypes.data, C.byref(t)), "bsw_cigar_ref_submit")
+        self._keep_alive(t.value, params, ctasks, res, cig, md)
+        return t.value, res, cig, md
+
+    @staticmethod
+    def md_strings(res, md):
+        """the MD strings of a collected submit_cigar_ref, as cigar_ref_batch returns them"""
+        return [bytes(md[i, :max(int(res["md_len"][i]), 0)]).decode("ascii") for i in range(len(res))]
+
+    def submit_matesw_ref(self, params, ref, mtasks):
+        """matesw_ref_batch as a ticket of the streaming pipeline (bsw_matesw_ref_submit_t).  Returns (ticket, MRESULT array);
+        the array is filled once the ticket is complete.  The mates that `mtasks` points to must stay alive until then."""
+        res = np.zeros(len(mtasks), dtype=MRESULT)
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_matesw_ref_submit_t(self.handle, params.ctypes.data, ref, mtasks.ctypes.data, len(mtasks), res.ctypes.data,
+                                                C.byref(t)), "bsw_matesw_ref_submit")
+        self._keep_alive(t.value, params, mtasks, res)
+        return t.value, res
 
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""

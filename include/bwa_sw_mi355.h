@@ -31,6 +31,8 @@
  *                              (bwa host software, not the RTL)
  *   bsw_matesw_ref_batch       mem_matesw's ksw_align2 against the device-resident
  *                              reference (bwa host software, not the RTL)
+ *   bsw_cigar_ref_submit_t /   the two calls above as tickets of the streaming pipeline:
+ *   bsw_matesw_ref_submit_t    every device of the context, beside extension submits
  *
  * Base codes: 0..3 = A,C,G,T; 4 = N; one base per byte, exactly as bwa passes
  * them to ksw_extend.  Left-extension query/target must already be reversed by
@@ -237,7 +239,8 @@ int      bsw_host_unregister(void *p);
  * submit order, so the tail of one overlaps the head of the next.  One more than that answers BSW_E_BUSY.
  * bsw_wait waits for ALL of them and returns the first failure in submit order.
  *
- * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called
+ * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, bsw_wait_ticket,
+ * bsw_test, bsw_wait and bsw_inflight may be called
  * on ONE context from several threads at once, the first submit included; every other call that takes the context
  * (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free, bsw_host_stats) needs it to itself.
  *   - A ticket belongs to whoever collects it first.  bsw_wait collects every submit in flight when it is called, other threads'
@@ -312,7 +315,8 @@ int ksw_global(int qlen, const uint8_t *query, int tlen, const uint8_t *target, 
  * reads plus reference intervals go in, score, CIGAR, NM and MD come back.  The target [rb, re) is fetched on the GPU from
  * the reference of bsw_ref_upload (reverse strand: the read and the target are both reversed, as bwa does, so indels sit
  * leftmost and the CIGAR / MD are in that reversed frame), the band follows bwa's formula, ksw_global2 runs on the GPU and
- * NM / MD are computed there from the CIGAR.  Only the reads cross PCIe.  The whole batch runs on the context's first device.
+ * NM / MD are computed there from the CIGAR.  Only the reads cross PCIe.  The whole batch runs on the context's first device
+ * (bsw_cigar_ref_submit_t below: the same work as a ticket, over every device of the context).
  * Retry (mem_reg2aln):  w2 = w; last = -(1 << 30);
  *     do { w2 = min(w2, w_cap); bwa_gen_cigar2(w_ = w2); if (score == last || w2 == w_cap) break; last = score; w2 <<= 1; }
  *     while (++i < max_tries && score < min_score);
@@ -346,6 +350,24 @@ typedef struct bsw_cresult {
  * l_query > BSW_GLOBAL_MAX_QLEN, re - rb > BSW_MAX_TLEN, w or w_cap > BSW_MAX_TLEN -> BSW_E_LIMIT. */
 int      bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_ctask *tasks, size_t n,
                              int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res);
+/* The same as a TICKET of the context's pipeline (bsw_submit_t above: one ticket space, BSW_MAX_INFLIGHT submits of any mix,
+ * collected by bsw_wait_ticket / bsw_wait, polled by bsw_test, counted by bsw_inflight; ticket may be NULL; n == 0 completes at
+ * once).  The argument and task checks of bsw_cigar_ref_batch run in the caller's thread before anything is queued, with the
+ * same codes and texts, and no ticket is made when they fail; BSW_E_BUSY changes nothing.  The submit is cut into chunks by
+ * work, chunk k runs on device k mod n_devices of the context against that device's copy of the reference, on the slot threads
+ * and streams the extension submits use, in submit order with them: it is accepted while extension submits are in flight and
+ * the other way round.  res, cigars and md receive, byte for byte, what bsw_cigar_ref_batch writes for the same tasks, in task
+ * order.  tasks[], the reads they point to, res, cigars and md stay valid until the ticket is collected.  A chunk that fails
+ * makes the others of its ticket give up; the wait returns the failure, nothing of the ticket is still queued then, and other
+ * tickets are left alone.  May be called on one context from several threads (THREADS above).
+ * A watchdog expiry is different: the wait answers BSW_E_HIP, the context is dead, and what the hung device still holds in its
+ * queues may read the reads and `ref` whenever it wakes.  Call bsw_destroy (it leaves the runtime alone on a dead context), do
+ * NOT call bsw_ref_free on that reference and do not free or unregister the reads of the failed tickets: that memory is
+ * abandoned with the device, as the context's own buffers are; a new context needs a new bsw_ref_upload.
+ * The work a chunk holds is a constant of the library; the environment variables BSW_F4_CIGAR_WORK /
+ * BSW_F4_MATESW_WORK replace it for tests and measurements only. */
+int      bsw_cigar_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_ctask *tasks, size_t n,
+                                int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket);
 /* mem_reg2aln's infer_bw: the band a global alignment of l1 x l2 bases needs to reach `score` (a = match, q / r = gap
  * open / extend of one kind; bwa takes the larger of the deletion and the insertion answers) */
 int      bsw_infer_bw(int l1, int l2, int score, int a, int q, int r);
@@ -386,7 +408,7 @@ kswr_t ksw_align(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, con
 /* ---- mate rescue against a DEVICE-RESIDENT reference (bwa's mem_matesw, bwamem_pair.c): one ksw_align2 per window,
  * the window [rb, re) fetched on the GPU from the reference of bsw_ref_upload (bns_get_seq semantics, both strands), the
  * mate complemented and reversed on the GPU when is_rev.  Only the mates cross PCIe.  The whole batch runs on the context's
- * first device.  mem_matesw's bookkeeping (which orientations to try, its order dependency) stays with the caller:
+ * first device (bsw_matesw_ref_submit_t below: the same work as a ticket, over every device of the context).  mem_matesw's bookkeeping (which orientations to try, its order dependency) stays with the caller:
  * bsw_infer_dir and bsw_matesw_windows below, INTEGRATION.md "Mate rescue".  Kept (status 0) exactly when bwa keeps the
  * region: aln.score >= min_score && aln.qb >= 0. ---- */
 typedef struct bsw_mtask {
@@ -414,6 +436,11 @@ typedef struct bsw_mresult {
  * l_ms > BSW_ALIGN_MAX_QLEN or re - rb > BSW_MAX_TLEN -> BSW_E_LIMIT. */
 int      bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_mtask *tasks, size_t n,
                               bsw_mresult *res);
+/* The same as a TICKET of the context's pipeline: the contract of bsw_cigar_ref_submit_t above, with the checks and the results
+ * of bsw_matesw_ref_batch.  tasks[], the mates they point to and res stay valid until the ticket is collected.  mem_matesw's
+ * replay of the anchor order (INTEGRATION.md "Mate rescue") runs on res after the ticket is collected. */
+int      bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                                 bsw_mresult *res, bsw_ticket *ticket);
 /* mem_infer_dir: the orientation (0..3) of a pair whose leftmost positions are b1 (anchor) and b2 (mate), and in *dist the
  * distance between them on the anchor's strand */
 int      bsw_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist);

@@ -232,7 +232,10 @@ struct range_acc {
 template <class Src>
 static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, size_t n, bool dev_targets,
                            bsw_dtask *dt, bsw_rawoff *ro, chunk_info &ci, bool rev_left, bool packed = false, size_t idx0 = 0 /* index of the chunk's first seed in the caller's array: error texts name the caller's index */,
-                           int threads = 1 /* ranges walked side by side (helper threads started here; their CPU time -> *helper_ns) */, std::atomic<uint64_t> *helper_ns = nullptr)
+                           int threads = 1 /* ranges walked side by side (helper threads started here; their CPU time -> *helper_ns) */, std::atomic<uint64_t> *helper_ns = nullptr,
+                           bool by_pos = false /* bsw_submit_reads_t: the query "pointers" are no addresses — their low 32 bits are base positions in the
+                                                  resident read store (rawoff takes them as it takes pointers' low bits): nothing is dereferenced, no span is
+                                                  kept, no registration is tested */)
 {
     ci.packed = packed;
     const int mx = mat_max(p->mat);
@@ -290,7 +293,7 @@ static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, si
             return v;
         };
         auto span = [&](const uint8_t *sq, int len) {
-            if (len > 0) { if (sq < lo) lo = sq; if (sq + len > hi) hi = sq + len; }
+            if (len > 0 && !by_pos) { if (sq < lo) lo = sq; if (sq + len > hi) hi = sq + len; }
         };
         auto bad = [&](int code) { A.rc = code; };
     for (size_t i = i0; i < i1; ++i) {
@@ -341,14 +344,14 @@ static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, si
         if (t.lqlen) {
             d.lq_off = (uint32_t)acc; acc += nwords(t.lqlen);
             d.lt_off = (uint32_t)acc; acc += nwords(t.ltlen);
-            r.lq = (uint32_t)(uintptr_t)t.lquery; accb += (uint64_t)t.lqlen;
+            r.lq = (uint32_t)(uintptr_t)t.lquery; accb += by_pos ? 0u : (uint64_t)t.lqlen;
             span(rev_left ? t.lquery - (t.lqlen - 1) : t.lquery, t.lqlen);    /* rev_left: lquery points at the LAST base, read backwards */
             if (!dev_targets) { r.lt = (uint32_t)(uintptr_t)t.ltarget; accb += (uint64_t)t.ltlen; span(t.ltarget, t.ltlen); }
         }
         if (t.rqlen) {
             d.rq_off = (uint32_t)acc; acc += nwords(t.rqlen);
             d.rt_off = (uint32_t)acc; acc += nwords(t.rtlen);
-            r.rq = (uint32_t)(uintptr_t)t.rquery; accb += (uint64_t)t.rqlen;
+            r.rq = (uint32_t)(uintptr_t)t.rquery; accb += by_pos ? 0u : (uint64_t)t.rqlen;
             span(t.rquery, t.rqlen);
             if (!dev_targets) { r.rt = (uint32_t)(uintptr_t)t.rtarget; accb += (uint64_t)t.rtlen; span(t.rtarget, t.rtlen); }
         }
@@ -455,7 +458,7 @@ static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, si
          * the general kernel would get */
         const uint32_t n8 = group ? n_lane : n_lane - n16;
         double nfrac = -1.0;
-        if (nsplit_candidate(kern, bp, packed_ok, n8, ci.streaming) && nsplit_env() != 1) {
+        if (!by_pos && nsplit_candidate(kern, bp, packed_ok, n8, ci.streaming) && nsplit_env() != 1) {      /* (resident reads: the bases are not on the host — unknown) */
             const auto has_n = [&](const uint8_t *q, int len, bool backwards) -> bool {
                 if (!q || len <= 0) return false;
                 if (packed) {
@@ -499,7 +502,7 @@ static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, si
     /* DMA the caller's arena as it is when it is registered memory and not much larger than what it holds */
     const size_t spanb = hi ? (size_t)(hi - lo) : 0;
     ci.direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * ci.sum_len + (1u << 20) && is_registered(lo, spanb);
-    ci.rev_left = rev_left && ci.direct;            /* the gather path mirrors the left queries while copying */
+    ci.rev_left = rev_left && (ci.direct || by_pos);    /* the gather path mirrors the left queries while copying */
     ci.raw_bias = ci.direct ? (uint32_t)(uintptr_t)lo : 0u;
     {
         static const bool dbg = getenv("BSW_DEBUG_TIMING") != nullptr;
@@ -859,7 +862,7 @@ static int stage_device(errs &e, stage_t &st, hipStream_t s, const chunk_info &c
                         const bsw_ref *ref, uint64_t *h2d_bytes, const gate_turn *turn = nullptr, size_t dev_index = 0)
 {
     const size_t n_desc = ref ? n : 0;              /* st.h_desc: one bsw_refx per seed */
-    const size_t rawb = ci.packed ? 0 : (ci.direct ? (size_t)(ci.hi - ci.lo) : ci.sum_len);
+    const size_t rawb = ci.packed || ci.store ? 0 : (ci.direct ? (size_t)(ci.hi - ci.lo) : ci.sum_len);
     hipError_t he;
     if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve(ci.words + 4)) != hipSuccess ||
         (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
@@ -902,7 +905,8 @@ static int stage_device(errs &e, stage_t &st, hipStream_t s, const chunk_info &c
     (void)dev_targets;
     if (ci.rb_on) HIPCHK(e, bsw::launch_rebase(st.d_tasks.p, st.d_roff.p, (uint32_t)n, ci.rb, s));
     if (!ci.packed)
-        HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, ci.raw_bias, (uint32_t)n, ci.rev_left ? 1 : 0,
+        HIPCHK(e, bsw::launch_pack(ci.store ? (const uint8_t *)ci.store : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, ci.raw_bias, (uint32_t)n,
+                                   (ci.rev_left ? BSW_PACK_REV_LEFT : 0) | (ci.store ? BSW_PACK_STORE : 0),
                                    ref ? ref->d_pac[dev_index] : nullptr, ref ? ref->l_pac : 0, ref ? st.d_desc.p : nullptr, st.d_seq.p, st.d_nflag.p, s));
     HIPCHK(e, bsw::launch_bin(ci.bp, st.d_seq.p, ci.packed ? nullptr : st.d_nflag.p, st.d_tasks.p, (uint32_t)n, st.d_bins.p, st.d_keys.p, st.d_order.p, s));
     if (h2d_bytes) *h2d_bytes = (ci.packed ? ci.words * 8 : rawb + n * sizeof(bsw_rawoff)) + n * sizeof(bsw_dtask) + n_desc * sizeof(bsw_refx);
@@ -1177,6 +1181,17 @@ BSW_LOCAL int ref_to_task(errs &e, const bsw_params *p, int64_t l_pac, const bsw
     }
     t.h0 = sd.len * p->mat[0]; t.init_score = r.init_score; t.qbeg = sd.qbeg; t.tag = r.tag;
     return BSW_OK;
+}
+
+/* a seed of a resident read as the pointer form's record.  Its query is NOT an address: 2^32 + the position of the read's first
+ * base in the store — ref_to_task's pointer arithmetic then yields the positions of the two flanks, and prepare_chunk_t
+ * (by_pos) takes their low 32 bits as it takes those of real pointers.  Never dereferenced.  read < n_reads (checked at submit). */
+static inline bsw_ref_task rd_to_ref(const bsw_reads *rd, const bsw_rd_task &r)
+{
+    bsw_ref_task t;
+    t.query = (const uint8_t *)(uintptr_t)((1ull << 32) + rd->pos(r.read));
+    t.l_query = rd->rd[r.read].len; t.init_score = r.init_score; t.seed = r.seed; t.rmax0 = r.rmax0; t.rmax1 = r.rmax1; t.tag = r.tag; t._pad = 0;
+    return t;
 }
 
 /* where the device finds the two targets of every seed in the resident pac */
@@ -1532,6 +1547,10 @@ struct ticket_t {
     const bsw_task *tasks = nullptr;
     const bsw_ref *ref = nullptr;
     const bsw_ref_task *rtasks = nullptr;      /* non-NULL: seeds against the device-resident reference */
+    const bsw_rd_task *rdtasks = nullptr;      /* non-NULL: ... whose reads are resident too (bsw_submit_reads_t; rd below) */
+    const bsw_reads *rd = nullptr;
+    const bsw_reads *rd_held = nullptr;        /* the read block this ticket took (reads_acquire), given back when the ticket goes, i.e. is collected */
+    ~ticket_t() { reads_release(rd_held); }
     bsw_result *out = nullptr;
     bool packed = false;
     size_t n = 0;
@@ -1654,7 +1673,23 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
             if (pend.active && (rc = wait_event(ctx, e, dev.h2d_done[s]))) break;           /* pinned host staging is free again */
             t1 = dbg ? tnow() : 0;
             if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
-                (t->rtasks && (he = st.h_desc.reserve(n + 1)) != hipSuccess)) { rc = fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he)); break; }
+                ((t->rtasks || t->rdtasks) && (he = st.h_desc.reserve(n + 1)) != hipSuccess)) { rc = fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he)); break; }
+            if (t->rdtasks) {                       /* reference AND reads resident: the pass fills the records and two positions per seed, and that is all */
+                const bsw_rd_task *crd = t->rdtasks + base;
+                bsw_refx *rx = st.h_desc.p;
+                std::mutex emu;
+                rc = prepare_chunk_t(e, &p, ctx->cfg.kernel, [&](size_t i, bsw_task &tmp, int &erc) -> const bsw_task * {
+                    errs le;
+                    size_t so_l = 0;
+                    erc = ref_to_task(le, &p, t->ref->l_pac, rd_to_ref(t->rd, crd[i]), base + i, true, nullptr, so_l, tmp);
+                    if (erc) { std::lock_guard<std::mutex> lk(emu); e = le; }
+                    rx[i] = bsw_refx{crd[i].seed.rbeg - 1, crd[i].seed.rbeg + crd[i].seed.len};
+                    return erc ? nullptr : &tmp;
+                }, n, true, st.h_tasks.p, st.h_roff.p, ci, true, false, base, pass_threads, &pp.helper_cpu_ns, true);
+                if (rc) break;
+                ci.store = t->rd->dev(d);
+                break;                              /* nothing to gather */
+            }
             if (t->rtasks) {                        /* mem_chain2aln's task extraction fused into the pass; the targets stay on the device */
                 const bsw_ref_task *crt = t->rtasks + base;
                 bsw_refx *rx = st.h_desc.p;
@@ -1693,7 +1728,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
             gate_turn turn;
             turn.gate = &dq.gate; turn.seq = job.seq; turn.ev = dev.h2d_done[s]; turn.abort_flag = &t->abort; turn.passed = &passed;
             queued = true;
-            rc = stage_device(e, st, stream, ci, n, t->rtasks != nullptr, t->ref, &h2d, &turn, d);
+            rc = stage_device(e, st, stream, ci, n, t->rtasks != nullptr || t->rdtasks != nullptr, t->ref, &h2d, &turn, d);
             if (!rc && pairs && (he = st.d_pair.reserve(n + 1)) != hipSuccess) rc = fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
             if (!rc) rc = enqueue_batch(e, t->dp, p.variant, st.d_seq.p, st.d_tasks.p, st.d_order.p, ci.plan, st.d_out.p, stream, nullptr, fork_for(ctx, stream, true), pairs ? st.d_pair.p : nullptr);
         }
@@ -1764,9 +1799,9 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
         } else if (ctx->dead) rc = fail(e, BSW_E_HIP, "context is dead (an earlier wait for the GPU timed out)");      /* nothing more is queued on a hung device */
         else if (t->abort) rc = fail(e, BSW_E_HIP, "aborted: another chunk failed");
         else if (f.kind == 1)
-            rc = cigar_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ctasks + base, n, f.max_cigar, f.cigars ? f.cigars + base * (size_t)f.max_cigar : nullptr,
-                             f.max_md, f.md ? f.md + base * (size_t)f.max_md : nullptr, f.cres + base);
-        else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks + base, n, f.mres + base);
+            rc = cigar_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ctasks ? f.ctasks + base : nullptr, n, f.max_cigar, f.cigars ? f.cigars + base * (size_t)f.max_cigar : nullptr,
+                             f.max_md, f.md ? f.md + base * (size_t)f.max_md : nullptr, f.cres + base, f.rd, f.rd ? f.rd_ctasks + base : nullptr);
+        else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks ? f.mtasks + base : nullptr, n, f.mres + base, f.rd, f.rd ? f.rd_mtasks + base : nullptr);
         if (rc) ticket_fail(t, rc, e);
         else { pp.h2d_bytes += lane.h2d; pp.d2h_bytes += lane.d2h; pp.chunks += 1; }
         chunk_done(t);                              /* (the ticket may be collected and freed from here on) */
@@ -1837,7 +1872,8 @@ BSW_LOCAL void pipeline_shutdown(bsw_ctx *ctx)
 }
 
 static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *tasks, const bsw_ref *ref, const bsw_ref_task *rtasks,
-                         size_t n, bsw_result *out, bool packed, bsw_ticket *ticket, const char *what)
+                         size_t n, bsw_result *out, bool packed, bsw_ticket *ticket, const char *what,
+                         const bsw_reads *rd = nullptr /* acquired by the caller; the ticket gives it back */, const bsw_rd_task *rdtasks = nullptr)
 {
     if (ticket) *ticket = 0;
     errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
@@ -1850,6 +1886,7 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
     const size_t G = ctx->devs.size();
     std::shared_ptr<ticket_t> t(new ticket_t());
     t->p = *p; t->dp = dp; t->tasks = tasks; t->ref = ref; t->rtasks = rtasks; t->out = out; t->packed = packed; t->n = n;
+    t->rd = rd; t->rdtasks = rdtasks;
     /* chunk_tasks = 0 (the default): sized by WORK, not by seeds.  A chunk's launches must fill the machine — 128 Ki seeds of
      * the 150 bp single bin (131-base sides) do; PE seeds with their two shorter sides hold half the cells per seed and want
      * twice the seeds (sweep on 4 M PE seeds, profiles/r6/e2e_pe_chunk_sweep.txt: packed input 67 / 91 / 104 / 86 M seeds/s
@@ -1864,7 +1901,8 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
             size_t cnt = 0;
             for (size_t i = 0; i < n; i += step, ++cnt) {
                 double l, r;
-                if (rtasks) { l = rtasks[i].seed.qbeg; r = rtasks[i].l_query - rtasks[i].seed.qbeg - rtasks[i].seed.len; }
+                if (rdtasks) { l = rdtasks[i].seed.qbeg; r = rd->rd[rdtasks[i].read].len - rdtasks[i].seed.qbeg - rdtasks[i].seed.len; }
+                else if (rtasks) { l = rtasks[i].seed.qbeg; r = rtasks[i].l_query - rtasks[i].seed.qbeg - rtasks[i].seed.len; }
                 else { l = tasks[i].lqlen; r = tasks[i].rqlen; }
                 acc += l * l + r * r;
             }
@@ -1895,6 +1933,7 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
         for (size_t k = 0; left; ++k)
             for (size_t d = 0; d < G; ++d)
                 if (k < chunks[d].size()) { pp.devs[d]->q.push_back(chunk_job{t.get(), chunks[d][k], pp.devs[d]->next_seq++}); --left; }
+        t->rd_held = rd;                             /* the ticket exists: from here on IT gives the block back */
         pp.live.push_back(std::move(t));
         pp.submits += 1;
     }
@@ -1926,6 +1965,7 @@ BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket
         t->id = pp.next_id++;
         if (ticket) *ticket = t->id;
         for (size_t k = 0; k < total; ++k) pp.devs[k % G]->q.push_back(chunk_job{t.get(), t->f4.spans[k], 0});
+        t->rd_held = t->f4.rd;                       /* (a *_reads_* submit: acquired by its entry point, given back when the ticket goes) */
         pp.live.push_back(std::move(t));
         pp.submits += 1;
     }
@@ -1964,6 +2004,36 @@ extern "C" int bsw_submit_ref_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref
     return submit_common(ctx, p, nullptr, ref, rtasks, n, out, false, ticket, "bsw_submit_ref");
 }
 extern "C" int bsw_submit_ref(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ref_task *rtasks, size_t n, bsw_result *out) { return bsw_submit_ref_t(ctx, p, ref, rtasks, n, out, nullptr); }
+
+/* bsw_submit_ref_t against a resident read block (bsw_reads_upload): a task names its read by index.  Every check runs HERE, in
+ * the caller's thread — the block and the index first, then what bsw_submit_ref_t's chunks check on the slot threads, with the
+ * same codes and texts — so no task that names a base outside the store is ever queued. */
+extern "C" int bsw_submit_reads_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_task *tasks, size_t n,
+                                  bsw_result *out, bsw_ticket *ticket)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;
+    if (!p || !ref || !rd || (!tasks && n) || (!out && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_submit_reads: NULL argument"));
+    if (ref->d_pac.size() != ctx->devs.size()) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_submit_reads: the reference was uploaded through another context"));
+    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_submit_reads: the read block was uploaded through another context, or is being freed"));
+    bsw_dparams dpx;
+    int rc = check_params(e, p, &dpx);               /* (first, as in the pointer form) */
+    const int mx = mat_max(p->mat);
+    for (size_t i = 0; i < n && !rc; ++i) {
+        if (tasks[i].read >= rd->rd.size()) { rc = fail(e, BSW_E_INVAL, "task %zu: read %u is not in the block of %zu reads", i, tasks[i].read, rd->rd.size()); break; }
+        bsw_task t;
+        size_t so = 0;
+        if ((rc = ref_to_task(e, p, ref->l_pac, rd_to_ref(rd, tasks[i]), i, true, nullptr, so, t))) break;
+        if (t.lqlen > BSW_MAX_QLEN || t.rqlen > BSW_MAX_QLEN) rc = fail(e, BSW_E_LIMIT, "task %zu: length beyond BSW_MAX_QLEN/BSW_MAX_TLEN", i);
+        else if (t.h0 <= 0) rc = fail(e, BSW_E_INVAL, "task %zu: h0 must be > 0", i);
+        else if ((int64_t)t.h0 + (int64_t)(t.lqlen + t.rqlen) * mx >= BSW_MAX_SCORE) rc = fail(e, BSW_E_LIMIT, "task %zu: score range beyond BSW_MAX_SCORE", i);
+    }
+    if (!rc) rc = submit_common(ctx, p, nullptr, ref, nullptr, n, out, false, ticket, "bsw_submit_reads", rd, tasks);
+    else rc = ctx_fail(ctx, e, rc);
+    if (rc) reads_release(rd);                       /* no ticket was made */
+    return rc;
+}
 
 /* every submit in flight; the first failure in submit order is returned (and is what bsw_last_error describes) */
 extern "C" int bsw_wait(bsw_ctx *ctx)

@@ -50,8 +50,21 @@ struct cstate {                       /* one task's place in mem_reg2aln's loop 
     bool live;                        /* still has a try to run */
 };
 
+/* task i of a chunk in the pointer form's terms: the caller's record, or the one a resident-read task stands for (query stays
+ * NULL: the bases are on the device already; l_query = qe - qb, checked at submit) */
+static inline bsw_ctask ctask_of(const bsw_ctask *tasks, const bsw_rd_ctask *rtasks, size_t i)
+{
+    if (!rtasks) return tasks[i];
+    const bsw_rd_ctask &r = rtasks[i];
+    bsw_ctask t;
+    t.query = nullptr; t.l_query = r.qe - r.qb; t.w = r.w; t.rb = r.rb; t.re = r.re; t.w_cap = r.w_cap; t.min_score = r.min_score;
+    t.max_tries = r.max_tries; t._pad = 0;
+    return t;
+}
+
 BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
-                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res)
+                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res,
+                          const bsw_reads *rd, const bsw_rd_ctask *rtasks)
 {
     stage_t &st = *L.st;
     hipStream_t s = L.s;
@@ -66,7 +79,7 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     uint64_t acc = 0, accb = 0;
     const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
     for (size_t i = 0; i < n; ++i) {
-        const bsw_ctask &t = tasks[i];
+        const bsw_ctask t = ctask_of(tasks, rtasks, i);
         bsw_dtask &d = st.h_tasks.p[i];
         bsw_rawoff &r = st.h_roff.p[i];
         bsw_refx &x = st.h_desc.p[i];
@@ -88,18 +101,22 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         const bool rev = t.rb >= l_pac;
         const uint32_t qw = (uint32_t)acc, tw = (uint32_t)(acc + nwords(t.l_query));
         acc += nwords(t.l_query) + nwords(rlen);
+        /* where the slice starts: a byte offset into the raw bytes, or (resident reads) the position of base qb of its read */
+        const uint32_t at = rd ? rd->pos(rtasks[i].read) + (uint32_t)rtasks[i].qb : (uint32_t)accb;
         if (rev) {                        /* left side only: read backwards from its last base, target downwards from re - 1 */
             d.lq_off = qw; d.lt_off = tw; d.lqlen = (uint16_t)t.l_query; d.ltlen = (uint16_t)rlen;
-            r.lq = (uint32_t)accb + (uint32_t)t.l_query - 1u;
+            r.lq = at + (uint32_t)t.l_query - 1u;
             x.xl = t.re - 1;
         } else {                          /* right side only: read forwards, target upwards from rb */
             d.rq_off = qw; d.rt_off = tw; d.rqlen = (uint16_t)t.l_query; d.rtlen = (uint16_t)rlen;
-            r.rq = (uint32_t)accb;
+            r.rq = at;
             x.xr = t.rb;
         }
-        accb += (uint64_t)t.l_query;
-        if (t.query < lo) lo = t.query;
-        if (t.query + t.l_query > hi) hi = t.query + t.l_query;
+        if (!rd) {
+            accb += (uint64_t)t.l_query;
+            if (t.query < lo) lo = t.query;
+            if (t.query + t.l_query > hi) hi = t.query + t.l_query;
+        }
         c.q_off = qw; c.t_off = tw; c.qlen = t.l_query; c.tlen = rlen;
         c.flags = rev ? BSW_CD_REV : 0u;
         if (t.l_query == rlen && q.w2 == 0) {            /* the no-gap shortcut: the NM / MD kernel does it */
@@ -171,8 +188,8 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), n * sizeof(bsw_cdtask), 0), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
     L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_cdtask));
-    HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 1, ref->d_pac[L.dev], l_pac, st.d_desc.p,
-                               st.d_seq.p, nullptr, s));
+    HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
+                               BSW_PACK_REV_LEFT | (rd ? BSW_PACK_STORE : 0), ref->d_pac[L.dev], l_pac, st.d_desc.p, st.d_seq.p, nullptr, s));
 
     /* the tries: each launches the global kernels on the tasks still in the loop, then reads their scores */
     for (size_t i = 0; i < n; ++i) if (cs[i].live) live.push_back((uint32_t)i);
@@ -217,7 +234,7 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         std::vector<uint32_t> next;
         for (uint32_t i : live) {
             cstate &q = cs[i];
-            const bsw_ctask &t = tasks[i];
+            const bsw_ctask t = ctask_of(tasks, rtasks, i);
             const int score = grp[i].score;
             ++q.tries;
             q.live = false;
@@ -274,17 +291,24 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
 
 /* what both entry points check before anything runs or is queued: the parameters (the band is per task: pp gets w = 0), then
  * the tasks in order — the first malformed one rejects the call */
-static int cigar_validate(errs &e, const bsw_params *p, const bsw_ctask *tasks, size_t n, bsw_params *pp, bsw_dparams *dp)
+static int cigar_validate(errs &e, const bsw_params *p, const bsw_ctask *tasks, size_t n, bsw_params *pp, bsw_dparams *dp,
+                          const bsw_reads *rd = nullptr, const bsw_rd_ctask *rtasks = nullptr)
 {
     *pp = *p;
     pp->w = 0;                                        /* the band is per task here */
     int rc = check_params(e, pp, dp);
     if (rc) return rc;
     for (size_t i = 0; i < n; ++i) {
-        const bsw_ctask &t = tasks[i];
+        if (rd) {                                     /* the slice lies inside its read: nothing else may reach the kernel */
+            const bsw_rd_ctask &r = rtasks[i];
+            if (r.read >= rd->rd.size()) return fail(e, BSW_E_INVAL, "cigar task %zu: read %u is not in the block of %zu reads", i, r.read, rd->rd.size());
+            if (r.qb < 0 || r.qe < r.qb || r.qe > rd->rd[r.read].len)
+                return fail(e, BSW_E_INVAL, "cigar task %zu: [qb, qe) = [%d, %d) is not inside read %u of %d bases", i, r.qb, r.qe, r.read, rd->rd[r.read].len);
+        }
+        const bsw_ctask t = ctask_of(tasks, rtasks, i);
         if (t.l_query < 0 || t.w < 0 || t.w_cap < 0 || t.max_tries < 0 || t.max_tries > 3)
             return fail(e, BSW_E_INVAL, "cigar task %zu: negative length or band, or max_tries outside 0..3", i);
-        if (t.l_query && !t.query) return fail(e, BSW_E_INVAL, "cigar task %zu: NULL read", i);
+        if (t.l_query && !t.query && !rd) return fail(e, BSW_E_INVAL, "cigar task %zu: NULL read", i);
         if (t.l_query > BSW_GLOBAL_MAX_QLEN || t.w > BSW_MAX_TLEN || t.w_cap > BSW_MAX_TLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
             return fail(e, BSW_E_LIMIT, "cigar task %zu: beyond BSW_GLOBAL_MAX_QLEN / BSW_MAX_TLEN", i);
     }
@@ -356,25 +380,26 @@ static uint64_t cigar_chunk_work()
 /* bsw_cigar_ref_batch as a ticket of the context's pipeline: the same checks in the caller's thread, then chunks of about
  * cigar_chunk_work() cells (within the batch call's bounds, and F4_CIGAR_OUT_MAX bytes of CIGAR / MD room) through the slots
  * of every device, chunk k on device k mod n_devices against that device's copy of the reference. */
-extern "C" int bsw_cigar_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ctask *tasks, size_t n,
-                                      int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket)
+/* both ticket forms: tasks (pointer form) or rd + rtasks (resident reads) */
+static int cigar_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ctask *tasks, const bsw_reads *rd, const bsw_rd_ctask *rtasks,
+                        size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket, const char *what)
 {
     if (!ctx) return BSW_E_INVAL;
     if (ticket) *ticket = 0;
     errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
-    if (!p || !ref || (!tasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1))
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_ref_submit: bad argument"));
+    if (!p || !ref || (!tasks && !rtasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1))
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: bad argument", what));
     if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_ref_submit: the reference was uploaded through another context"));
-    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "bsw_cigar_ref_submit: context is dead (an earlier wait for the GPU timed out)"));
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what));
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
     f4_submit f;
     f.kind = 1;
-    int rc = cigar_validate(e, p, tasks, n, &f.pp, &f.dp);
+    int rc = cigar_validate(e, p, tasks, n, &f.pp, &f.dp, rd, rtasks);
     if (rc) return ctx_fail(ctx, e, rc);
-    f.ref = ref; f.ctasks = tasks; f.n = n; f.max_cigar = max_cigar; f.cigars = cigars; f.max_md = max_md; f.md = md; f.cres = res;
+    f.ref = ref; f.ctasks = tasks; f.rd = rd; f.rd_ctasks = rtasks; f.n = n; f.max_cigar = max_cigar; f.cigars = cigars; f.max_md = max_md; f.md = md; f.cres = res;
     std::vector<uint64_t> nz(n), ns(n);               /* one walk over the tasks: the band formula is the cost of this pass */
     uint64_t total = 0;
-    for (size_t i = 0; i < n; ++i) { cigar_task_cost(f.pp, tasks[i], nz[i], ns[i]); total += nz[i]; }
+    for (size_t i = 0; i < n; ++i) { cigar_task_cost(f.pp, ctask_of(tasks, rtasks, i), nz[i], ns[i]); total += nz[i]; }
     const uint64_t wcap = std::min<uint64_t>(f4_chunk_work(ctx, total, cigar_chunk_work()), 4ull << 30);
     const uint64_t per_out = std::max<uint64_t>((uint64_t)max_cigar * sizeof(uint32_t), md ? (uint64_t)max_md : 0);
     for (size_t a = 0; a < n;) {
@@ -390,5 +415,25 @@ extern "C" int bsw_cigar_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const b
         f.spans.push_back(chunk_span{a, b - a});
         a = b;
     }
-    return pipeline_submit_f4(ctx, std::move(f), ticket, "bsw_cigar_ref_submit");
+    return pipeline_submit_f4(ctx, std::move(f), ticket, what);
+}
+
+extern "C" int bsw_cigar_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ctask *tasks, size_t n,
+                                      int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket)
+{
+    return cigar_submit(ctx, p, ref, tasks, nullptr, nullptr, n, max_cigar, cigars, max_md, md, res, ticket, "bsw_cigar_ref_submit");
+}
+
+/* the same against a resident read block: a task names its read by index and the slice by [qb, qe) */
+extern "C" int bsw_cigar_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_ctask *tasks,
+                                        size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;
+    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_reads_submit: bad argument"));
+    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_reads_submit: the read block was uploaded through another context, or is being freed"));
+    const int rc = cigar_submit(ctx, p, ref, nullptr, rd, tasks, n, max_cigar, cigars, max_md, md, res, ticket, "bsw_cigar_reads_submit");
+    if (rc) reads_release(rd);                       /* no ticket was made */
+    return rc;
 }

@@ -9,6 +9,7 @@
  *   bsw_f4.hip      ksw_global2 / ksw_align2 hosts (F4)
  *   bsw_cigar.hip   bwa_gen_cigar2 (+ mem_reg2aln's retries) against the resident reference, batch and ticketed submit
  *   bsw_matesw.hip  mem_matesw's ksw_align2 against the resident reference, batch and ticketed submit
+ *   bsw_reads.hip   the resident read store: upload, free, info (its submits live with their pointer forms in the three files above)
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
 #ifndef BSW_INTERNAL_H
@@ -36,6 +37,7 @@
 
 #include "bsw_device.h"
 #include "bsw_stage.h"
+#include "bsw_reads_fetch.h"
 
 #define BSW_LOCAL __attribute__((visibility("hidden")))
 
@@ -44,6 +46,20 @@ struct bsw_ref {
     int64_t l_pac = 0;
 };
 
+/* A resident read block (bsw_reads_upload, bsw_reads.hip): one 4-bit packed copy per device of the context, every read on a word
+ * boundary.  A base has a POSITION in the store, 16 * woff + index in the read; positions fit 32 bits (checked at upload) and are
+ * what bsw_rawoff carries to bsw_pack_kernel in place of byte offsets (BSW_PACK_STORE).  Plain data: the submit paths read it
+ * without calling into bsw_reads.hip. */
+struct bsw_reads {
+    struct ent { uint32_t woff; int32_t len; };     /* word offset of a read in the store, its length */
+    const bsw_ctx *owner = nullptr;
+    std::vector<uint64_t *> d_words;  /* one allocation per device (index = position in devs): BSW_READS_SLACK zeroed words, the reads, the same slack */
+    std::vector<ent> rd;
+    uint64_t bases = 0, words = 0;
+    std::atomic<int> users{0};        /* tickets not collected yet that use the block; -1: being freed */
+    const uint64_t *dev(size_t d) const { return d_words[d] + BSW_READS_SLACK; }    /* word 0 of the reads */
+    uint32_t pos(uint32_t read) const { return rd[read].woff << 4; }
+};
 /* BSW_KERNEL_AUTO: a lane launch costs one wave's full duration (1.0 ms for a 131-column side) however few seeds it
  * holds, and a chunk with both sides pays it twice; the general kernels scale with the seed count.  Measured crossovers,
  * device-resident (profiles/r4/crossover_general_kernels.json): one-sided 131 x 257 seeds 27 k (17.4 k before the
@@ -336,6 +352,18 @@ inline int ctx_fail(bsw_ctx *ctx, const errs &e, int rc)
     return rc;
 }
 
+/* a *_reads_* submit takes its block: false for a block of another context, or one that is being freed.  The ticket gives it
+ * back when it is destroyed, i.e. collected (ticket_t, bsw_batch.hip). */
+inline bool reads_acquire(const bsw_ctx *ctx, const bsw_reads *rd)
+{
+    if (rd->owner != ctx || rd->d_words.size() != ctx->devs.size()) return false;
+    bsw_reads *w = const_cast<bsw_reads *>(rd);
+    int u = w->users.load();
+    while (u >= 0 && !w->users.compare_exchange_weak(u, u + 1)) {}
+    return u >= 0;
+}
+inline void reads_release(const bsw_reads *rd) { if (rd) const_cast<bsw_reads *>(rd)->users.fetch_sub(1); }
+
 /* Where one chunk of bsw_cigar_ref_* / bsw_matesw_ref_* runs: the device (index into bsw_config.devices[], and so into
  * bsw_ref::d_pac), the staging, the stream, the watchdog event and the scratch buffers.  The synchronous calls pass the context's
  * own lane (ctx_lane); every pipeline slot has one over its own stage_t, stream and f4_bufs. */
@@ -397,6 +425,9 @@ struct f4_submit {
     const bsw_ref *ref = nullptr;
     const bsw_ctask *ctasks = nullptr;
     const bsw_mtask *mtasks = nullptr;
+    const bsw_reads *rd = nullptr;    /* non-NULL: the tasks name reads of this resident block (rd_ctasks / rd_mtasks instead of the two above) */
+    const bsw_rd_ctask *rd_ctasks = nullptr;
+    const bsw_rd_mtask *rd_mtasks = nullptr;
     size_t n = 0;
     int max_cigar = 0, max_md = 0;
     uint32_t *cigars = nullptr;
@@ -415,10 +446,13 @@ inline uint64_t f4_chunk_work(const bsw_ctx *ctx, uint64_t total, uint64_t targe
 /* ---- bsw_batch.hip: queues the chunks of `f` on the devices' queues in submit order; BSW_E_BUSY changes nothing ---- */
 BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket, const char *what);
 /* ---- bsw_cigar.hip / bsw_matesw.hip: one chunk on a lane ---- */
+/* rd != NULL: the chunk's tasks are rtasks[0..n) and name reads of the resident block (tasks is NULL then): the per-task work is
+ * the device records plus a base position — no span, no registration test, no gather, no raw bytes */
 BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
-                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res);
+                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res,
+                          const bsw_reads *rd = nullptr, const bsw_rd_ctask *rtasks = nullptr);
 BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                           bsw_mresult *res);
+                           bsw_mresult *res, const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr);
 
 struct chunk_info;
 struct bsw_dev_batch {
@@ -486,6 +520,8 @@ struct chunk_info {
     bsw_binparams bp;
     bool streaming = false;           /* (set by the caller) one of MANY chunks of a submit: the slots keep the GPU full, so the chunk is bound by
                                          throughput whatever its size — the lane kernels then keep a list per side (no fused launch) */
+    const uint64_t *store = nullptr;  /* non-NULL (bsw_submit_reads_t): the queries come from this device copy of a resident read block — rawoff holds
+                                         base positions, no raw bytes travel */
     bool rb_on = false;               /* the records' word offsets are still relative: bsw_rebase_kernel runs behind their DMA */
     bsw_rebase rb{};
 };

@@ -27,8 +27,19 @@ static bool mtask_runs(const bsw_mtask &t, int64_t l_pac)
     return t.l_ms > 0 && t.rb < t.re && !(t.rb < l_pac && t.re > l_pac) && t.rb >= 0 && t.re <= 2 * l_pac;
 }
 
+/* task i of a chunk in the pointer form's terms: the caller's record, or the one a resident-read task stands for (mate stays
+ * NULL: the bases are on the device already) */
+static inline bsw_mtask mtask_of(const bsw_mtask *tasks, const bsw_reads *rd, const bsw_rd_mtask *rtasks, size_t i)
+{
+    if (!rd) return tasks[i];
+    const bsw_rd_mtask &r = rtasks[i];
+    bsw_mtask t;
+    t.mate = nullptr; t.l_ms = rd->rd[r.read].len; t.is_rev = r.is_rev; t.rb = r.rb; t.re = r.re; t.xtra = r.xtra; t.min_score = r.min_score;
+    return t;
+}
+
 BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                           bsw_mresult *res)
+                           bsw_mresult *res, const bsw_reads *rd, const bsw_rd_mtask *rtasks)
 {
     stage_t &st = *L.st;
     hipStream_t s = L.s;
@@ -44,7 +55,7 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     uint64_t acc = 0, accb = 0, bacc = 0;
     const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
     for (size_t i = 0; i < n; ++i) {
-        const bsw_mtask &t = tasks[i];
+        const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
         bsw_dtask &d = st.h_tasks.p[i];
         bsw_rawoff &r = st.h_roff.p[i];
         bsw_refx &x = st.h_desc.p[i];
@@ -57,10 +68,13 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
         d.rq_off = (uint32_t)acc; acc += nwords(t.l_ms);
         d.rt_off = (uint32_t)acc; acc += nwords(tlen);
         d.rqlen = (uint16_t)t.l_ms; d.rtlen = (uint16_t)tlen;
-        r.rq = (uint32_t)accb; accb += (uint64_t)t.l_ms;
         x.xr = t.rb;
-        if (t.mate < lo) lo = t.mate;
-        if (t.mate + t.l_ms > hi) hi = t.mate + t.l_ms;
+        if (rd) r.rq = rd->pos(rtasks[i].read);      /* the mate's first base in the store: read forwards */
+        else {
+            r.rq = (uint32_t)accb; accb += (uint64_t)t.l_ms;
+            if (t.mate < lo) lo = t.mate;
+            if (t.mate + t.l_ms > hi) hi = t.mate + t.l_ms;
+        }
         bsw_adtask &a = at[i];
         a.q_off = d.rq_off; a.t_off = d.rt_off; a.qlen = t.l_ms; a.tlen = tlen; a.xtra = t.xtra;
         a.pad = t.is_rev ? BSW_AD_QRC : 0u;
@@ -99,15 +113,15 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     const bsw_kswr *alnp = L.h_back ? (const bsw_kswr *)L.h_back->p : aln.data();      /* a slot reads back into pinned memory */
     drain_on_failure drain(ctx, s, L.ev);
     if (!order.empty()) {
-        if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
+        if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));     /* (resident reads: rawb == 0) */
         HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, L.dma_src(at.data(), n * sizeof(bsw_adtask), 0), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(order.data(), order.size() * sizeof(uint32_t), in_order), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_adtask)) + order.size() * sizeof(uint32_t);
-        HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, ref->d_pac[L.dev], l_pac, st.d_desc.p,
-                                   st.d_seq.p, nullptr, s));
+        HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
+                                   rd ? BSW_PACK_STORE : 0, ref->d_pac[L.dev], l_pac, st.d_desc.p, st.d_seq.p, nullptr, s));
         for (int c = 0; c < ncls; ++c) {
             const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
             if (!k) continue;
@@ -121,7 +135,7 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     }
     /* mem_matesw: if (aln.score >= opt->min_seed_len && aln.qb >= 0) { b.qb = is_rev? l_ms - (aln.qe + 1) : aln.qb; ... } */
     for (size_t i = 0; i < n; ++i) {
-        const bsw_mtask &t = tasks[i];
+        const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
         bsw_mresult &m = res[i];
         memset(&m, 0, sizeof(m));
         if (!runs[i]) {
@@ -151,7 +165,8 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
 
 /* what both entry points check before anything runs or is queued: the parameters (band and variant are the call's own), then
  * the tasks in order — the first malformed one rejects the call */
-static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks, size_t n, const char *what, bsw_dparams *dp)
+static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks, size_t n, const char *what, bsw_dparams *dp,
+                           const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr)
 {
     bsw_params pp = *p;
     pp.w = 0; pp.variant = BSW_VARIANT_H;
@@ -161,9 +176,10 @@ static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks,
     for (int i = 0; i < 25; ++i) mxs = std::max(mxs, (int)p->mat[i]);
     if (mxs <= 0) return fail(e, BSW_E_INVAL, "%s: the scoring matrix has no positive score", what);
     for (size_t i = 0; i < n; ++i) {
-        const bsw_mtask &t = tasks[i];
+        if (rd && rtasks[i].read >= rd->rd.size()) return fail(e, BSW_E_INVAL, "mate task %zu: read %u is not in the block of %zu reads", i, rtasks[i].read, rd->rd.size());
+        const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
         if (t.l_ms < 0) return fail(e, BSW_E_INVAL, "mate task %zu: negative length", i);
-        if (t.l_ms && !t.mate) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
+        if (t.l_ms && !t.mate && !rd) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
         if (t.is_rev != 0 && t.is_rev != 1) return fail(e, BSW_E_INVAL, "mate task %zu: is_rev is neither 0 nor 1", i);
         if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "mate task %zu: unknown xtra flag", i);
         if (t.l_ms > BSW_ALIGN_MAX_QLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
@@ -219,30 +235,33 @@ static uint64_t matesw_chunk_work()
 /* bsw_matesw_ref_batch as a ticket of the context's pipeline: the same checks in the caller's thread, then chunks of about
  * matesw_chunk_work() cells (and within the batch call's bounds) through the slots of every device, chunk k on device
  * k mod n_devices against that device's copy of the reference.  Collected by bsw_wait_ticket / bsw_wait. */
-extern "C" int bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                                       bsw_mresult *res, bsw_ticket *ticket)
+/* both ticket forms: tasks (pointer form) or rd + rtasks (resident reads) */
+static int matesw_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_mtask *tasks, const bsw_reads *rd,
+                         const bsw_rd_mtask *rtasks, size_t n, bsw_mresult *res, bsw_ticket *ticket, const char *what)
 {
     if (!ctx) return BSW_E_INVAL;
     if (ticket) *ticket = 0;
     errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
-    if (!p || !ref || (!tasks && n) || (!res && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_ref_submit: NULL argument"));
+    if (!p || !ref || (!tasks && !rtasks && n) || (!res && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: NULL argument", what));
     if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_ref_submit: the reference was uploaded through another context"));
-    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "bsw_matesw_ref_submit: context is dead (an earlier wait for the GPU timed out)"));
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what));
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
     f4_submit f;
     f.kind = 2; f.pp = *p; f.pp.w = 0; f.pp.variant = BSW_VARIANT_H;
-    int rc = matesw_validate(e, p, tasks, n, "bsw_matesw_ref_submit", &f.dp);
+    int rc = matesw_validate(e, p, tasks, n, what, &f.dp, rd, rtasks);
     if (rc) return ctx_fail(ctx, e, rc);
-    f.ref = ref; f.mtasks = tasks; f.n = n; f.mres = res;
+    f.ref = ref; f.mtasks = tasks; f.rd = rd; f.rd_mtasks = rtasks; f.n = n; f.mres = res;
     uint64_t total = 0;
-    for (size_t i = 0; i < n; ++i)
-        if (tasks[i].re > tasks[i].rb) total += (uint64_t)tasks[i].l_ms * (uint64_t)(tasks[i].re - tasks[i].rb);
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
+        if (t.re > t.rb) total += (uint64_t)t.l_ms * (uint64_t)(t.re - t.rb);
+    }
     const uint64_t wcap = f4_chunk_work(ctx, total, matesw_chunk_work());
     for (size_t a = 0; a < n;) {                      /* the batch call's bounds, and the work of a chunk */
         size_t b = a;
         uint64_t sb = 0, bb = 0, wb = 0;
         while (b < n && b - a < (1u << 20)) {
-            const bsw_mtask &t = tasks[b];
+            const bsw_mtask t = mtask_of(tasks, rd, rtasks, b);
             const uint64_t tl = t.re > t.rb ? (uint64_t)(t.re - t.rb) : 0;
             if (b > a && (sb + (uint64_t)t.l_ms + tl > (1ull << 31) || bb + tl > (1ull << 28) || wb >= wcap)) break;      /* (a chunk is closed once it HOLDS its share: no sliver is left over) */
             sb += (uint64_t)t.l_ms + tl;
@@ -253,5 +272,26 @@ extern "C" int bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const 
         f.spans.push_back(chunk_span{a, b - a});
         a = b;
     }
-    return pipeline_submit_f4(ctx, std::move(f), ticket, "bsw_matesw_ref_submit");
+    return pipeline_submit_f4(ctx, std::move(f), ticket, what);
+}
+
+extern "C" int bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                                       bsw_mresult *res, bsw_ticket *ticket)
+{
+    return matesw_submit(ctx, p, ref, tasks, nullptr, nullptr, n, res, ticket, "bsw_matesw_ref_submit");
+}
+
+/* the same against a resident read block: a task names its mate by index, and only the 32-byte task records' worth of
+ * coordinates cross PCIe (the device records built from them: 76 + 32 + 4 bytes a task) */
+extern "C" int bsw_matesw_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_mtask *tasks,
+                                         size_t n, bsw_mresult *res, bsw_ticket *ticket)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;
+    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_reads_submit: NULL argument"));
+    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_reads_submit: the read block was uploaded through another context, or is being freed"));
+    const int rc = matesw_submit(ctx, p, ref, nullptr, rd, tasks, n, res, ticket, "bsw_matesw_reads_submit");
+    if (rc) reads_release(rd);                       /* no ticket was made */
+    return rc;
 }

@@ -1,0 +1,103 @@
+/*
+ * bsw_reads.hip — the resident read store: bsw_reads_upload / bsw_reads_free / bsw_reads_info (part of the host side of
+ * libbwasw_mi355.so; shared types: bsw_internal.h).
+ *
+ * A read block is packed once on the host into the device sequence format (4 bits per base, every read on a word boundary,
+ * BSW_READS_SLACK zeroed words in front and behind) and copied to every device of the context, as bsw_ref_upload copies the pac.
+ * The three *_reads_* submits live with their pointer forms (bsw_batch.hip, bsw_matesw.hip, bsw_cigar.hip) and read the block
+ * as plain data; bsw_pack_kernel fetches the query words from it (bsw_reads_fetch.h).
+ *
+ * These calls may run while tickets are in flight and from several threads: they use no state of the context but its device
+ * list and its error text (under its lock), and the upload copies on a stream of its own per device.
+ */
+#include "bsw_internal.h"
+
+/* positions are 32 bits: 16 * words + the longest read must stay below 2^32 */
+#define READS_MAX_WORDS ((1ull << 28) - (1ull << 13))
+#define READS_MAX_LEN 65535
+
+static void reads_release_devices(bsw_ctx *ctx, bsw_reads *r)
+{
+    for (size_t d = 0; d < r->d_words.size(); ++d) {
+        if (!r->d_words[d]) continue;
+        (void)hipSetDevice(ctx->devs[d].device);
+        (void)hipFree(r->d_words[d]);
+        r->d_words[d] = nullptr;
+    }
+    (void)hipSetDevice(ctx->device0());
+}
+
+extern "C" int bsw_reads_upload(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out)
+{
+    if (!ctx) return BSW_E_INVAL;
+    errs e;
+    if (!out || ((!reads || !lens) && n_reads)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_upload: NULL argument"));
+    *out = nullptr;
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "bsw_reads_upload: context is dead (an earlier wait for the GPU timed out)"));
+    if (n_reads >= (1ull << 32)) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "bsw_reads_upload: more than 2^32 - 1 reads"));
+    std::unique_ptr<bsw_reads> r(new bsw_reads());
+    r->owner = ctx;
+    r->rd.resize(n_reads);
+    uint64_t words = 0, bases = 0;
+    for (size_t i = 0; i < n_reads; ++i) {
+        if (lens[i] < 0) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_upload: read %zu: negative length", i));
+        if (lens[i] && !reads[i]) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_upload: read %zu: NULL read", i));
+        if (lens[i] > READS_MAX_LEN) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "bsw_reads_upload: read %zu: more than %d bases", i, READS_MAX_LEN));
+        r->rd[i] = bsw_reads::ent{(uint32_t)words, lens[i]};
+        words += nwords(lens[i]);
+        bases += (uint64_t)lens[i];
+        if (words > READS_MAX_WORDS) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "bsw_reads_upload: the block needs more than %llu packed words; split it", (unsigned long long)READS_MAX_WORDS));
+    }
+    r->words = words;
+    r->bases = bases;
+    /* the device image: slack | reads | slack, packed here once for all devices */
+    const size_t total = (size_t)words + 2 * BSW_READS_SLACK;
+    std::vector<uint64_t> img;
+    try { img.assign(total, 0ull); } catch (const std::bad_alloc &) { return ctx_fail(ctx, e, fail(e, BSW_E_NOMEM, "bsw_reads_upload: %zu bytes of host memory", total * 8)); }
+    for (size_t i = 0; i < n_reads; ++i)
+        if (lens[i]) (void)bsw_pack_bases(reads[i], lens[i], img.data() + BSW_READS_SLACK + r->rd[i].woff);
+    r->d_words.assign(ctx->devs.size(), nullptr);
+    for (size_t d = 0; d < ctx->devs.size(); ++d) {               /* every GPU of the context keeps its own copy */
+        hipStream_t up = nullptr;
+        hipError_t he = hipSetDevice(ctx->devs[d].device);
+        if (he == hipSuccess) he = hipMalloc((void **)&r->d_words[d], total * sizeof(uint64_t));
+        if (he == hipSuccess) he = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
+        if (he == hipSuccess) he = hipMemcpyAsync(r->d_words[d], img.data(), total * sizeof(uint64_t), hipMemcpyHostToDevice, up);
+        if (up) {
+            const hipError_t se = hipStreamSynchronize(up);      /* (also behind a failed copy: img is ours until nothing reads it) */
+            if (he == hipSuccess) he = se;
+            const hipError_t de = hipStreamDestroy(up);
+            if (he == hipSuccess) he = de;
+        }
+        if (he != hipSuccess) {
+            reads_release_devices(ctx, r.get());                 /* a failed upload leaves no copy on any device */
+            return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "read block upload to device %d: %s", ctx->devs[d].device, hipGetErrorString(he)));
+        }
+    }
+    (void)hipSetDevice(ctx->device0());
+    *out = r.release();
+    return BSW_OK;
+}
+
+extern "C" int bsw_reads_free(bsw_ctx *ctx, bsw_reads *rd)
+{
+    if (!rd) return BSW_OK;
+    if (!ctx) return BSW_E_INVAL;
+    errs e;
+    if (rd->owner != ctx) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_free: the read block was uploaded through another context"));
+    int none = 0;
+    if (!rd->users.compare_exchange_strong(none, -1))
+        return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "bsw_reads_free: %d ticket(s) that use the block have not been collected", none));
+    reads_release_devices(ctx, rd);
+    delete rd;
+    return BSW_OK;
+}
+
+extern "C" int bsw_reads_info(const bsw_reads *rd, uint64_t *n_reads, uint64_t *bases, uint64_t *device_bytes)
+{
+    if (!rd) return BSW_E_INVAL;
+    if (n_reads) *n_reads = rd->rd.size();
+    if (bases) *bases = rd->bases;
+    if (device_bytes) *device_bytes = (rd->words + 2 * BSW_READS_SLACK) * sizeof(uint64_t);
+    return BSW_OK;
+}

@@ -20,9 +20,11 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "bsw_device.h"
 #include "bsw_stage.h"
+#include "bsw_reads_fetch.h"
 
 namespace bsw {
 
@@ -113,6 +115,9 @@ __device__ __forceinline__ uint64_t fetch_word(const uint8_t *__restrict__ pac, 
  * rev_left: the left query is read BACKWARDS from its offset (base k = raw[off - k]): a read DMA'd as it is holds
  * query[0..qbeg) forwards, mem_chain2aln extends it reversed (the host's reversal loop, done here for free).
  * pac != NULL: the two target sequences are fetched from the resident reference instead of packed from raw bytes.
+ * rev_left & BSW_PACK_STORE: the two QUERIES come from the resident read store (bsw_reads_fetch.h): raw addresses its word 0,
+ * roff holds base positions instead of byte offsets, and the words are funnel-shifted out of the 4-bit store instead of squeezed
+ * out of bytes (the left query backwards from its position when rev_left & BSW_PACK_REV_LEFT, as above).
  * nflag != NULL: nflag[seed] = (left query holds an N) | (right query holds an N) << 1 — what the binning needs to know about
  * the bases, so that bsw_bin_count does not have to read `seq` again. */
 #define BSW_PACK_SEEDS 64
@@ -159,6 +164,9 @@ __global__ __launch_bounds__(256) void bsw_pack_kernel(const uint8_t *__restrict
     if (sq == 255) start[256] = before + inc;
     __syncthreads();
     const uint32_t total = start[256];
+    /* the walk over the group's words, once per source of the queries: the source is uniform over the launch, so the choice is a
+     * scalar branch around two loops and the store costs the byte path neither a divergent branch nor a register */
+    const auto walk = [&](auto from_store) {
     for (uint32_t w = (uint32_t)sq; w < total; w += 256u) {
         int lo = 0;                                            /* the last sequence that starts at or before word w */
 #pragma unroll
@@ -172,8 +180,11 @@ __global__ __launch_bounds__(256) void bsw_pack_kernel(const uint8_t *__restrict
             const bsw_refx X = refx[tsk];
             const bool left = wh == 1;
             v = fetch_word(pac, l_pac, left ? X.xl : X.xr, left ? -1 : 1, L, k);
+        } else if (decltype(from_store)::value) {
+            /* the resident read store: s_boff = the base position of the query's first base */
+            v = bsw_reads_word((const uint64_t *)raw, s_boff[lo], (rev_left & BSW_PACK_REV_LEFT) && wh == 0, L, k);
         } else {
-            const bool rev = rev_left && wh == 0;
+            const bool rev = (rev_left & BSW_PACK_REV_LEFT) && wh == 0;
             const uint8_t *base = raw + s_boff[lo];
             /* forwards: bytes [off + 16k, +16); backwards: bytes (off - 16k - 16, off - 16k], then mirrored */
             const uintptr_t a = rev ? (uintptr_t)base - 16u * (uint32_t)k - 15u : (uintptr_t)base + 16u * (uint32_t)k;
@@ -200,6 +211,9 @@ __global__ __launch_bounds__(256) void bsw_pack_kernel(const uint8_t *__restrict
         seq[s_woff[lo] + (uint32_t)k] = v;
         if (!(wh & 1) && (v & 0x4444444444444444ull)) s_hasn[lo] = 1u;      /* (a query word with an N: rare; any writer writes the same 1) */
     }
+    };
+    if (pac && (rev_left & BSW_PACK_STORE)) walk(std::true_type());      /* (store launches always fetch their targets from the pac) */
+    else walk(std::false_type());
     if (nflag) {
         __syncthreads();
         if (which == 0 && ti < n) nflag[ti] = (uint8_t)((s_hasn[sq] ? 1u : 0u) | (s_hasn[sq + 2] ? 2u : 0u));
@@ -475,6 +489,7 @@ hipError_t launch_pack(const uint8_t *raw, const bsw_dtask *tasks, const bsw_raw
                        const uint8_t *pac, int64_t l_pac, const bsw_refx *refx, uint64_t *seq, uint8_t *nflag, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
+    if ((rev_left & BSW_PACK_STORE) && !pac) return hipErrorInvalidValue;      /* positions are never taken for byte offsets */
     hipLaunchKernelGGL(bsw_pack_kernel, dim3((n + BSW_PACK_SEEDS - 1u) / BSW_PACK_SEEDS), dim3(256), 0, s, raw, tasks, roff, bias, n, rev_left, pac, l_pac, refx, seq, nflag);
     return hipGetLastError();
 }

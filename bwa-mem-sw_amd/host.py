@@ -48,6 +48,13 @@ MRESULT = np.dtype([("aln", KSWR), ("status", "<i4"), ("rb", "<i8"), ("re", "<i8
                     ("score", "<i4"), ("csub", "<i4"), ("seedcov", "<i4"), ("_pad", "<i4")], align=True)
 REF_TASK = np.dtype([("query", "<u8"), ("l_query", "<i4"), ("init_score", "<i4"), ("seed", SEED),
                      ("rmax0", "<i8"), ("rmax1", "<i8"), ("tag", "<u4"), ("_pad", "<u4")])
+# resident read blocks (bsw_reads_upload): the three stages' tasks name a read by its index
+RD_TASK = np.dtype([("read", "<u4"), ("init_score", "<i4"), ("seed", SEED), ("rmax0", "<i8"), ("rmax1", "<i8"),
+                    ("tag", "<u4"), ("_pad", "<u4")])
+RD_MTASK = np.dtype([("read", "<u4"), ("is_rev", "<i4"), ("rb", "<i8"), ("re", "<i8"), ("xtra", "<i4"), ("min_score", "<i4")])
+RD_CTASK = np.dtype([("read", "<u4"), ("qb", "<i4"), ("qe", "<i4"), ("w", "<i4"), ("rb", "<i8"), ("re", "<i8"),
+                     ("w_cap", "<i4"), ("min_score", "<i4"), ("max_tries", "<i4"), ("_pad", "<i4")])
+assert RD_TASK.itemsize == 48 and RD_MTASK.itemsize == 32 and RD_CTASK.itemsize == 48
 MAX_DEVICES = 16
 CONFIG = np.dtype([("device", "<i4"), ("kernel", "<i4"), ("streams", "<i4"), ("pack_threads", "<i4"),
                    ("chunk_tasks", "<u8"), ("n_devices", "<i4"), ("devices", "<i4", (MAX_DEVICES,)),
@@ -147,6 +154,12 @@ def lib():
             "bsw_cigar_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp]),
             "bsw_cigar_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_uint64)]),
             "bsw_matesw_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
+            "bsw_reads_upload": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp)]),
+            "bsw_reads_free": (C.c_int, [vp, vp]),
+            "bsw_reads_info": (C.c_int, [vp] + [C.POINTER(C.c_uint64)] * 3),
+            "bsw_submit_reads_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
+            "bsw_matesw_reads_submit_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
+            "bsw_cigar_reads_submit_t": (C.c_int, [vp, vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_uint64)]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -183,6 +196,7 @@ def lib():
 
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
+           "bsw_reads_upload", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
            "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
@@ -558,6 +572,55 @@ class BswContext:
                                                 C.byref(t)), "bsw_matesw_ref_submit")
         self._keep_alive(t.value, params, mtasks, res)
         return t.value, res
+
+    # resident read blocks: upload once, then the three stages name a read by index
+    def reads_upload(self, reads):
+        """bsw_reads_upload: `reads` is a sequence of uint8 arrays (codes 0..4).  Returns the block's handle; synchronous."""
+        reads = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+        ptrs = np.array([r.ctypes.data if len(r) else 0 for r in reads], dtype=np.uint64)
+        lens = np.array([len(r) for r in reads], dtype=np.int32)
+        h = C.c_void_p()
+        self._chk(lib().bsw_reads_upload(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(reads), C.byref(h)), "bsw_reads_upload")
+        return h
+
+    def reads_free(self, rd):
+        """bsw_reads_free; raises BswError(BSW_E_BUSY) while a ticket that uses the block has not been collected"""
+        self._chk(lib().bsw_reads_free(self.handle, rd), "bsw_reads_free")
+
+    @staticmethod
+    def reads_info(rd):
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = lib().bsw_reads_info(rd, C.byref(a), C.byref(b), C.byref(c))
+        if rc:
+            raise BswError(rc, "bsw_reads_info")
+        return {"n_reads": a.value, "bases": b.value, "device_bytes": c.value}
+
+    def submit_reads(self, params, ref, rd, rdtasks, out=None):
+        """submit_ref against a resident read block (bsw_submit_reads_t; RD_TASK records).  Returns the result array, filled
+        once the ticket (self.last_ticket) is collected."""
+        return self._submit(lib().bsw_submit_reads_t, "bsw_submit_reads", params, rdtasks, out, ref, rd)
+
+    def submit_matesw_reads(self, params, ref, rd, rdmtasks):
+        """submit_matesw_ref against a resident read block (RD_MTASK records).  Returns (ticket, MRESULT array)."""
+        res = np.zeros(len(rdmtasks), dtype=MRESULT)
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_matesw_reads_submit_t(self.handle, params.ctypes.data, ref, rd, rdmtasks.ctypes.data, len(rdmtasks),
+                                                  res.ctypes.data, C.byref(t)), "bsw_matesw_reads_submit")
+        self._keep_alive(t.value, params, rdmtasks, res)
+        return t.value, res
+
+    def submit_cigar_reads(self, params, ref, rd, rdctasks, max_cigar=64, max_md=256, want_cigar=True, want_md=True):
+        """submit_cigar_ref against a resident read block (RD_CTASK records).  Returns (ticket, CRESULT array, cigars, MD slots)."""
+        n = len(rdctasks)
+        res = np.zeros(n, dtype=CRESULT)
+        cig = np.zeros((n, max_cigar), dtype=np.uint32) if want_cigar else None
+        md = np.zeros((n, max_md), dtype=np.uint8) if want_md else None
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_cigar_reads_submit_t(self.handle, params.ctypes.data, ref, rd, rdctasks.ctypes.data, n, max_cigar,
+                                                 cig.ctypes.data if want_cigar else None, max_md,
+                                                 md.ctypes.data if want_md else None, res.ctypes.data, C.byref(t)), "bsw_cigar_reads_submit")
+        self._keep_alive(t.value, params, rdctasks, res, cig, md)
+        return t.value, res, cig, md
 
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""

@@ -33,6 +33,8 @@
  *                              reference (bwa host software, not the RTL)
  *   bsw_cigar_ref_submit_t /   the two calls above as tickets of the streaming pipeline:
  *   bsw_matesw_ref_submit_t    every device of the context, beside extension submits
+ *   bsw_reads_upload,          a read block resident on every device; the three stages as tickets that name a
+ *   bsw_*_reads_submit_t       read by its index (only coordinates cross PCIe)
  *
  * Base codes: 0..3 = A,C,G,T; 4 = N; one base per byte, exactly as bwa passes
  * them to ksw_extend.  Left-extension query/target must already be reversed by
@@ -239,10 +241,13 @@ int      bsw_host_unregister(void *p);
  * submit order, so the tail of one overlaps the head of the next.  One more than that answers BSW_E_BUSY.
  * bsw_wait waits for ALL of them and returns the first failure in submit order.
  *
- * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, bsw_wait_ticket,
- * bsw_test, bsw_wait and bsw_inflight may be called
+ * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, the three
+ * *_reads_* submits, bsw_reads_upload, bsw_reads_free, bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called
  * on ONE context from several threads at once, the first submit included; every other call that takes the context
  * (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free, bsw_host_stats) needs it to itself.
+ *   - bsw_reads_upload and bsw_reads_free may run while tickets are in flight (block k+1 is uploaded while block k is on the GPU):
+ *     the upload copies on a stream of its own per device and returns when the copies are complete; a block is handed to a
+ *     submit only after its upload has returned, and freed only by one thread.
  *   - A ticket belongs to whoever collects it first.  bsw_wait collects every submit in flight when it is called, other threads'
  *     too; a thread blocked in bsw_wait_ticket on a ticket that bsw_wait (or a second bsw_wait_ticket) collects meanwhile returns
  *     BSW_E_INVAL once that submit is complete: its results are in out[], its error code went to the collector.
@@ -573,6 +578,62 @@ int      bsw_submit_ref(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, c
 int      bsw_submit_ref_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ref_task *tasks, size_t n, bsw_result *out, bsw_ticket *ticket);
 /* convenience: upload_ref + run + download + free (synchronous) */
 int      bsw_extend_ref(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ref_task *tasks, size_t n, bsw_result *out);
+
+/* ---- RESIDENT READ BLOCKS: the reads of a block are uploaded once and the three Smith-Waterman stages name a read by its
+ * index, so that only coordinates cross PCIe: seed extension (bsw_submit_reads_t), mate rescue (bsw_matesw_reads_submit_t) and
+ * CIGAR generation (bsw_cigar_reads_submit_t) against the resident reference AND the resident reads.  The pointer forms send the
+ * same read up to three times (whole, as a mate per rescue task, as &query[qb] slices) and look at every sequence pointer of a
+ * chunk on the host (span, registration, gather); these forms send 76 - 112 bytes of records per task whatever the read length.
+ * bsw_pack_kernel takes the query words out of the 4-bit store (a funnel shift over two words, backwards for the left flank and
+ * the reverse-strand CIGAR read); every kernel behind it reads the same `seq` as before. ---- */
+typedef struct bsw_reads bsw_reads;
+/* reads[i]: lens[i] bases, codes 0..4 (larger codes stored as 4), any host memory.  A 4-bit packed copy (the device sequence
+ * format, every read on a word boundary, zeroed slack words in front and behind) is placed on every device of the context, as
+ * bsw_ref_upload does for the reference.  Synchronous: the copies are complete and reads[] may be freed when it returns; it
+ * copies on a stream of its own per device, so it neither waits for nor holds up tickets in flight.
+ * BSW_E_INVAL: lens[i] < 0, a NULL read of non-zero length; BSW_E_LIMIT: lens[i] > 65 535, or a block whose base positions do
+ * not fit 32 bits (more than 2^28 - 2^13 packed words = ~4.29 G bases of word-aligned reads).  A failed upload leaves no copy on
+ * any device.  n_reads == 0 is a valid, empty block. */
+int      bsw_reads_upload(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out);
+/* BSW_E_BUSY while a ticket that has not been collected uses rd (nothing is freed then); BSW_E_INVAL for a block of another
+ * context.  rd == NULL is BSW_OK. */
+int      bsw_reads_free(bsw_ctx *ctx, bsw_reads *rd);
+/* reads, bases, and the bytes ONE device copy holds (slack included); any pointer may be NULL */
+int      bsw_reads_info(const bsw_reads *rd, uint64_t *n_reads, uint64_t *bases, uint64_t *device_bytes);
+
+typedef struct bsw_rd_task {         /* bsw_ref_task with query = reads[read], l_query = lens[read] */
+    uint32_t read;
+    int32_t  init_score;
+    bsw_seed seed;
+    int64_t  rmax0, rmax1;
+    uint32_t tag, _pad;
+} bsw_rd_task;                       /* 48 bytes */
+typedef struct bsw_rd_mtask {        /* bsw_mtask with mate = reads[read], l_ms = lens[read] */
+    uint32_t read;
+    int32_t  is_rev;
+    int64_t  rb, re;
+    int32_t  xtra, min_score;
+} bsw_rd_mtask;                      /* 32 bytes */
+typedef struct bsw_rd_ctask {        /* bsw_ctask with query = reads[read] + qb, l_query = qe - qb */
+    uint32_t read;
+    int32_t  qb, qe, w;
+    int64_t  rb, re;
+    int32_t  w_cap, min_score, max_tries, _pad;
+} bsw_rd_ctask;                      /* 48 bytes */
+/* Tickets of the context's pipeline under the contract of bsw_cigar_ref_submit_t (one ticket space, BSW_MAX_INFLIGHT, chunk k on
+ * device k mod n_devices against that device's copies of the reference and of the reads).  Results are, byte for byte, those of
+ * bsw_submit_ref_t (BSW_RESULT_PAIR included) / bsw_matesw_ref_submit_t / bsw_cigar_ref_submit_t for the same read bytes.
+ * ALL checks run in the caller's thread before anything is queued, and no ticket is made when one fails: the pointer form's
+ * checks with its codes and texts (for extension also those the pointer form reports from the wait), read >= n_reads ->
+ * BSW_E_INVAL, a CIGAR task with qb < 0, qe < qb or qe > lens[read] -> BSW_E_INVAL, a block uploaded through another context ->
+ * BSW_E_INVAL.  tasks[] and the result arrays stay valid, and rd stays allocated, until the ticket is collected. */
+int      bsw_submit_reads_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_task *tasks,
+                            size_t n, bsw_result *out, bsw_ticket *ticket);
+int      bsw_matesw_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd,
+                                   const bsw_rd_mtask *tasks, size_t n, bsw_mresult *res, bsw_ticket *ticket);
+int      bsw_cigar_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd,
+                                  const bsw_rd_ctask *tasks, size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md,
+                                  bsw_cresult *res, bsw_ticket *ticket);
 
 /* ---- device sequence format: 4 bits per base, 16 bases per uint64, base k of a word in bits [4k,4k+3];
  * codes > 4 are stored as 4 (N).  words must hold (len+15)/16 entries.  Returns 1 if an N was seen. ---- */

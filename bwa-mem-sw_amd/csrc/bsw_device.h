@@ -57,6 +57,14 @@ typedef struct bsw_dparams {
     int32_t w, pen_clip5, pen_clip3, zdrop, max_band_try;
 } bsw_dparams;
 
+/* what the packed two-seeds-per-lane formulation (bsw_lane2_core.h) needs from the scoring parameters, whatever the variant:
+ * a bwa-style matrix and penalties that fit the 8 score bits */
+static inline int lane2_range_ok(const bsw_dparams &P)
+{
+    const int a = P.mat[0], pb = -P.mat[1], pn = -P.mat[24];
+    return a > 0 && pb >= 0 && pn >= 0 && pb >= pn && a + pb < 256 && P.o_del + P.e_del < 256 && P.o_ins + P.e_ins < 256;
+}
+
 /* where a seed's two targets start in the device-resident 2-bit reference, in bwa's [0, 2*l_pac) coordinates
  * (bsw_pack_kernel fetches them: ltlen bases downwards from xl, rtlen bases upwards from xr) */
 typedef struct bsw_refx {

@@ -310,9 +310,9 @@ L2_FN void row_begin2(pairv &p, const int i, rowp &r)
  *   Fnz half = the same key of the LOWEST such block, minus 1; 0xffff: none.
  * (:1829-1833 gscore / max_ie, ties -> later i; :1959,1810,1845 new maximum; zdrop; :1942 m == 0; K8: CPU semantics of
  * SURVEY.md §8a, quirk Q5 avoided.) */
+/* K7 alone (the variants share it): updates max / max_i / max_j / max_off / gscore / max_ie and returns the halves that stop */
 template <bool SYM>
-L2_FN void row_tail2(pairv &p, const consts &k, const int i, const uint32_t act, const uint32_t h1, const uint32_t mk2,
-                     const uint32_t Fnz, const uint32_t Lnz)
+L2_FN uint32_t row_tail_k7(pairv &p, const consts &k, const int i, const uint32_t act, const uint32_t h1, const uint32_t mk2)
 {
     const uint32_t I2 = dup16(i), IP1 = dup16(i + 1);
     const uint32_t H1P = pk_shr8(h1) + k.ONE2;                           /* eh[end].h + 1 (<= 256: no carry between the halves) */
@@ -340,6 +340,14 @@ L2_FN void row_tail2(pairv &p, const consts &k, const int i, const uint32_t act,
     p.MAXI1 = (gt & IP1) | (~gt & p.MAXI1);
     p.MAXJ1 = (gt & MJ1) | (~gt & p.MAXJ1);
     p.MX = (gt & M) | (~gt & p.MX);
+    return stop;
+}
+
+template <bool SYM>
+L2_FN void row_tail2(pairv &p, const consts &k, const int i, const uint32_t act, const uint32_t h1, const uint32_t mk2,
+                     const uint32_t Fnz, const uint32_t Lnz)
+{
+    const uint32_t stop = row_tail_k7<SYM>(p, k, i, act, h1, mk2);
     /* K8 next-row range: first / last non-zero eh entry in [beg, end] */
     const uint32_t nF = ~Fnz;                                            /* low byte of a half: ~(bits - 1): its trailing zeros = ctz(bits) */
     const uint32_t f0 = add_byte<1>(ffbl_byte<0>(nF), Fnz), f1 = add_byte<3>(ffbl_byte<2>(nF), Fnz);   /* j0 + ctz(bits); 254 when none */
@@ -1009,6 +1017,199 @@ struct lane2g {
     L2_MFN uint32_t hfin_of(const rowk &rk, const uint32_t reduced)
     {
         return bfi(pk_nzmask(rk.END2), reduced, rk.h1init);
+    }
+};
+
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * lane2r: variant RTL (BSW_VARIANT_RTL; tests/ksw_extend_rtl_ref.c) on the shell of lane2 — the same
+ * packed layout, first row, K3, K7 and cell arithmetic (variant H's); what changes is what a row may assume about eh[]:
+ *   K4  H(i, beg - 1) = max(h0 - (o_del + e_del (i + 1)), 0) on EVERY row, with f = 0 there.  The two seeds of a lane have
+ *       different beg, so the value enters each half at its own column: the chains hp (H(i, j-1)) and f are held at
+ *       {H1C, 0} in a half until its column beg has run.
+ *   K8  the next row is the run of non-zero eh[].h around mj (e is not looked at), and `end` may grow by one per row.  So
+ *       entries below beg and at or beyond end may hold non-zero h and e of earlier rows, and none of lane2's edge
+ *       invariants holds: a cell outside [beg, end) must not be stored and must not reach hp / f, the row-max key or the
+ *       K8 bits.  Blocks that lie inside [beg, end) of EVERY active seed of the wave (8b >= max beg, 8b + 8 <= min end) run
+ *       the mask-free body; the others the body with a left (J >= beg) and a right (J < end) mask per column.
+ *       K8 bits: bit J of a seed = "the entry stored at J this row has a non-zero h" — eh[J].h = H(i, J-1) for J in
+ *       [beg, end), eh[end].h = h1; never set outside [beg, end].  They are kept per 16-column chunk (both seeds per
+ *       register) and read after the row, when mj is known: beg' = 1 + the highest clear bit at or below mj (beg - 1 is
+ *       clear: "the row's beg when there is none"), end' = the lowest clear bit at or above mj + 2 (end + 1 is clear).
+ * Nothing relies on zeros below beg, so the columns a band clamp drops are left as they are (no zero_dropped). */
+struct unir : uni {
+    int jbm;                            /* max beg over the active seeds of the wave */
+};
+
+template <int QB, bool SYM = true>
+struct lane2r : lane2<QB, false, SYM> {
+    using B = lane2<QB, false, SYM>;
+    static constexpr int QMAX = B::QMAX, NW = B::NW, NC = B::NC, NG = B::NG;
+    static constexpr int NZW = (NC + 1) / 2;        /* 32-column words of K8 bits per seed */
+    using state = typename B::state;
+
+    /* One cell of column J for both seeds: lane2::cell's arithmetic (variant H).  !EDGE: J lies inside [beg, end) of every
+     * active seed and so does J - 1 or it is beg - 1 (hp / f enter as the chain left them).  EDGE: BEGr / ENDr = beg / end
+     * relative to the block (saturated at 0), r_prev = the right mask of column J - 1 (0xffff where J <= end: the
+     * column takes a store), H1C = K4's value scaled.  h1 = the last H inside [beg, end) (H1C when the range is empty). */
+    template <int J, bool EDGE, bool NQ>
+    L2_MFN void cell(uint32_t &P, const uint32_t Wc8, const uint32_t WNc, const uint32_t Bv2s, const uint32_t D2s, const consts &k,
+                     const uint32_t BEGr, const uint32_t ENDr, const uint32_t H1C, uint32_t &r_prev, uint32_t &hp, uint32_t &h1,
+                     uint32_t &f, uint32_t &mk, uint32_t &nz)
+    {
+        constexpr int C = J & 7;
+        constexpr uint32_t JJ = (uint32_t)C * 0x00010001u;
+        constexpr uint32_t BIT = (uint32_t)(1u << C) * 0x00010001u;
+        const uint32_t t = Wc8 & BIT;
+        const uint32_t hd = pk_shl8(P);                      /* eh[j].h = H(i-1,j-1), scaled */
+        const uint32_t e = P;                                /* eh[j].e in the high byte */
+        uint32_t X = pk_mad_vsv(t, k.MC[C], hd);
+        if (NQ) {
+            uint32_t n = (J & 15) ? (WNc >> (J & 15)) : WNc;
+            n &= 0x00010001u;
+            X = pk_mad(n, D2s, X);
+        }
+        const uint32_t M = pk_subs(X, Bv2s);
+        const uint32_t h = pk_max(pk_max(M, e), f);
+        const uint32_t tD = pk_subs_vs(h, k.OED2s);
+        const uint32_t tI = SYM ? tD : pk_subs_vs(h, k.OEI2s);
+        const uint32_t en = pk_max(pk_subs_vs(e, k.ED2s), tD);
+        const uint32_t fn = pk_max(pk_subs_vs(f, SYM ? k.ED2s : k.EI2s), tI);
+        const uint32_t hb = pk_min_vs(pk_shr8(hp), k.ONE2);  /* 1 where the h this column stores, H(i, j-1), is non-zero */
+        if (!EDGE) {
+            const uint32_t key = and_or_vvs(h, k.HI2, JJ);   /* ties -> later j */
+            mk = C ? pk_max(mk, key) : key;
+            nz = C ? pk_mad_vsv(hb, BIT, nz) : hb;
+            P = pack_hi_bytes(en, hp);
+            hp = h;
+            f = fn;
+        } else {
+            const uint32_t Lm = pk_nzmask(pk_subs_sv(dup16(C + 1), BEGr));   /* J >= beg */
+            const uint32_t Rm = pk_nzmask(pk_subs_vs(ENDr, dup16(C)));       /* J < end */
+            const uint32_t in = Lm & Rm;
+            h1 = bfi(in, h, h1);
+            const uint32_t key = and_or_vvs(h, in & k.HI2, JJ);              /* a cell outside the range: score 0 */
+            mk = C ? pk_max(mk, key) : key;
+            const uint32_t st = Lm & r_prev;                                 /* beg <= J <= end: stored, {0, h1} at end */
+            const uint32_t sb = hb & st;
+            nz = C ? pk_mad_vsv(sb, BIT, nz) : sb;
+            P = bfi(st, pack_hi_bytes(en & Rm, hp), P);
+            hp = bfi(Lm, h, H1C);                                            /* below beg the chains stay at K4's {H1C, 0} */
+            f = fn & Lm;
+            r_prev = Rm;
+        }
+    }
+
+    template <bool EDGE, bool NQ>
+    L2_MFN void block8(uint32_t (&T)[8], const uint32_t Wc, const uint32_t WN, const uint32_t Bv2s, const uint32_t D2s, const consts &k,
+                       const uint32_t BEGr, const uint32_t ENDr, const uint32_t H1C, const uint32_t r_in, uint32_t &hp, uint32_t &h1,
+                       uint32_t &f, uint32_t &mk, uint32_t &nz)
+    {
+        uint32_t r_prev = r_in;
+        sfor<8>([&](auto ci) { cell<decltype(ci)::value, EDGE, NQ>(T[decltype(ci)::value], Wc, WN, Bv2s, D2s, k, BEGr, ENDr, H1C, r_prev, hp, h1, f, mk, nz); });
+        if (!EDGE) h1 = hp;
+    }
+
+    /* K8 for one seed: W = its bits (bit J of word J >> 5), mj = the column of the row maximum.  lo = the highest clear bit
+     * <= mj (-1: none), hi = the lowest clear bit >= mj + 2 (one exists: bit end + 1 <= QMAX is never set). */
+    L2_MFN void run_around(const uint32_t (&W)[NZW], const int mj, int &lo, int &hi)
+    {
+        lo = -1; hi = 32 * NZW;
+        sfor<NZW>([&](auto wi) {
+            constexpr int wu = decltype(wi)::value, wd = NZW - 1 - wu;     /* lo walks the words upwards, hi downwards */
+            const int dl = mj - 32 * wu, dh = mj + 2 - 32 * wd;
+            const uint32_t zu = ~W[wu], zd = ~W[wd];
+            const uint32_t zl = dl < 0 ? 0u : (dl >= 31 ? zu : (zu & ((2u << (dl & 31)) - 1u)));
+            const uint32_t zh = dh > 31 ? 0u : (dh <= 0 ? zd : (zd & ~((1u << (dh & 31)) - 1u)));
+            lo = zl ? 32 * wu + 31 - (int)ffbh(zl) : lo;
+            hi = zh ? 32 * wd + (int)ffbl(zh) : hi;
+        });
+    }
+
+    /* One DP row for both seeds (lane2::row_body's interface; u.jbm next to jlo / jhi / jem). */
+    template <class QP, class KP, class WN>
+    L2_MFN void row_body(state &S, const consts &k, const int i, const rowp &r, const unir &u, const int (&tb)[2],
+                         const QP &qp, const KP &kp, const WN &wn)
+    {
+        pairv &p = S.p;
+        uint32_t rmA[NW], rmB[NW];
+        B::match_words(qp, kp, 0, tb[0], 0, rmA);           /* (cells below beg are masked: their match bits may stay) */
+        B::match_words(qp, kp, 1, tb[1], 0, rmB);
+        const int pbA = tb[0] < 4 ? k.pb : k.pn, pbB = tb[1] < 4 ? k.pb : k.pn;
+        const uint32_t Bv2 = pack2(pbA, pbB) << 8, D2 = pack2(pbA - k.pn, pbB - k.pn) << 8;
+        const uint32_t BEG2 = p.BEG, END2 = p.END;
+        /* K4 on every row: h0 - (o_del + e_del (i + 1)), both seeds at once, scaled */
+        const uint32_t H1C = pk_shl8(pk_subs_vs(p.H0, dup16(imin(k.o_del + k.e_del * (i + 1), 0xffff))));
+        uint32_t hp = H1C, h1 = H1C, f = 0;
+        L2_STAMP(2);
+        uint32_t mkg[NG], NZc[NC];
+        sfor<NG>([&](auto gi) { mkg[decltype(gi)::value] = 0; });
+        sfor<NC>([&](auto ci) { NZc[decltype(ci)::value] = 0; });
+
+        const int blo = u.jlo >> 3, bhi = u.jhi >> 3, bdl = (u.jbm + 7) >> 3, bem = u.jem >> 3;
+        const uint32_t nblk = opaque_s(u.nblk);
+        const uint32_t ALLB = (1u << QB) - 1u;
+        const uint32_t m_run = ALLB & ~((1u << imin(blo, 31)) - 1u) & ((2u << imin(bhi, 30)) - 1u);               /* blo <= b <= bhi */
+        const uint32_t m_in = m_run & ~((1u << imin(bdl, 31)) - 1u) & ((1u << imin(imax(bem, 0), 31)) - 1u);      /* inside every seed's range */
+        const uint32_t m_dense = opaque_u(m_in & ~nblk), m_edge = opaque_u(m_run & ~m_in & ~nblk);
+        const uint32_t m_dnq = opaque_u(m_in & nblk), m_enq = opaque_u(m_run & ~m_in & nblk);
+        const uint32_t m_any = opaque_u(m_run), m_cold = opaque_u(m_run & nblk);
+        sfor<QB>([&](auto bi) {
+            constexpr int b = decltype(bi)::value, j0 = b * 8, g = j0 >> 6, c = j0 >> 4, wd = j0 >> 5;
+            if (!((m_any >> b) & 1u)) return;                 /* j0 + 8 <= jlo or j0 > jhi */
+            const uint32_t Wc = byte_pair<b & 3>(rmA[wd], rmB[wd]);
+            uint32_t mkb = 0, nz8 = 0;
+            const auto run8 = [&](auto edge, auto nqv, const uint32_t WNc) {
+                constexpr bool EDGE = decltype(edge)::value;
+                uint32_t BEGr = 0, ENDr = 0, r_in = 0;
+                if (EDGE) {
+                    BEGr = pk_subs_vs(BEG2, dup16(j0));
+                    ENDr = pk_subs_vs(END2, dup16(j0));
+                    r_in = pk_nzmask(pk_subs_vs(END2 + 0x00010001u, dup16(j0)));      /* the right mask of column j0 - 1 */
+                }
+                uint32_t T[8];
+                sfor<8>([&](auto ci) { T[decltype(ci)::value] = S.Pr[j0 + decltype(ci)::value]; });
+                block8<EDGE, decltype(nqv)::value>(T, Wc, WNc, Bv2, D2, k, BEGr, ENDr, H1C, r_in, hp, h1, f, mkb, nz8);
+                sfor<8>([&](auto ci) { S.Pr[j0 + decltype(ci)::value] = T[decltype(ci)::value]; });
+            };
+            using no_t = std::integral_constant<bool, false>;
+            using yes_t = std::integral_constant<bool, true>;
+            /* mutually exclusive bodies as consecutive `if`s (lane2::row_body) */
+            if ((m_dense >> b) & 1u) run8(no_t{}, no_t{}, 0u);
+            if (__builtin_expect((m_cold >> b) & 1u, 0)) {
+                if ((m_dnq >> b) & 1u) { const uint32_t WNr = wn(c); run8(no_t{}, yes_t{}, (b & 1) ? (WNr >> 8) : WNr); }
+                if ((m_enq >> b) & 1u) { const uint32_t WNr = wn(c); run8(yes_t{}, yes_t{}, (b & 1) ? (WNr >> 8) : WNr); }
+            }
+            if ((m_edge >> b) & 1u) run8(yes_t{}, no_t{}, 0u);
+            mkg[g] = pk_max(mkg[g], mkb + (uint32_t)(j0 & 63) * 0x00010001u);
+            NZc[c] |= (b & 1) ? (nz8 << 8) : nz8;
+        });
+
+        L2_STAMP(3);
+        uint32_t mk2 = mkg[0];
+        sfor<NG - 1>([&](auto gi) {
+            constexpr int g = decltype(gi)::value + 1;
+            mk2 = pk_max(mk2, mkg[g] + (uint32_t)(64 * g) * 0x00010001u);
+        });
+        /* ---- row tail: K7 as in lane2, K8 per seed from the bits ---- */
+        const uint32_t stop = row_tail_k7<SYM>(p, k, i, r.ACT, h1, mk2);
+        uint32_t WA[NZW], WB[NZW];
+        sfor<NZW>([&](auto wi) {
+            constexpr int w = decltype(wi)::value;
+            const uint32_t c0 = NZc[2 * w];
+            uint32_t c1 = 0;
+            if constexpr (2 * w + 1 < NC) c1 = NZc[2 * w + 1];
+            WA[w] = half_pair<0>(c0, c1);
+            WB[w] = half_pair<1>(c0, c1);
+        });
+        int lo0, hi0, lo1, hi1;
+        run_around(WA, (int)(mk2 & 0xffu), lo0, hi0);
+        run_around(WB, (int)((mk2 >> 16) & 0xffu), lo1, hi1);
+        const uint32_t nbeg = pack2(lo0 + 1, lo1 + 1), nend = pack2(hi0, hi1);      /* (row_begin2 clamps end to qlen) */
+        const uint32_t act = r.ACT;
+        p.BEG = (act & nbeg) | (~act & p.BEG);
+        p.END = (act & nend) | (~act & p.END);
+        p.ALIVE = (act & ~stop) | (~act & p.ALIVE);
     }
 };
 

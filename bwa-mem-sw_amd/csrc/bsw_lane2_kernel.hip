@@ -9,6 +9,12 @@
  * model of the tests); this file is the wave-level glue: operand staging through LDS, the wave-uniform block
  * dispatch, result records.  As in bsw_lane_kernel.hip only the first band try runs here; bsw_pair_finalize
  * sends seeds that need MAX_BAND_TRY's second pass to the wave-per-task kernel.
+ *
+ * Compiled a second time with -DBSW_L2_RTL_TU (Makefile) into the companion library libbwasw_mi355_rtl2.so: the same shell
+ * — slot pair per lane, stand-in for empty slots, match words and N planes in LDS, target staging, row_begin2, pair_result —
+ * around the variant-RTL row (l2::lane2r), as bsw_lane2_rtl_kernel<QB, WPS, SYM> for the 72- and the 136-column class.  That
+ * unit holds nothing else: the kernel set of the main library stays what it is (bsw_quad_rtl.o is the precedent), and its
+ * block bodies come from the C++ cell(), not from bsw_lane2_body_asm.inc.
  */
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -80,6 +86,17 @@ __device__ __forceinline__ uint32_t nib_plane(uint64_t w, int b)
 
 #define BSW_L2_TCHUNK 4         /* target words staged per seed in LDS = 64 DP rows */
 
+#ifdef BSW_L2_RTL_TU
+template <int QB, int WPS, bool SYM>
+__global__ __launch_bounds__(256, WPS) void bsw_lane2_rtl_kernel(const bsw_dparams P, const int side_arg,
+                                                                 const uint64_t *__restrict__ seq,
+                                                                 const bsw_dtask *__restrict__ tasks,
+                                                                 const uint32_t *__restrict__ order, const uint32_t n,
+                                                                 bsw_result *__restrict__ out, uint32_t *tail_flag, const bsw_fin fin)
+{
+    constexpr bool FUSED = false;
+    using L = l2::lane2r<QB, SYM>;
+#else
 template <int QB, int WPS, bool VM, bool SYM, bool FUSED>
 __global__ __launch_bounds__(256, WPS) void bsw_lane2_kernel(const bsw_dparams P, const int side_arg,
                                                              const uint64_t *__restrict__ seq,
@@ -87,10 +104,11 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane2_kernel(const bsw_dparams P
                                                              const uint32_t *__restrict__ order, const uint32_t n,
                                                              bsw_result *__restrict__ out, uint32_t *tail_flag, const bsw_fin fin)
 {
+    using L = l2::lane2<QB, VM, SYM>;
+#endif
     /* *tail_flag counts the workgroups that have a slot (bsw_lane2l_kernel.hip): the next launch of the
      * chunk's chain is released when the count reaches the grid size */
     if (tail_flag && threadIdx.x == 0) __hip_atomic_fetch_add(tail_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    using L = l2::lane2<QB, VM, SYM>;
     constexpr int QMAX = L::QMAX, NW = L::NW, NC = L::NC;
     static_assert(QMAX <= BSW_LANE_QBINS && QMAX <= 256, "row-max key and binning assume at most 256 eh[] columns");
     __shared__ uint64_t lds_t[4][2][BSW_L2_TCHUNK][64];             /* [wave][seed][word][lane] */
@@ -251,7 +269,12 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane2_kernel(const bsw_dparams P
 
         /* wave-uniform column ranges over the active seeds: blocks outside [jlo, jhi] are skipped, blocks that
          * reach past jem (the smallest `end`) run the masked body */
+#ifdef BSW_L2_RTL_TU
+        l2::unir u;
+        u.jbm = wave_max2((int)l2::max_halves(S.p.BEG & r.ACT));      /* the largest beg: blocks below it hold some seed's left edge */
+#else
         l2::uni u;
+#endif
         {
             /* min beg, max end, min end over the ACTIVE seeds: an inactive half reads 0xffff for the minima, 0 for the maximum */
             const uint32_t nact = ~r.ACT;
@@ -259,8 +282,11 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane2_kernel(const bsw_dparams P
             wave_min_max_min(ra, rb, rc);
             u.jlo = (int)ra; u.jhi = (int)rb; u.jem = (int)rc;
         }
-        u.anybite = __builtin_amdgcn_ballot_w64(r.BITE != 0) != 0;
+        u.anybite = false;
         u.zl = 0; u.zh = 0;
+#ifndef BSW_L2_RTL_TU                                                 /* (variant RTL keeps no zeros below beg: nothing to clear) */
+        u.anybite = __builtin_amdgcn_ballot_w64(r.BITE != 0) != 0;
+#endif
         if (__builtin_expect(u.anybite, 0)) {
             const bool bt0 = (r.BITE & 0xffffu) != 0, bt1 = (r.BITE >> 16) != 0;
             u.zl = -wave_max2(max(bt0 ? -l2::half_of(r.ZLO, 0) : INT_MIN, bt1 ? -l2::half_of(r.ZLO, 1) : INT_MIN));
@@ -313,6 +339,7 @@ __global__ __launch_bounds__(256, WPS) void bsw_lane2_kernel(const bsw_dparams P
     else run_side(side_arg);
 }
 
+#ifndef BSW_L2_RTL_TU
 /* what the packed formulation needs from the scoring parameters (everything else takes bsw_lane_kernel): a bwa-style
  * matrix and penalties that fit the 8 score bits.  Both recurrence variants and separate deletion / insertion penalties
  * (the RTL's four-penalty datapath, sw_pe_array_proc_element.v:816-819) run here. */
@@ -320,8 +347,7 @@ bool lane2_params_ok(const bsw_dparams &P, int variant)
 {
     static const bool off = getenv("BSW_NO_LANE2") != nullptr;
     if (off || (variant != BSW_VARIANT_H && variant != BSW_VARIANT_M)) return false;
-    const int a = P.mat[0], pb = -P.mat[1], pn = -P.mat[24];
-    return a > 0 && pb >= 0 && pn >= 0 && pb >= pn && a + pb < 256 && P.o_del + P.e_del < 256 && P.o_ins + P.e_ins < 256;
+    return lane2_range_ok(P);
 }
 
 hipError_t launch_lane2(int qb, const bsw_dparams &P, int variant, int side, const uint64_t *seq, const bsw_dtask *tasks, const uint32_t *order,
@@ -350,5 +376,38 @@ hipError_t launch_lane2(int qb, const bsw_dparams &P, int variant, int side, con
 #undef BSW_L2_GO
     return hipGetLastError();
 }
+#else
+/* Variant RTL on the packed kernels (the opt-in of bsw_set_rtl_packed: launch_lane_k in bsw_lane_kernel.hip).  One side of the
+ * seeds of a lane list, first band try; the side's bsw_ext record is written as bsw_lane_kernel writes it and the seed is
+ * finished by bsw_pair_finalize, so no bsw_fin and no tail flag are taken.  Returns the index of the instantiation that ran
+ * in *which: 72 columns shared / separate penalties, 136 columns shared / separate.
+ * Occupancy: the RTL row carries the K8 bits, K4's value and a second mask per edge column on top of
+ * variant H's working set. */
+#ifndef BSW_L2R_WPS9
+#define BSW_L2R_WPS9 3
+#endif
+#ifndef BSW_L2R_WPS17
+#define BSW_L2R_WPS17 2
+#endif
+hipError_t launch_lane2_rtl(int qb, const bsw_dparams &P, int side, const uint64_t *seq, const bsw_dtask *tasks, const uint32_t *order,
+                            uint32_t n, bsw_result *out, hipStream_t s, int *which)
+{
+    if (qb != 9 && qb != 17) return hipErrorInvalidValue;
+    const bool sym = P.o_del == P.o_ins && P.e_del == P.e_ins;
+    if (which) *which = (qb == 9 ? 0 : 2) + (sym ? 0 : 1);
+    if (n == 0) return hipSuccess;
+    bsw_fin fin;
+    fin.redo = fin.redo_cnt = nullptr; fin.pairs = nullptr; fin.on = 0; fin.group = 0;
+    const dim3 grid((n + 511u) / 512u), block(256);
+    if (qb == 9) {
+        if (sym) hipLaunchKernelGGL((bsw_lane2_rtl_kernel<9, BSW_L2R_WPS9, true>), grid, block, 0, s, P, side, seq, tasks, order, n, out, (uint32_t *)nullptr, fin);
+        else hipLaunchKernelGGL((bsw_lane2_rtl_kernel<9, BSW_L2R_WPS9, false>), grid, block, 0, s, P, side, seq, tasks, order, n, out, (uint32_t *)nullptr, fin);
+    } else {
+        if (sym) hipLaunchKernelGGL((bsw_lane2_rtl_kernel<17, BSW_L2R_WPS17, true>), grid, block, 0, s, P, side, seq, tasks, order, n, out, (uint32_t *)nullptr, fin);
+        else hipLaunchKernelGGL((bsw_lane2_rtl_kernel<17, BSW_L2R_WPS17, false>), grid, block, 0, s, P, side, seq, tasks, order, n, out, (uint32_t *)nullptr, fin);
+    }
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace bsw

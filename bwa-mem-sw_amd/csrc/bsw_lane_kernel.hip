@@ -21,6 +21,7 @@
  * every pair that involves an N), qlen < 8*QB, score range as above.
  */
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <limits.h>
 #include <stdint.h>
 #include <utility>
@@ -476,6 +477,20 @@ hipError_t launch_lane2g(int cols, const bsw_dparams &P, int variant, int side, 
 static hipError_t launch_lane_k(int cls, int variant, const bsw_dparams &P, int side, const uint64_t *seq, const bsw_dtask *tasks,
                                 const uint32_t *order, uint32_t n, bsw_result *out, hipStream_t s, uint32_t *&tail_flag, uint32_t *tail_target, const bsw_fin *fin);
 
+/* ---- variant RTL on the packed kernels: a process-wide opt-in (bsw_set_rtl_packed, BSW_RTL_PACKED=1) ----
+ * bsw_lane2_rtl_kernel lives in the companion library libbwasw_mi355_rtl2.so (bsw_lane2_kernel.hip compiled with
+ * -DBSW_L2_RTL_TU).  The route sits below launch_lane: lane2_params_ok(P, RTL) stays false, so the fused launches, the group
+ * kernel, lane_class_finishes, the N-list policy and the launch-count planning see RTL as before, and with the switch off
+ * every launch is the one it was. */
+hipError_t launch_lane2_rtl(int qb, const bsw_dparams &P, int side, const uint64_t *seq, const bsw_dtask *tasks, const uint32_t *order,
+                            uint32_t n, bsw_result *out, hipStream_t s, int *which);
+static std::atomic<int> &rtl_packed_switch()
+{
+    static std::atomic<int> on([] { const char *e = getenv("BSW_RTL_PACKED"); return (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }());
+    return on;
+}
+static std::atomic<uint64_t> g_rtl_packed_launches[4];      /* 72 columns shared / separate penalties, 136 shared / separate */
+
 /* which kernel serves the class under these parameters: 2 = bsw_lane2_kernel, 3 = bsw_lane2l_kernel, 1 = round 1's
  * one-seed-per-lane kernel (16-bit rows, N scores outside the packed range, gap penalties >= 256) */
 static int lane_kernel_of(int cls, const bsw_dparams &P, int variant)
@@ -517,6 +532,14 @@ static hipError_t launch_lane_k(int cls, int variant, const bsw_dparams &P, int 
     int ncls;
     const lane_class_t &C = lane_classes(&ncls)[cls];
     const int kern = lane_kernel_of(cls, P, variant);
+    if (variant == BSW_VARIANT_RTL && (C.kind == K_LANE2_9 || C.kind == K_LANE2_17) && lane2_range_ok(P) &&
+        rtl_packed_switch().load(std::memory_order_relaxed) != 0) {
+        /* (takes neither the tail flag nor a bsw_fin: launch_lane raises the flag behind it, bsw_pair_finalize follows) */
+        int which = 0;
+        const hipError_t e = launch_lane2_rtl(C.qb, P, side, seq, tasks, order, n, out, s, &which);
+        if (e == hipSuccess) g_rtl_packed_launches[which].fetch_add(1, std::memory_order_relaxed);
+        return e;
+    }
     if (kern != 1 && fin && fin->group)                               /* (does not signal its tail: launch_lane raises the flag behind it) */
         return launch_lane2g(C.qb * 8, P, variant, side, seq, tasks, order, n, out, s, fin);
     if (kern != 1) {
@@ -532,6 +555,18 @@ static hipError_t launch_lane_k(int cls, int variant, const bsw_dparams &P, int 
     default: return launch_lane_c2(variant, sym, P, side, seq, tasks, order, n, out, s);
     }
 }
+
+}  // namespace bsw
+extern "C" {
+void bsw_set_rtl_packed(int on) { bsw::rtl_packed_switch().store(on ? 1 : 0, std::memory_order_relaxed); }
+int bsw_rtl_packed(void) { return bsw::rtl_packed_switch().load(std::memory_order_relaxed); }
+int bsw_rtl_packed_stats(uint64_t *launches, int cap)
+{
+    for (int q = 0; q < 4 && q < cap && launches; ++q) launches[q] = bsw::g_rtl_packed_launches[q].load(std::memory_order_relaxed);
+    return 4;
+}
+}
+namespace bsw {
 
 hipError_t launch_finalize(const bsw_dparams &P, const bsw_dtask *tasks, const uint32_t *order, uint32_t n,
                            bsw_result *out, uint32_t *redo, uint32_t *redo_cnt, bsw_pair *pairs, hipStream_t s)

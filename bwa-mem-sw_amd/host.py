@@ -149,6 +149,9 @@ def lib():
             "bsw_host_register": (C.c_int, [vp, sz]), "bsw_host_unregister": (C.c_int, [vp]),
             "bsw_batch_order": (C.c_int, [vp, vp, vp, vp]),
             "bsw_scalar_stats": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+            "bsw_set_rtl_packed": (None, [C.c_int]),
+            "bsw_rtl_packed": (C.c_int, []),
+            "bsw_rtl_packed_stats": (C.c_int, [C.c_void_p, C.c_int]),
             "bsw_global_batch": (C.c_int, [vp, vp, vp, sz, C.c_int, vp, vp]),
             "bsw_align_batch": (C.c_int, [vp, vp, vp, sz, vp]),
             "bsw_cigar_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp]),
@@ -197,7 +200,7 @@ def lib():
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
            "bsw_reads_upload", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
-           "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_host_alloc", "bsw_host_free",
+           "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
            "bsw_submit_packed", "bsw_upload_packed", "bsw_pack_tasks", "bsw_pack_tasks_bound",
@@ -710,6 +713,23 @@ def scalar_stats():
     a, b = C.c_uint64(0), C.c_uint64(0)
     lib().bsw_scalar_stats(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def set_rtl_packed(on):
+    """Process-wide opt-in: variant RTL's 72- and 136-column 8-bit lane classes on the packed two-seeds-per-lane kernel
+    (bsw_set_rtl_packed; initially BSW_RTL_PACKED=1).  Applies to launches enqueued afterwards."""
+    lib().bsw_set_rtl_packed(1 if on else 0)
+
+
+def rtl_packed():
+    return bool(lib().bsw_rtl_packed())
+
+
+def rtl_packed_stats():
+    """Launches of the packed RTL kernel so far: (72 columns shared penalties, 72 separate, 136 shared, 136 separate)."""
+    a = np.zeros(4, dtype=np.uint64)
+    assert lib().bsw_rtl_packed_stats(a.ctypes.data, 4) == 4
+    return tuple(int(x) for x in a)
 
 
 def refbatch_encode(params, tasks):

@@ -204,6 +204,19 @@ void bsw_set_default_variant(int variant);
 /* calls served / device round trips made by the scalar ABI so far (their ratio = mean coalescing factor) */
 void bsw_scalar_stats(uint64_t *calls, uint64_t *trips);
 
+/* ---- BSW_VARIANT_RTL on the packed two-seeds-per-lane kernels (opt-in) ----
+ * Process-wide and atomic; applies to the launches enqueued afterwards.  Initially 1 when the environment variable
+ * BSW_RTL_PACKED is "1", else 0.  With the switch on, the lane-list sides of variant RTL whose class is the 72- or the
+ * 136-column 8-bit class, under scoring parameters in the packed range (a bwa-style matrix, a + b < 256, o + e < 256 per gap
+ * kind), run on bsw_lane2_rtl_kernel (libbwasw_mi355_rtl2.so) instead of the one-seed-per-lane kernel, through every entry
+ * point that builds lane lists; results are the same bytes.  The 232-column and the 16-bit class, parameters outside that
+ * range, and variants H and M are not affected. */
+void bsw_set_rtl_packed(int on);
+int  bsw_rtl_packed(void);
+/* launches of the packed RTL kernel so far, per instantiation: [0] 72 columns shared gap penalties (o_del == o_ins and
+ * e_del == e_ins), [1] 72 separate, [2] 136 shared, [3] 136 separate.  Writes min(cap, 4) counters, returns 4. */
+int  bsw_rtl_packed_stats(uint64_t *launches, int cap);
+
 /* ---- batch API ------------------------------------------------------------ */
 void     bsw_default_params(bsw_params *p);          /* bwa defaults a=1,b=4,o=6,e=1,w=100,clip=5,zdrop=100 */
 void     bsw_default_config(bsw_config *c);

@@ -5,7 +5,7 @@
  * `bwa --target=ASE|Direct mem -t N -b BATCH ...`) with bwa mem's scoring flags:
  *
  *   bsw-bench [--target=hip] [--gpus G | --devices 0,1,..] [-t gather_threads] [-b batch_seeds] [-n seeds] [-l read_len]
- *             [-A a] [-B b] [-O o[,o_ins]] [-E e[,e_ins]] [-L clip] [-w band] [-d zdrop] [--variant=H|M|RTL] [--reps R] [--pageable]
+ *             [-A a] [-B b] [-O o[,o_ins]] [-E e[,e_ins]] [-L clip] [-w band] [-d zdrop] [--variant=H|M|RTL] [--rtl-packed] [--reps R] [--pageable]
  *             [--packed] [--dump FILE | --load FILE]
  *
  * --target=cpu is refused: the library has no CPU path (the CPU oracle lives under oracle/ and is test-only).
@@ -105,6 +105,7 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(f, "--dump")) dump = v, ++k; else if (!strcmp(f, "--load")) load = v, ++k;
         else if (!strcmp(f, "--pageable")) pageable = 1;
+        else if (!strcmp(f, "--rtl-packed")) bsw_set_rtl_packed(1);      /* variant RTL's narrow 8-bit lane classes on the packed kernel */
         else if (!strcmp(f, "--variant=M")) variant = BSW_VARIANT_M; else if (!strcmp(f, "--variant=H")) variant = BSW_VARIANT_H; else if (!strcmp(f, "--variant=RTL")) variant = BSW_VARIANT_RTL;
         else if (!strcmp(f, "--target=hip")) {}
         else if (!strncmp(f, "--target=", 9)) { fprintf(stderr, "%s: only --target=hip exists; this library has no CPU path\n", f); return 2; }
@@ -160,7 +161,9 @@ int main(int argc, char **argv)
         cells += res[i].left.cells + res[i].right.cells;
         sum = sum * 1315423911ull + (unsigned)res[i].score + ((unsigned long long)(unsigned)res[i].truesc << 20) + (unsigned)res[i].qb * 7u + (unsigned)res[i].re * 13u;
     }
-    printf("{\"seeds\": %zu, \"packed_input\": %d, \"gpus\": %d, \"seconds\": %.5f, \"seeds_per_s\": %.1f, \"gcups_pcie_inclusive\": %.2f, \"cells\": %llu, \"result_checksum\": \"%016llx\"}\n",
-           n, packed, ndev, best, (double)n / best, (double)cells / best / 1e9, cells, sum);
+    uint64_t rp[4] = {0, 0, 0, 0};
+    bsw_rtl_packed_stats(rp, 4);        /* launches of the packed RTL kernel (--rtl-packed): 0 when it did not run */
+    printf("{\"seeds\": %zu, \"packed_input\": %d, \"gpus\": %d, \"seconds\": %.5f, \"seeds_per_s\": %.1f, \"gcups_pcie_inclusive\": %.2f, \"cells\": %llu, \"rtl_packed_launches\": %llu, \"result_checksum\": \"%016llx\"}\n",
+           n, packed, ndev, best, (double)n / best, (double)cells / best / 1e9, cells, (unsigned long long)(rp[0] + rp[1] + rp[2] + rp[3]), sum);
     return 0;
 }

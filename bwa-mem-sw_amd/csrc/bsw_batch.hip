@@ -1571,6 +1571,8 @@ struct chunk_job {
     chunk_span span{0, 0};
     size_t seq = 0;                             /* the chunk's place in its device's input-DMA order (extension chunks only: a
                                                    CIGAR or rescue chunk gets no number and never waits at, or holds up, the gate) */
+    slot_job_fn fn = nullptr;                   /* non-NULL: no ticket's chunk (t is NULL) but piece span.base of a job of its own */
+    void *arg = nullptr;                        /* (pipeline_submit_job: a piece of an asynchronous read-block upload) */
 };
 
 struct dev_pipe {
@@ -1728,7 +1730,8 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
             gate_turn turn;
             turn.gate = &dq.gate; turn.seq = job.seq; turn.ev = dev.h2d_done[s]; turn.abort_flag = &t->abort; turn.passed = &passed;
             queued = true;
-            rc = stage_device(e, st, stream, ci, n, t->rtasks != nullptr || t->rdtasks != nullptr, t->ref, &h2d, &turn, d);
+            if (t->rdtasks) rc = reads_order(e, t->rd, d, stream);     /* a block whose upload is in flight: the stream waits for this device's copy */
+            if (!rc) rc = stage_device(e, st, stream, ci, n, t->rtasks != nullptr || t->rdtasks != nullptr, t->ref, &h2d, &turn, d);
             if (!rc && pairs && (he = st.d_pair.reserve(n + 1)) != hipSuccess) rc = fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
             if (!rc) rc = enqueue_batch(e, t->dp, p.variant, st.d_seq.p, st.d_tasks.p, st.d_order.p, ci.plan, st.d_out.p, stream, nullptr, fork_for(ctx, stream, true), pairs ? st.d_pair.p : nullptr);
         }
@@ -1782,6 +1785,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
     lane.bind(dev.f4[s]);
     lane.h_back = &dev.f4[s].h_back;
     lane.h_in = &dev.f4[s].h_in;
+    lane.h2d_total = &pp.h2d_bytes;
     auto process_f4 = [&](const chunk_job &job) {
         ticket_t *t = job.t;
         const f4_submit &f = t->f4;
@@ -1809,13 +1813,24 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
                          f.kind == 1 ? "cigar" : "matesw", base, n, tnow() - t0, t0, rc ? " FAILED" : "");
     };
 
+    /* A job that is no ticket's (pipeline_submit_job): like a CIGAR chunk it takes the slot's lane once the extension chunk in
+     * flight is handed over, and no turn at the gate; it reports through its own argument. */
+    auto process_job = [&](const chunk_job &job) {
+        finish();
+        lane.abort = nullptr;
+        lane.h2d = lane.d2h = 0;
+        if (dev_err != hipSuccess) dev_err = hipSetDevice(dev.device);
+        job.fn(ctx, lane, job.arg, job.span.base);        /* (it counts its own bytes through lane.h2d_total) */
+    };
+
     std::unique_lock<std::mutex> lk(pp.mu);
     for (;;) {
         if (!dq.q.empty()) {
             const chunk_job job = dq.q.front();
             dq.q.pop_front();
             lk.unlock();
-            if (job.t->kind) process_f4(job);
+            if (job.fn) process_job(job);
+            else if (job.t->kind) process_f4(job);
             else process(job);
             account();
             lk.lock();
@@ -1968,6 +1983,27 @@ BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket
         t->rd_held = t->f4.rd;                       /* (a *_reads_* submit: acquired by its entry point, given back when the ticket goes) */
         pp.live.push_back(std::move(t));
         pp.submits += 1;
+    }
+    pp.cv_work.notify_all();
+    return BSW_OK;
+}
+
+/* a job per piece on EVERY device's queue, behind what is queued and ahead of whatever is submitted later; it is no submit: no
+ * ticket, no place among BSW_MAX_INFLIGHT */
+BSW_LOCAL int pipeline_submit_job(bsw_ctx *ctx, slot_job_fn fn, void *arg, size_t pieces)
+{
+    int rc = pipeline_start(ctx);
+    if (rc) return rc;
+    pipeline &pp = *ctx->pipe.load();
+    {
+        std::lock_guard<std::mutex> lk(pp.mu);
+        for (size_t k = 0; k < pieces; ++k)
+            for (auto &dq : pp.devs) {
+                chunk_job j;
+                j.span = chunk_span{k, 0};
+                j.fn = fn; j.arg = arg;
+                dq->q.push_back(j);
+            }
     }
     pp.cv_work.notify_all();
     return BSW_OK;

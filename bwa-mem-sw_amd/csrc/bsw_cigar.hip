@@ -188,6 +188,7 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), n * sizeof(bsw_cdtask), 0), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
     L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_cdtask));
+    if (rd) { const int orc = reads_order(e, rd, L.dev, s); if (orc) return orc; }      /* (an upload in flight: s waits for this device's copy) */
     HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
                                BSW_PACK_REV_LEFT | (rd ? BSW_PACK_STORE : 0), ref->d_pac[L.dev], l_pac, st.d_desc.p, st.d_seq.p, nullptr, s));
 

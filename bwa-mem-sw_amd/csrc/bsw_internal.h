@@ -10,6 +10,7 @@
  *   bsw_cigar.hip   bwa_gen_cigar2 (+ mem_reg2aln's retries) against the resident reference, batch and ticketed submit
  *   bsw_matesw.hip  mem_matesw's ksw_align2 against the resident reference, batch and ticketed submit
  *   bsw_reads.hip   the resident read store: upload, free, info (its submits live with their pointer forms in the three files above)
+ *   bsw_reads_async.hip  the asynchronous upload: the reads cross as they lie and bsw_reads_pack_kernel packs them on the GPU
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
 #ifndef BSW_INTERNAL_H
@@ -50,9 +51,11 @@ struct bsw_ref {
  * boundary.  A base has a POSITION in the store, 16 * woff + index in the read; positions fit 32 bits (checked at upload) and are
  * what bsw_rawoff carries to bsw_pack_kernel in place of byte offsets (BSW_PACK_STORE).  Plain data: the submit paths read it
  * without calling into bsw_reads.hip. */
+struct reads_up;                      /* (below: it carries an errs) */
 struct bsw_reads {
     struct ent { uint32_t woff; int32_t len; };     /* word offset of a read in the store, its length */
     const bsw_ctx *owner = nullptr;
+    std::unique_ptr<reads_up> up;
     std::vector<uint64_t *> d_words;  /* one allocation per device (index = position in devs): BSW_READS_SLACK zeroed words, the reads, the same slack */
     std::vector<ent> rd;
     uint64_t bases = 0, words = 0;
@@ -326,6 +329,7 @@ struct bsw_ctx {
     std::mutex err_mu, pipe_mu;
     /* async submits: persistent slot threads behind a chunk queue (bsw_batch.hip), started by the first submit */
     std::atomic<struct pipeline *> pipe{nullptr};
+    std::atomic<int> uploads{0};      /* bsw_reads_upload_start: uploads in flight (at most BSW_READS_MAX_UPLOADS) */
     /* small synchronous batches (bsw_extend_batch, scalar ABI, wire format) */
     stage_t small;
     /* banded global alignment (F4) */
@@ -352,6 +356,23 @@ inline int ctx_fail(bsw_ctx *ctx, const errs &e, int rc)
     return rc;
 }
 
+/* The state of an ASYNCHRONOUS upload (bsw_reads_upload_start, bsw_reads_async.hip), NULL in a block of bsw_reads_upload.  The
+ * block is cut into pieces; every piece is a job on every device's queue (its GPU packs its own copy) and records ev[d][piece]
+ * behind its kernel.  Plain data: a chunk that names the block asks reads_order() below, without calling into that file. */
+struct reads_up {
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t npieces = 0;
+    std::vector<size_t> enq;                        /* per device: pieces whose work is on a stream (or that gave up) */
+    std::vector<std::vector<hipEvent_t>> ev;        /* per device, per piece */
+    size_t left = 0;                                /* piece jobs that have not reported yet, over all devices; 0: the upload is over */
+    int rc = 0;                                     /* the first failure */
+    errs err;
+    std::atomic<int> failed{0};                     /* a piece failed: the others give up */
+    std::vector<const uint8_t *> src;               /* the reads as the caller holds them (theirs until the block is ready) */
+    std::vector<size_t> cut;                        /* piece k = reads [cut[k], cut[k + 1]) */
+};
+
 /* a *_reads_* submit takes its block: false for a block of another context, or one that is being freed.  The ticket gives it
  * back when it is destroyed, i.e. collected (ticket_t, bsw_batch.hip). */
 inline bool reads_acquire(const bsw_ctx *ctx, const bsw_reads *rd)
@@ -363,6 +384,26 @@ inline bool reads_acquire(const bsw_ctx *ctx, const bsw_reads *rd)
     return u >= 0;
 }
 inline void reads_release(const bsw_reads *rd) { if (rd) const_cast<bsw_reads *>(rd)->users.fetch_sub(1); }
+
+/* A chunk on device d is about to launch the first kernel that reads rd's store, on stream s.  A block of bsw_reads_upload, or one
+ * whose upload is over: nothing happens, no HIP call is made.  An upload in flight: the slot thread waits HERE only until every
+ * piece of device d has been enqueued (those jobs sit in d's queue ahead of this chunk's and wait for nothing), then s waits for
+ * their events on the GPU.  A failed upload fails the chunk before it launches anything. */
+inline int reads_order(errs &e, const bsw_reads *rd, size_t d, hipStream_t s)
+{
+    reads_up *u = rd->up.get();
+    if (!u) return BSW_OK;
+    bool over;
+    {
+        std::unique_lock<std::mutex> lk(u->mu);
+        u->cv.wait(lk, [&]() { return u->enq[d] == u->npieces || u->failed.load(); });
+        over = u->left == 0;
+    }
+    if (u->failed.load()) return fail(e, BSW_E_HIP, "the upload of the read block failed: its reads are not on the device");
+    if (over) return BSW_OK;
+    for (hipEvent_t ev : u->ev[d]) HIPCHK(e, hipStreamWaitEvent(s, ev, 0));
+    return BSW_OK;
+}
 
 /* Where one chunk of bsw_cigar_ref_* / bsw_matesw_ref_* runs: the device (index into bsw_config.devices[], and so into
  * bsw_ref::d_pac), the staging, the stream, the watchdog event and the scratch buffers.  The synchronous calls pass the context's
@@ -394,6 +435,8 @@ struct f4_lane {
     }
     const std::atomic<int> *abort = nullptr;      /* a slot: the chunk's submit has failed elsewhere — give up between tries */
     uint64_t h2d = 0, d2h = 0;        /* bytes the chunk moved (bsw_host_stats) */
+    std::atomic<uint64_t> *h2d_total = nullptr;   /* a slot: the pipeline's H2D counter, for a job that must have its bytes counted BEFORE it reports
+                                                     (a piece of an upload: the block is ready once the last piece has reported) */
     void bind(f4_bufs &b)
     {
         g_tasks = &b.g_tasks; g_z = &b.g_z; g_cig = &b.g_cig; g_order = &b.g_order; g_res = &b.g_res;
@@ -445,6 +488,12 @@ inline uint64_t f4_chunk_work(const bsw_ctx *ctx, uint64_t total, uint64_t targe
 }
 /* ---- bsw_batch.hip: queues the chunks of `f` on the devices' queues in submit order; BSW_E_BUSY changes nothing ---- */
 BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket, const char *what);
+/* ---- bsw_batch.hip: a job that is no ticket's chunk (a piece of an asynchronous read-block upload, bsw_reads_async.hip).  It is
+ * queued once per device, `pieces` times, in front of whatever is submitted later; a slot thread hands over its extension chunk in
+ * flight and calls fn(ctx, lane, arg, piece) on its own lane (lane.dev says which device), with no turn at the input-DMA gate.
+ * fn waits for nothing but its own work, reports through arg and adds its bytes to *lane.h2d_total (bsw_host_stats). ---- */
+typedef void (*slot_job_fn)(bsw_ctx *ctx, f4_lane &lane, void *arg, size_t piece);
+BSW_LOCAL int pipeline_submit_job(bsw_ctx *ctx, slot_job_fn fn, void *arg, size_t pieces);
 /* ---- bsw_cigar.hip / bsw_matesw.hip: one chunk on a lane ---- */
 /* rd != NULL: the chunk's tasks are rtasks[0..n) and name reads of the resident block (tasks is NULL then): the per-task work is
  * the device records plus a base position — no span, no registration test, no gather, no raw bytes */

@@ -120,6 +120,7 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
         HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, L.dma_src(at.data(), n * sizeof(bsw_adtask), 0), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(order.data(), order.size() * sizeof(uint32_t), in_order), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_adtask)) + order.size() * sizeof(uint32_t);
+        if (rd) { const int orc = reads_order(e, rd, L.dev, s); if (orc) return orc; }      /* (an upload in flight: s waits for this device's copy) */
         HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
                                    rd ? BSW_PACK_STORE : 0, ref->d_pac[L.dev], l_pac, st.d_desc.p, st.d_seq.p, nullptr, s));
         for (int c = 0; c < ncls; ++c) {

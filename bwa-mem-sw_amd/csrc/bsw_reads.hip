@@ -7,6 +7,11 @@
  * The three *_reads_* submits live with their pointer forms (bsw_batch.hip, bsw_matesw.hip, bsw_cigar.hip) and read the block
  * as plain data; bsw_pack_kernel fetches the query words from it (bsw_reads_fetch.h).
  *
+ * bsw_reads_upload is the SYNCHRONOUS form: the caller sits in it while one host thread packs and a pageable image is copied.
+ * bsw_reads_upload_start (bsw_reads_async.hip) is the asynchronous one: it returns at once, the reads cross PCIe as they lie,
+ * bsw_reads_pack_kernel packs them on every GPU, and tickets that name the block are ordered behind that on the device.  Both
+ * make the same image, and bsw_reads_free / bsw_reads_info here serve both.
+ *
  * These calls may run while tickets are in flight and from several threads: they use no state of the context but its device
  * list and its error text (under its lock), and the upload copies on a stream of its own per device.
  */
@@ -24,6 +29,11 @@ static void reads_release_devices(bsw_ctx *ctx, bsw_reads *r)
         (void)hipFree(r->d_words[d]);
         r->d_words[d] = nullptr;
     }
+    if (r->up)                                       /* (after a failed upload too: what there is) */
+        for (size_t d = 0; d < r->up->ev.size(); ++d) {
+            (void)hipSetDevice(ctx->devs[d].device);
+            for (hipEvent_t &ev : r->up->ev[d]) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
+        }
     (void)hipSetDevice(ctx->device0());
 }
 
@@ -85,6 +95,10 @@ extern "C" int bsw_reads_free(bsw_ctx *ctx, bsw_reads *rd)
     if (!ctx) return BSW_E_INVAL;
     errs e;
     if (rd->owner != ctx) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_free: the read block was uploaded through another context"));
+    if (rd->up) {                                    /* bsw_reads_upload_start: its pieces read and write the block until the last one has reported */
+        std::lock_guard<std::mutex> lk(rd->up->mu);
+        if (rd->up->left) return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "bsw_reads_free: the upload of the block is still in flight"));
+    }
     int none = 0;
     if (!rd->users.compare_exchange_strong(none, -1))
         return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "bsw_reads_free: %d ticket(s) that use the block have not been collected", none));

@@ -158,6 +158,10 @@ def lib():
             "bsw_cigar_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_uint64)]),
             "bsw_matesw_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
             "bsw_reads_upload": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp)]),
+            "bsw_reads_upload_start": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp)]),
+            "bsw_reads_test": (C.c_int, [vp, vp]),
+            "bsw_reads_wait": (C.c_int, [vp, vp]),
+            "bsw_reads_image": (C.c_int, [vp, vp, C.c_int, vp, sz]),
             "bsw_reads_free": (C.c_int, [vp, vp]),
             "bsw_reads_info": (C.c_int, [vp] + [C.POINTER(C.c_uint64)] * 3),
             "bsw_submit_reads_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
@@ -199,7 +203,7 @@ def lib():
 
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
-           "bsw_reads_upload", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
+           "bsw_reads_upload", "bsw_reads_upload_start", "bsw_reads_test", "bsw_reads_wait", "bsw_reads_image", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
            "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
@@ -586,9 +590,39 @@ class BswContext:
         self._chk(lib().bsw_reads_upload(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(reads), C.byref(h)), "bsw_reads_upload")
         return h
 
+    def reads_upload_start(self, reads):
+        """bsw_reads_upload_start: returns the block's handle at once; it may be handed to the *_reads_* submits at once.  The
+        arrays in `reads` are kept alive here until the block is freed (their bases belong to the upload until it is ready)."""
+        reads = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+        ptrs = np.array([r.ctypes.data if len(r) else 0 for r in reads], dtype=np.uint64)
+        lens = np.array([len(r) for r in reads], dtype=np.int32)
+        h = C.c_void_p()
+        self._chk(lib().bsw_reads_upload_start(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(reads), C.byref(h)), "bsw_reads_upload_start")
+        if not hasattr(self, "_reads_alive"):
+            self._reads_alive = {}
+        self._reads_alive[h.value] = reads
+        return h
+
+    def reads_test(self, rd):
+        """bsw_reads_test: True once the block is ready, False while its upload is in flight; raises for a failed upload"""
+        rc = lib().bsw_reads_test(self.handle, rd)
+        if rc < 0:
+            self._chk(rc, "bsw_reads_test")
+        return rc == 1
+
+    def reads_wait(self, rd):
+        self._chk(lib().bsw_reads_wait(self.handle, rd), "bsw_reads_wait")
+
+    def reads_image(self, rd, k=0):
+        """bsw_reads_image: device k's copy of a ready block as uint64 words, slack included"""
+        out = np.zeros(self.reads_info(rd)["device_bytes"] // 8, dtype=np.uint64)
+        self._chk(lib().bsw_reads_image(self.handle, rd, k, out.ctypes.data, len(out)), "bsw_reads_image")
+        return out
+
     def reads_free(self, rd):
         """bsw_reads_free; raises BswError(BSW_E_BUSY) while a ticket that uses the block has not been collected"""
         self._chk(lib().bsw_reads_free(self.handle, rd), "bsw_reads_free")
+        getattr(self, "_reads_alive", {}).pop(getattr(rd, "value", rd), None)
 
     @staticmethod
     def reads_info(rd):

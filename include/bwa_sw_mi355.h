@@ -255,12 +255,15 @@ int      bsw_host_unregister(void *p);
  * bsw_wait waits for ALL of them and returns the first failure in submit order.
  *
  * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, the three
- * *_reads_* submits, bsw_reads_upload, bsw_reads_free, bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called
- * on ONE context from several threads at once, the first submit included; every other call that takes the context
- * (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free, bsw_host_stats) needs it to itself.
+ * *_reads_* submits, bsw_reads_upload, bsw_reads_upload_start, bsw_reads_test, bsw_reads_wait, bsw_reads_free, bsw_wait_ticket,
+ * bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
+ * every other call that takes the context (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free,
+ * bsw_host_stats, bsw_reads_image) needs it to itself.
  *   - bsw_reads_upload and bsw_reads_free may run while tickets are in flight (block k+1 is uploaded while block k is on the GPU):
  *     the upload copies on a stream of its own per device and returns when the copies are complete; a block is handed to a
  *     submit only after its upload has returned, and freed only by one thread.
+ *   - bsw_reads_upload_start returns at once and its block may be handed to a submit at once, from any thread; bsw_reads_test and
+ *     bsw_reads_wait may be called on one block from several threads.
  *   - A ticket belongs to whoever collects it first.  bsw_wait collects every submit in flight when it is called, other threads'
  *     too; a thread blocked in bsw_wait_ticket on a ticket that bsw_wait (or a second bsw_wait_ticket) collects meanwhile returns
  *     BSW_E_INVAL once that submit is complete: its results are in out[], its error code went to the collector.
@@ -598,7 +601,10 @@ int      bsw_extend_ref(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, c
  * same read up to three times (whole, as a mate per rescue task, as &query[qb] slices) and look at every sequence pointer of a
  * chunk on the host (span, registration, gather); these forms send 76 - 112 bytes of records per task whatever the read length.
  * bsw_pack_kernel takes the query words out of the 4-bit store (a funnel shift over two words, backwards for the left flank and
- * the reverse-strand CIGAR read); every kernel behind it reads the same `seq` as before. ---- */
+ * the reverse-strand CIGAR read); every kernel behind it reads the same `seq` as before.
+ * A block goes up in one of two ways: bsw_reads_upload packs it on the caller's thread and returns when every device has its
+ * copy; bsw_reads_upload_start returns at once, sends the reads across as they lie and packs them on the GPU, and the tickets
+ * that name the block wait for it ON THE DEVICE.  Both make the same image. ---- */
 typedef struct bsw_reads bsw_reads;
 /* reads[i]: lens[i] bases, codes 0..4 (larger codes stored as 4), any host memory.  A 4-bit packed copy (the device sequence
  * format, every read on a word boundary, zeroed slack words in front and behind) is placed on every device of the context, as
@@ -608,7 +614,30 @@ typedef struct bsw_reads bsw_reads;
  * not fit 32 bits (more than 2^28 - 2^13 packed words = ~4.29 G bases of word-aligned reads).  A failed upload leaves no copy on
  * any device.  n_reads == 0 is a valid, empty block. */
 int      bsw_reads_upload(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out);
-/* BSW_E_BUSY while a ticket that has not been collected uses rd (nothing is freed then); BSW_E_INVAL for a block of another
+/* The ASYNCHRONOUS upload.  The argument and per-read checks of bsw_reads_upload run in the caller's thread, with the same codes;
+ * the {offset, length} table is built and the device copies are reserved; the transfer is queued on every device and the call
+ * returns.  When a check or a reservation fails no block is made, nothing is queued and no device keeps anything.
+ *   - *out may be handed to bsw_submit_reads_t, bsw_matesw_reads_submit_t and bsw_cigar_reads_submit_t AT ONCE: their checks need
+ *     only the table, and on every device the first kernel of each of their chunks that reads the block runs after that device's
+ *     copy is complete (ordered on the GPU; the host does not wait for the copy).
+ *   - reads[] and lens[] may be freed when the call returns; the BASES they point to stay valid and unchanged until the block is
+ *     ready (bsw_reads_test == 1 / bsw_reads_wait returned).  Bases in registered memory (bsw_host_alloc / bsw_host_register) are
+ *     DMA'd as they lie; anything else is gathered into pinned staging by the context's slot threads.
+ *   - An upload is not a submit: no ticket, no place among BSW_MAX_INFLIGHT, not counted by bsw_inflight, not collected by
+ *     bsw_wait.  At most 2 uploads per context are in flight (block k+1 goes up while block k's tickets and upload are still
+ *     about); one more answers BSW_E_BUSY and changes nothing.  A block without a base (n_reads == 0 included) is ready at once.
+ *   - A failed upload (bsw_reads_wait / bsw_reads_test say so) fails every chunk that names the block with BSW_E_HIP before it
+ *     launches anything that reads the block; other tickets are left alone.  bsw_reads_free then frees what there is.
+ *   - bsw_reads_free answers BSW_E_BUSY while the upload is in flight; bsw_destroy waits for it, as it does for tickets. */
+int      bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out);
+/* 1: the block is ready, 0: its upload is in flight, < 0: the upload's failure.  Never blocks. */
+int      bsw_reads_test(bsw_ctx *ctx, const bsw_reads *rd);
+/* blocks until the upload is over (the watchdog of every wait applies) and returns its error code; may be called again */
+int      bsw_reads_wait(bsw_ctx *ctx, bsw_reads *rd);
+/* tests and tools: device k's copy of a READY block, slack words included (bsw_reads_info's device_bytes / 8 words), into
+ * words[0 .. cap_words).  Synchronous; BSW_E_BUSY while the upload is in flight, BSW_E_INVAL for too small a buffer. */
+int      bsw_reads_image(bsw_ctx *ctx, const bsw_reads *rd, int k, uint64_t *words, size_t cap_words);
+/* BSW_E_BUSY while a ticket that has not been collected uses rd, or while its upload is in flight (nothing is freed then); BSW_E_INVAL for a block of another
  * context.  rd == NULL is BSW_OK. */
 int      bsw_reads_free(bsw_ctx *ctx, bsw_reads *rd);
 /* reads, bases, and the bytes ONE device copy holds (slack included); any pointer may be NULL */

@@ -1805,7 +1805,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
         else if (f.kind == 1)
             rc = cigar_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ctasks ? f.ctasks + base : nullptr, n, f.max_cigar, f.cigars ? f.cigars + base * (size_t)f.max_cigar : nullptr,
                              f.max_md, f.md ? f.md + base * (size_t)f.max_md : nullptr, f.cres + base, f.rd, f.rd ? f.rd_ctasks + base : nullptr);
-        else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks ? f.mtasks + base : nullptr, n, f.mres + base, f.rd, f.rd ? f.rd_mtasks + base : nullptr);
+        else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks ? f.mtasks + base : nullptr, n, f.mres + base, f.rd, f.rd ? f.rd_mtasks + base : nullptr, f.al_mode);
         if (rc) ticket_fail(t, rc, e);
         else { pp.h2d_bytes += lane.h2d; pp.d2h_bytes += lane.d2h; pp.chunks += 1; }
         chunk_done(t);                              /* (the ticket may be collected and freed from here on) */

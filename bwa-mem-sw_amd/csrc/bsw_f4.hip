@@ -184,8 +184,15 @@ extern "C" int ksw_global(int qlen, const uint8_t *query, int tlen, const uint8_
 /* ---- local alignment with start / second-best search (bwa ksw_align2, mate rescue) -----------
  * Host side as for the global alignment: the byte-per-base sequences travel and are packed like extension tasks
  * (registered arenas DMA'd as they are), every alignment gets its slice of the sub-optimal list scratch, tasks are
- * sorted by kernel class (mode x vectors per lane), bsw_align_kernel runs per class. */
-static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_atask *tasks, size_t n, bsw_kswr *out)
+ * sorted by kernel class (mode x vectors per lane), bsw_align_kernel runs per class.
+ * Under bsw_set_align_long a query of more than BSW_ALIGN_MAX_QLEN bases (mode 2: every query) is sorted into the classes of
+ * bsw_align_long_kernel, which follow the ten of bsw_align_kernel in g_order; the route is the call's snapshot al_mode, and a chunk
+ * without such a task makes the HIP calls it made before the route existed. */
+static std::atomic<const align_long_ops *> g_align_long_ops{nullptr};
+BSW_LOCAL void align_long_register(const align_long_ops *ops) { g_align_long_ops.store(ops, std::memory_order_release); }
+BSW_LOCAL const align_long_ops *align_long_registered() { return g_align_long_ops.load(std::memory_order_acquire); }
+
+static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_atask *tasks, size_t n, bsw_kswr *out, int al_mode)
 {
     stage_t &st = ctx->small;
     hipStream_t s = ctx->stream0();
@@ -194,7 +201,9 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
         return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     std::vector<bsw_adtask> at(n);
     const int ncls = bsw::align_class_count();
-    std::vector<uint32_t> order(n), cnt((size_t)ncls + 1, 0), cls(n);
+    const align_long_ops *alo = al_mode ? align_long_registered() : nullptr;
+    const int nall = ncls + (alo ? alo->class_count() : 0);
+    std::vector<uint32_t> order(n), cnt((size_t)nall + 1, 0), cls(n);
     uint64_t acc = 0, accb = 0, bacc = 0;
     const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
     for (size_t i = 0; i < n; ++i) {
@@ -213,11 +222,13 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
         bsw_adtask &a = at[i];
         a.q_off = d.rq_off; a.t_off = d.rt_off; a.qlen = t.qlen; a.tlen = t.tlen; a.xtra = t.xtra; a.pad = 0; a.b_off = bacc;
         if (t.xtra & KSW_XSUBO) bacc += (uint64_t)t.tlen;
-        const int c = bsw::align_class_of(t.qlen, (t.xtra & KSW_XBYTE) != 0);
+        const int lc = align_long_route(al_mode, t.qlen, (t.xtra & KSW_XBYTE) != 0);
+        const int c = lc == -1 ? bsw::align_class_of(t.qlen, (t.xtra & KSW_XBYTE) != 0) : lc < 0 ? -1 : ncls + lc;
+        if (c < 0 || c >= nall) return fail(e, BSW_E_LIMIT, "align task %zu: no kernel class takes %d query bases", i, t.qlen);
         cls[i] = (uint32_t)c;
         ++cnt[(size_t)c + 1];
     }
-    for (int c = 0; c < ncls; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
+    for (int c = 0; c < nall; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
     {
         std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
         for (size_t i = 0; i < n; ++i) order[pos[cls[i]]++] = (uint32_t)i;
@@ -255,6 +266,11 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
         if (!k) continue;
         HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, ctx->a_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->a_bl.p, ctx->a_res.p, s));
     }
+    for (int c = ncls; c < nall; ++c) {               /* the LDS-row kernel's classes: launched only where a task was routed */
+        const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
+        if (!k) continue;
+        HIPCHK(e, alo->launch(c - ncls, dp, st.d_seq.p, ctx->a_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->a_bl.p, ctx->a_res.p, s));
+    }
     int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
     if (rc) return rc;
     HIPCHK(e, hipMemcpy(out, ctx->a_res.p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
@@ -264,7 +280,14 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
 
 extern "C" int bsw_align_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_atask *tasks, size_t n, bsw_kswr *out)
 {
+    return align_batch_mode(ctx, p, tasks, n, out, align_long_snapshot());     /* the switch as this call finds it */
+}
+
+BSW_LOCAL int align_batch_mode(bsw_ctx *ctx, const bsw_params *p, const bsw_atask *tasks, size_t n, bsw_kswr *out, int al_mode)
+{
     if (!ctx) return BSW_E_INVAL;
+    if (!align_long_registered()) al_mode = 0;
+    const int qmax = al_mode ? BSW_ALIGN_LONG_MAX_QLEN : BSW_ALIGN_MAX_QLEN;
     errs &e = ctx->err;
     if (!p || (!tasks && n) || (!out && n)) return fail(e, BSW_E_INVAL, "bsw_align_batch: NULL argument");
     int rc = busy_check(ctx, "bsw_align_batch");
@@ -280,7 +303,8 @@ extern "C" int bsw_align_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_atas
     for (size_t i = 0; i < n; ++i) {
         const bsw_atask &t = tasks[i];
         if (t.qlen < 0 || t.tlen < 0) return fail(e, BSW_E_INVAL, "align task %zu: negative length", i);
-        if (t.qlen > BSW_ALIGN_MAX_QLEN || t.tlen > BSW_MAX_TLEN) return fail(e, BSW_E_LIMIT, "align task %zu: beyond BSW_ALIGN_MAX_QLEN/BSW_MAX_TLEN", i);
+        if (t.qlen > qmax || t.tlen > BSW_MAX_TLEN)
+            return fail(e, BSW_E_LIMIT, "align task %zu: beyond %s/BSW_MAX_TLEN", i, al_mode ? "BSW_ALIGN_LONG_MAX_QLEN" : "BSW_ALIGN_MAX_QLEN");
         if ((t.qlen && !t.query) || (t.tlen && !t.target)) return fail(e, BSW_E_INVAL, "align task %zu: NULL sequence pointer", i);
         if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "align task %zu: unknown xtra flag", i);
     }
@@ -295,7 +319,7 @@ extern "C" int bsw_align_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_atas
             bb += (t.xtra & KSW_XSUBO) ? (uint64_t)t.tlen : 0;
             ++b;
         }
-        rc = align_chunk(ctx, e, dp, tasks + a, b - a, out + a);
+        rc = align_chunk(ctx, e, dp, tasks + a, b - a, out + a, al_mode);
         if (rc) return rc;
         a = b;
     }
@@ -318,6 +342,7 @@ static kswr_t align_scalar(int qlen, const uint8_t *query, int tlen, const uint8
     req.p.o_del = o_del; req.p.e_del = e_del; req.p.o_ins = o_ins; req.p.e_ins = e_ins;
     memset(&req.at, 0, sizeof(req.at));
     req.at.query = query; req.at.target = target; req.at.qlen = qlen; req.at.tlen = tlen; req.at.xtra = xtra;
+    req.al_mode = align_long_snapshot();               /* in the caller's thread: the trip's leader may be another one */
     scalar_call(req);                                  /* coalesced with whatever other threads have queued */
     r.score = -1;
     if (!req.rc) { r.score = req.ar.score; r.te = req.ar.te; r.qe = req.ar.qe; r.score2 = req.ar.score2; r.te2 = req.ar.te2; r.tb = req.ar.tb; r.qb = req.ar.qb; }

@@ -478,6 +478,7 @@ struct f4_submit {
     bsw_cresult *cres = nullptr;
     bsw_mresult *mres = nullptr;
     std::vector<chunk_span> spans;    /* chunk k -> device k mod n_devices */
+    int al_mode = 0;                  /* mate rescue: bsw_align_long() as the submit found it; the chunks route by this, never by the switch */
 };
 /* the work one chunk of a submit should hold: the kind's target (a launch of that much fills the machine), less for a submit
  * that would otherwise leave slots of the context without a chunk, never below an eighth of the target */
@@ -501,7 +502,37 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
                           size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res,
                           const bsw_reads *rd = nullptr, const bsw_rd_ctask *rtasks = nullptr);
 BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                           bsw_mresult *res, const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr);
+                           bsw_mresult *res, const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr, int al_mode = 0);
+
+/* ---- bsw_f4.hip: the long-query route of ksw_align2 (bsw_set_align_long).  bsw_align_long.hip, the unit that owns the switch and
+ * names the launcher of the companion library, registers this table when the library is loaded; a program linked without that
+ * unit keeps the NULL pointer, which means "mode 0 only".  The hosts (align_chunk, matesw_chunk) read the mode ONCE per call or
+ * submit, in the caller's thread, and route by that snapshot: a task of more than BSW_ALIGN_MAX_QLEN bases that passed the check goes
+ * to `launch` whatever the switch says by the time its chunk runs. ---- */
+struct align_long_ops {
+    int (*mode)();                    /* bsw_align_long() */
+    int (*class_count)();
+    int (*class_of)(int qlen, int byte_mode);
+    hipError_t (*launch)(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,
+                         unsigned long long *blist, bsw_kswr *out, hipStream_t s);
+};
+BSW_LOCAL void align_long_register(const align_long_ops *ops);
+BSW_LOCAL const align_long_ops *align_long_registered();
+inline int align_long_snapshot()
+{
+    const align_long_ops *o = align_long_registered();
+    const int m = o ? o->mode() : 0;
+    return m == 1 || m == 2 ? m : 0;
+}
+/* the class of a task behind the ncls classes of bsw_align_kernel, -1: the register kernel takes it (al_mode: the snapshot) */
+inline int align_long_route(int al_mode, int qlen, bool byte_mode)
+{
+    if (qlen <= BSW_ALIGN_MAX_QLEN && al_mode != 2) return -1;
+    const align_long_ops *o = align_long_registered();
+    return o ? o->class_of(qlen, byte_mode ? 1 : 0) : -2;                /* -2: no route (the entry checks never let one through) */
+}
+/* bsw_align_batch under a given snapshot (the scalar queue takes it in the calling thread) */
+BSW_LOCAL int align_batch_mode(bsw_ctx *ctx, const bsw_params *p, const bsw_atask *tasks, size_t n, bsw_kswr *out, int al_mode);
 
 struct chunk_info;
 struct bsw_dev_batch {
@@ -617,6 +648,7 @@ struct scalar_req {
     bsw_ext x;
     bsw_atask at;                     /* align */
     bsw_kswr ar;
+    int al_mode = 0;                  /* align: bsw_align_long() when the call entered */
     bsw_gtask gt;                     /* global */
     bsw_gresult gr;
     int cap = 0;                      /* CIGAR words this call can take (0: score only) */

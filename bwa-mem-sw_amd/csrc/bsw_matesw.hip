@@ -39,7 +39,7 @@ static inline bsw_mtask mtask_of(const bsw_mtask *tasks, const bsw_reads *rd, co
 }
 
 BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                           bsw_mresult *res, const bsw_reads *rd, const bsw_rd_mtask *rtasks)
+                           bsw_mresult *res, const bsw_reads *rd, const bsw_rd_mtask *rtasks, int al_mode)
 {
     stage_t &st = *L.st;
     hipStream_t s = L.s;
@@ -51,7 +51,9 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     std::vector<bsw_adtask> at(n);
     std::vector<uint8_t> runs(n);
     const int ncls = bsw::align_class_count();
-    std::vector<uint32_t> order, cnt((size_t)ncls + 1, 0), cls(n);
+    const align_long_ops *alo = al_mode ? align_long_registered() : nullptr;       /* (al_mode: the call's or the submit's snapshot) */
+    const int nall = ncls + (alo ? alo->class_count() : 0);
+    std::vector<uint32_t> order, cnt((size_t)nall + 1, 0), cls(n);
     uint64_t acc = 0, accb = 0, bacc = 0;
     const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
     for (size_t i = 0; i < n; ++i) {
@@ -80,12 +82,14 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
         a.pad = t.is_rev ? BSW_AD_QRC : 0u;
         a.b_off = bacc;
         if (t.xtra & KSW_XSUBO) bacc += (uint64_t)tlen;
-        const int c = bsw::align_class_of(t.l_ms, (t.xtra & KSW_XBYTE) != 0);
+        const int lc = align_long_route(al_mode, t.l_ms, (t.xtra & KSW_XBYTE) != 0);
+        const int c = lc == -1 ? bsw::align_class_of(t.l_ms, (t.xtra & KSW_XBYTE) != 0) : lc < 0 ? -1 : ncls + lc;
+        if (c < 0 || c >= nall) return fail(e, BSW_E_LIMIT, "mate task %zu: no kernel class takes %d bases", i, t.l_ms);
         cls[i] = (uint32_t)c;
         ++cnt[(size_t)c + 1];
     }
-    for (int c = 0; c < ncls; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
-    order.assign(cnt[(size_t)ncls], 0u);
+    for (int c = 0; c < nall; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
+    order.assign(cnt[(size_t)nall], 0u);
     {
         std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
         for (size_t i = 0; i < n; ++i) if (runs[i]) order[pos[cls[i]]++] = (uint32_t)i;
@@ -128,6 +132,11 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
             if (!k) continue;
             HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.a_bl->p, L.a_res->p, s));
         }
+        for (int c = ncls; c < nall; ++c) {           /* bsw_align_long_kernel's classes: launched only where a mate was routed */
+            const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
+            if (!k) continue;
+            HIPCHK(e, alo->launch(c - ncls, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.a_bl->p, L.a_res->p, s));
+        }
         if (L.h_back) HIPCHK(e, hipMemcpyAsync(L.h_back->p, L.a_res->p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost, s));
         int rc = sync_stream(ctx, e, s, L.ev);
         if (rc) return rc;
@@ -166,9 +175,10 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
 
 /* what both entry points check before anything runs or is queued: the parameters (band and variant are the call's own), then
  * the tasks in order — the first malformed one rejects the call */
-static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks, size_t n, const char *what, bsw_dparams *dp,
+static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks, size_t n, const char *what, bsw_dparams *dp, int al_mode,
                            const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr)
 {
+    const int qmax = al_mode ? BSW_ALIGN_LONG_MAX_QLEN : BSW_ALIGN_MAX_QLEN;
     bsw_params pp = *p;
     pp.w = 0; pp.variant = BSW_VARIANT_H;
     int rc = check_params(e, &pp, dp);
@@ -183,8 +193,8 @@ static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks,
         if (t.l_ms && !t.mate && !rd) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
         if (t.is_rev != 0 && t.is_rev != 1) return fail(e, BSW_E_INVAL, "mate task %zu: is_rev is neither 0 nor 1", i);
         if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "mate task %zu: unknown xtra flag", i);
-        if (t.l_ms > BSW_ALIGN_MAX_QLEN || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
-            return fail(e, BSW_E_LIMIT, "mate task %zu: beyond BSW_ALIGN_MAX_QLEN / BSW_MAX_TLEN", i);
+        if (t.l_ms > qmax || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
+            return fail(e, BSW_E_LIMIT, "mate task %zu: beyond %s / BSW_MAX_TLEN", i, al_mode ? "BSW_ALIGN_LONG_MAX_QLEN" : "BSW_ALIGN_MAX_QLEN");
     }
     return BSW_OK;
 }
@@ -200,7 +210,8 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
     int rc = busy_check(ctx, "bsw_matesw_ref_batch");
     if (rc) return rc;
     bsw_dparams dp;
-    rc = matesw_validate(e, p, tasks, n, "bsw_matesw_ref_batch", &dp);
+    const int al_mode = align_long_snapshot();        /* the switch as this call finds it */
+    rc = matesw_validate(e, p, tasks, n, "bsw_matesw_ref_batch", &dp, al_mode);
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(ctx->device0()));
     f4_lane L = ctx_lane(ctx);
@@ -215,7 +226,7 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
             bb += (t.xtra & KSW_XSUBO) ? tl : 0;
             ++b;
         }
-        rc = matesw_chunk(ctx, e, L, dp, ref, tasks + a, b - a, res + a);
+        rc = matesw_chunk(ctx, e, L, dp, ref, tasks + a, b - a, res + a, nullptr, nullptr, al_mode);
         if (rc) return rc;
         a = b;
     }
@@ -249,7 +260,8 @@ static int matesw_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, 
     if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
     f4_submit f;
     f.kind = 2; f.pp = *p; f.pp.w = 0; f.pp.variant = BSW_VARIANT_H;
-    int rc = matesw_validate(e, p, tasks, n, what, &f.dp, rd, rtasks);
+    f.al_mode = align_long_snapshot();               /* in the submitting thread; the chunks run later on slot threads */
+    int rc = matesw_validate(e, p, tasks, n, what, &f.dp, f.al_mode, rd, rtasks);
     if (rc) return ctx_fail(ctx, e, rc);
     f.ref = ref; f.mtasks = tasks; f.rd = rd; f.rd_mtasks = rtasks; f.n = n; f.mres = res;
     uint64_t total = 0;

@@ -127,7 +127,7 @@ static int scalar_align_group(std::vector<scalar_req *> &batch, const std::vecto
     std::vector<bsw_atask> t(grp.size());
     std::vector<bsw_kswr> o(grp.size());
     for (size_t k = 0; k < grp.size(); ++k) t[k] = batch[grp[k]]->at;
-    const int rc = bsw_align_batch(g_ctx, &batch[grp[0]]->p, t.data(), t.size(), o.data());
+    const int rc = align_batch_mode(g_ctx, &batch[grp[0]]->p, t.data(), t.size(), o.data(), batch[grp[0]]->al_mode);
     if (rc && !quiet) fprintf(stderr, "ksw_align2(libbwasw_mi355): GPU path failed (%d): %s\n", rc, bsw_last_error(g_ctx));
     for (size_t k = 0; k < grp.size(); ++k) { batch[grp[k]]->rc = rc; if (!rc) batch[grp[k]]->ar = o[k]; }
     return rc;
@@ -209,7 +209,7 @@ static void scalar_round_trip(std::vector<scalar_req *> &batch)
             if (taken[i] || (pass == 0) != (kind != 0)) continue;
             std::vector<size_t> grp;
             for (size_t j = i; j < batch.size(); ++j)
-                if (!taken[j] && batch[j]->kind == kind &&
+                if (!taken[j] && batch[j]->kind == kind && (kind != 1 || batch[i]->al_mode == batch[j]->al_mode) &&
                     (kind == 0 ? same_scoring(batch[i]->p, batch[j]->p) : same_alignment_scoring(batch[i]->p, batch[j]->p))) { grp.push_back(j); taken[j] = 1; }
             scalar_run_group(batch, grp, kind);
         }

@@ -80,6 +80,13 @@ int align_class_count();
 int align_class_of(int qlen, int byte_mode);                 /* -1: query too long for the mode */
 hipError_t launch_align(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,
                         unsigned long long *blist, bsw_kswr *out, hipStream_t s);
+/* the same alignment with its rows in LDS (bsw_align_long_kernel.hip, in the companion library libbwasw_mi355_alnl.so): queries
+ * up to BSW_ALIGN_LONG_MAX_QLEN bases, classes by (mode, slen bound), launch_align's arguments.  The hosts reach these three
+ * through align_long_ops (bsw_internal.h) only, never by name. */
+int align_long_class_count();
+int align_long_class_of(int qlen, int byte_mode);            /* -1: beyond BSW_ALIGN_LONG_MAX_QLEN */
+hipError_t launch_align_long(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,
+                             unsigned long long *blist, bsw_kswr *out, hipStream_t s);
 /* nflag == NULL: the queries' words are read from seq instead (input that arrived packed); keys: n words of scratch */
 hipError_t launch_bin(const bsw_binparams &bp, const uint64_t *seq, const uint8_t *nflag, const bsw_dtask *tasks, uint32_t n, uint32_t *bins,
                       uint64_t *keys, uint32_t *order, hipStream_t s);

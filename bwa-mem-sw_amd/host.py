@@ -152,6 +152,9 @@ def lib():
             "bsw_set_rtl_packed": (None, [C.c_int]),
             "bsw_rtl_packed": (C.c_int, []),
             "bsw_rtl_packed_stats": (C.c_int, [C.c_void_p, C.c_int]),
+            "bsw_set_align_long": (None, [C.c_int]),
+            "bsw_align_long": (C.c_int, []),
+            "bsw_align_long_stats": (C.c_int, [C.c_void_p, C.c_int]),
             "bsw_global_batch": (C.c_int, [vp, vp, vp, sz, C.c_int, vp, vp]),
             "bsw_align_batch": (C.c_int, [vp, vp, vp, sz, vp]),
             "bsw_cigar_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp]),
@@ -204,7 +207,7 @@ def lib():
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
            "bsw_reads_upload", "bsw_reads_upload_start", "bsw_reads_test", "bsw_reads_wait", "bsw_reads_image", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
-           "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats", "bsw_host_alloc", "bsw_host_free",
+           "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats", "bsw_set_align_long", "bsw_align_long", "bsw_align_long_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
            "bsw_submit_packed", "bsw_upload_packed", "bsw_pack_tasks", "bsw_pack_tasks_bound",
@@ -763,6 +766,28 @@ def rtl_packed_stats():
     """Launches of the packed RTL kernel so far: (72 columns shared penalties, 72 separate, 136 shared, 136 separate)."""
     a = np.zeros(4, dtype=np.uint64)
     assert lib().bsw_rtl_packed_stats(a.ctypes.data, 4) == 4
+    return tuple(int(x) for x in a)
+
+
+ALIGN_LONG_MAX_QLEN = 8191
+
+
+def set_align_long(mode):
+    """Process-wide opt-in: ksw_align2 and everything built on it accept queries of 1 025 to 8 191 bases and run them on
+    bsw_align_long_kernel (1); every alignment runs on that kernel (2); 0: off (bsw_set_align_long; initially BSW_ALIGN_LONG).
+    Applies to the calls that enter the library afterwards."""
+    lib().bsw_set_align_long(int(mode))
+
+
+def align_long():
+    return int(lib().bsw_align_long())
+
+
+def align_long_stats():
+    """Launches of bsw_align_long_kernel so far, per class: 8-bit mode slen bound 16 .. 512, then 16-bit mode 32 .. 1 024."""
+    n = lib().bsw_align_long_stats(None, 0)
+    a = np.zeros(n, dtype=np.uint64)
+    assert lib().bsw_align_long_stats(a.ctypes.data, n) == n
     return tuple(int(x) for x in a)
 
 

@@ -217,6 +217,25 @@ int  bsw_rtl_packed(void);
  * e_del == e_ins), [1] 72 separate, [2] 136 shared, [3] 136 separate.  Writes min(cap, 4) counters, returns 4. */
 int  bsw_rtl_packed_stats(uint64_t *launches, int cap);
 
+/* ---- ksw_align2 for queries of 1 025 to BSW_ALIGN_LONG_MAX_QLEN bases (opt-in) ----
+ * Process-wide and atomic; applies to the calls that enter the library afterwards (a call or a submit reads the switch once, in
+ * the caller's thread: a ticket submitted under mode 1 completes under mode 1 whatever the switch says by then).  Initially the
+ * value of the environment variable BSW_ALIGN_LONG when that is "1" or "2", else 0.
+ *   0  a query beyond BSW_ALIGN_MAX_QLEN is refused: BSW_E_LIMIT from the batch calls, score -1 from ksw_align2 / ksw_align.
+ *   1  ksw_align2, ksw_align, bsw_align_batch, bsw_matesw_ref_batch, bsw_matesw_ref_submit_t and bsw_matesw_reads_submit_t accept
+ *      queries (mates) up to BSW_ALIGN_LONG_MAX_QLEN bases; those beyond BSW_ALIGN_MAX_QLEN run on bsw_align_long_kernel
+ *      (libbwasw_mi355_alnl.so: the rows of H, E and Hmax in LDS), shorter ones on bsw_align_kernel as before.  Results are the
+ *      same bit-exact ksw_u8 / ksw_i16 values.  Beyond BSW_ALIGN_LONG_MAX_QLEN: BSW_E_LIMIT still.
+ *   2  as 1, and every alignment runs on bsw_align_long_kernel, the short ones too (tests, rate comparisons).
+ * Any other value sets 0. */
+#define BSW_ALIGN_LONG_MAX_QLEN 8191
+void bsw_set_align_long(int mode);
+int  bsw_align_long(void);
+/* launches of bsw_align_long_kernel so far, per class: (8-bit mode, slen bound 16, 32, ... 512), then (16-bit mode, slen bound
+ * 32, 64, ... 1 024); slen = ceil(qlen / 16) resp. ceil(qlen / 8).  Writes min(cap, classes) counters, returns the number of
+ * classes (12). */
+int  bsw_align_long_stats(uint64_t *launches, int cap);
+
 /* ---- batch API ------------------------------------------------------------ */
 void     bsw_default_params(bsw_params *p);          /* bwa defaults a=1,b=4,o=6,e=1,w=100,clip=5,zdrop=100 */
 void     bsw_default_config(bsw_config *c);
@@ -258,7 +277,8 @@ int      bsw_host_unregister(void *p);
  * *_reads_* submits, bsw_reads_upload, bsw_reads_upload_start, bsw_reads_test, bsw_reads_wait, bsw_reads_free, bsw_wait_ticket,
  * bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
  * every other call that takes the context (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free,
- * bsw_host_stats, bsw_reads_image) needs it to itself.
+ * bsw_host_stats, bsw_reads_image) needs it to itself.  bsw_set_align_long, bsw_align_long and bsw_align_long_stats take no
+ * context and may be called from any thread at any time; a change applies to the calls that enter the library afterwards.
  *   - bsw_reads_upload and bsw_reads_free may run while tickets are in flight (block k+1 is uploaded while block k is on the GPU):
  *     the upload copies on a stream of its own per device and returns when the copies are complete; a block is handed to a
  *     submit only after its upload has returned, and freed only by one thread.
@@ -410,7 +430,7 @@ typedef struct bsw_kswr {            /* = bwa's kswr_t */
 } bsw_kswr;
 typedef struct bsw_atask {
     const uint8_t *query, *target;   /* codes 0..4, one per byte */
-    int32_t qlen, tlen;              /* qlen <= BSW_ALIGN_MAX_QLEN */
+    int32_t qlen, tlen;              /* qlen <= BSW_ALIGN_MAX_QLEN; <= BSW_ALIGN_LONG_MAX_QLEN under bsw_set_align_long(1 / 2) */
     int32_t xtra;
     int32_t _pad;
 } bsw_atask;
@@ -434,7 +454,8 @@ kswr_t ksw_align(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, con
  * region: aln.score >= min_score && aln.qb >= 0. ---- */
 typedef struct bsw_mtask {
     const uint8_t *mate;     /* the mate in READ order, codes 0..4 (bwa's ms)                                       */
-    int32_t  l_ms;           /* 0..BSW_ALIGN_MAX_QLEN (0: status 1, nothing run)                                     */
+    int32_t  l_ms;           /* 0..BSW_ALIGN_MAX_QLEN, 0..BSW_ALIGN_LONG_MAX_QLEN under bsw_set_align_long(1 / 2) (0: status 1,
+                                nothing run)                                                                          */
     int32_t  is_rev;         /* 0 / 1: align the reverse complement of the mate (mem_matesw: r>>1 != (r&1))          */
     int64_t  rb, re;         /* the window in bwa coordinates [0, 2*l_pac), as the caller would fetch it; re - rb <=
                                 BSW_MAX_TLEN                                                                          */
@@ -454,7 +475,7 @@ typedef struct bsw_mresult {
 } bsw_mresult;               /* 72 bytes */
 /* Batched mem_matesw Smith-Waterman on the GPU (m = 5; p supplies mat and the four gap penalties).  The first malformed task
  * rejects the batch: negative l_ms, NULL mate, is_rev other than 0 / 1, an unknown xtra flag -> BSW_E_INVAL;
- * l_ms > BSW_ALIGN_MAX_QLEN or re - rb > BSW_MAX_TLEN -> BSW_E_LIMIT. */
+ * l_ms > BSW_ALIGN_MAX_QLEN (BSW_ALIGN_LONG_MAX_QLEN under bsw_set_align_long(1 / 2)) or re - rb > BSW_MAX_TLEN -> BSW_E_LIMIT. */
 int      bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_mtask *tasks, size_t n,
                               bsw_mresult *res);
 /* The same as a TICKET of the context's pipeline: the contract of bsw_cigar_ref_submit_t above, with the checks and the results

@@ -2,7 +2,7 @@
  * bsw_batch.hip — the batch manager: host pass over a chunk (validate, lay out, count per kernel class), device staging (DMA, pack, bin), kernel launches, batch plan export, device-resident batches and reference, the small-batch path, the streaming slot pipeline behind bsw_submit / bsw_submit_packed / bsw_submit_ref (batch_manager.v:358-739, tbb.v, rbb.v)
  * (part of the host side of libbwasw_mi355.so; shared types and the functions that cross files: bsw_internal.h)
  */
-#include "bsw_internal.h"
+#include "bsw_f4_host.h"
 
 /* lane kernel needs a bwa-style matrix (bwa_fill_scmat): a on the diagonal, one mismatch score off it,
  * one score for every pair that involves an N */
@@ -500,8 +500,9 @@ static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, si
     ci.lo = hi ? lo : nullptr;
     ci.hi = hi;
     /* DMA the caller's arena as it is when it is registered memory and not much larger than what it holds */
-    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
-    ci.direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * ci.sum_len + (1u << 20) && is_registered(lo, spanb);
+    const raw_span sp{lo, hi, ci.sum_len};
+    const size_t spanb = sp.span();
+    ci.direct = sp.direct(RAW_SLACK);
     ci.rev_left = rev_left && (ci.direct || by_pos);    /* the gather path mirrors the left queries while copying */
     ci.raw_bias = ci.direct ? (uint32_t)(uintptr_t)lo : 0u;
     {
@@ -510,7 +511,7 @@ static int prepare_chunk_t(errs &e, const bsw_params *p, int kern, Src &&src, si
     }
     if (packed) {
         /* (span and bytes of packed input are whole words: lo / hi / sum_len were taken over 8 * nwords) */
-        ci.direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * ci.sum_len + (1u << 20) && is_registered(lo, spanb);
+        ci.direct = sp.direct(RAW_SLACK);
         ci.rev_left = false;
         ci.raw_bias = 0;
         if (ci.direct) ci.words = spanb >> 3;

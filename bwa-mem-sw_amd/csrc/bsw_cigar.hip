@@ -1,32 +1,18 @@
-/*
- * bsw_cigar.hip — host of bsw_cigar_ref_batch: bwa_gen_cigar2 (bwa.c), inside mem_reg2aln's band-widening loop (bwamem.c),
- * against the device-resident reference (part of the host side of libbwasw_mi355.so; shared types: bsw_internal.h).
- *
- * Per chunk of tasks:
- *   1. the reads cross PCIe (registered memory is DMA'd as it lies, anything else is gathered into pinned staging) and
- *      bsw_pack_kernel packs them next to the targets it fetches from the resident pac.  A forward-strand interval is a
- *      right-side-only seed (read forwards, target upwards from rb); a reverse-strand one a left-side-only seed (read
- *      backwards from its last base, target downwards from re - 1): that is bwa's reversal of both, for free;
- *   2. every try runs bsw_global_kernel / bsw_global_long_kernel (unchanged, with their class routing) on the tasks still
- *      in the loop, with their band and a fresh slice of the backtrack matrix; only the scores come back between tries,
- *      the packed sequences stay where they are.  A try whose band (after bwa's formula) equals the previous one's would
- *      return the previous score and end the loop on "score == last": it is counted, not run;
+/* bsw_cigar.hip — host of bsw_cigar_ref_batch: bwa_gen_cigar2 (bwa.c), inside mem_reg2aln's band-widening loop (bwamem.c),
+ * against the device-resident reference (part of the host side of libbwasw_mi355.so).  Spans, class lists, routing, staging,
+ * read-back and the sub-batch cutter are bsw_f4_host.h's; host-specific here, per chunk of tasks:
+ *   1. how a task is laid out for bsw_pack_kernel: a forward-strand interval is a right-side-only seed (read forwards, target
+ *      upwards from rb); a reverse-strand one a left-side-only seed (read backwards from its last base, target downwards from
+ *      re - 1): that is bwa's reversal of both, for free;
+ *   2. the tries: each runs the global kernels on the tasks still in the loop, with their band and a fresh slice of the backtrack
+ *      matrix; only the scores come back between tries, the packed sequences stay where they are.  A try whose band (after bwa's
+ *      formula) equals the previous one's would return the previous score and end the loop on "score == last": it is counted, not run;
  *   3. bsw_cigar_md_kernel derives NM and MD once per task from its final CIGAR, and settles bwa's no-gap shortcut.
- *
- * A chunk runs on a LANE (f4_lane, bsw_internal.h): bsw_cigar_ref_batch passes the context's own — first device, stream 0, blocking
- * read-backs —, bsw_cigar_ref_submit_t cuts the submit by work and hands the chunks to the slot pipeline (bsw_batch.hip), whose
- * slots each own a lane on their device and read back into pinned memory in front of the watchdog's wait.
- */
-#include "bsw_internal.h"
+ * A chunk runs on a LANE (f4_lane, bsw_internal.h): the context's own for bsw_cigar_ref_batch, a pipeline slot's for the chunks of
+ * bsw_cigar_ref_submit_t (bsw_batch.hip), which reads back into pinned memory in front of the watchdog's wait. */
+#include "bsw_f4_host.h"
 
 #include <climits>
-
-/* BSW_GLOBAL_LONG=1 sends every alignment to the LDS ring kernel, as it does for bsw_global_batch */
-static bool cigar_force_long()
-{
-    static const bool on = getenv("BSW_GLOBAL_LONG") && atoi(getenv("BSW_GLOBAL_LONG")) != 0;
-    return on;
-}
 
 /* bwa_gen_cigar2's band for a try with w_ (the no-gap shortcut aside) */
 static int gen_cigar_band(const bsw_params &p, int l_query, int rlen, int w_)
@@ -70,14 +56,13 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     hipStream_t s = L.s;
     hipError_t he;
     const int64_t l_pac = ref->l_pac;
-    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
-        (he = st.h_desc.reserve(n + 1)) != hipSuccess)
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    int rc = stage_records(e, st, n, true);
+    if (rc) return rc;
     std::vector<bsw_gdtask> gt(n);
     std::vector<bsw_cdtask> cd(n);
     std::vector<cstate> cs(n);
-    uint64_t acc = 0, accb = 0;
-    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    uint64_t acc = 0;
+    raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_ctask t = ctask_of(tasks, rtasks, i);
         bsw_dtask &d = st.h_tasks.p[i];
@@ -102,7 +87,7 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         const uint32_t qw = (uint32_t)acc, tw = (uint32_t)(acc + nwords(t.l_query));
         acc += nwords(t.l_query) + nwords(rlen);
         /* where the slice starts: a byte offset into the raw bytes, or (resident reads) the position of base qb of its read */
-        const uint32_t at = rd ? rd->pos(rtasks[i].read) + (uint32_t)rtasks[i].qb : (uint32_t)accb;
+        const uint32_t at = rd ? rd->pos(rtasks[i].read) + (uint32_t)rtasks[i].qb : (uint32_t)sp.bytes;
         if (rev) {                        /* left side only: read backwards from its last base, target downwards from re - 1 */
             d.lq_off = qw; d.lt_off = tw; d.lqlen = (uint16_t)t.l_query; d.ltlen = (uint16_t)rlen;
             r.lq = at + (uint32_t)t.l_query - 1u;
@@ -112,11 +97,7 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
             r.rq = at;
             x.xr = t.rb;
         }
-        if (!rd) {
-            accb += (uint64_t)t.l_query;
-            if (t.query < lo) lo = t.query;
-            if (t.query + t.l_query > hi) hi = t.query + t.l_query;
-        }
+        if (!rd) sp.add(t.query, (size_t)t.l_query);
         c.q_off = qw; c.t_off = tw; c.qlen = t.l_query; c.tlen = rlen;
         c.flags = rev ? BSW_CD_REV : 0u;
         if (t.l_query == rlen && q.w2 == 0) {            /* the no-gap shortcut: the NM / MD kernel does it */
@@ -131,26 +112,14 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         bsw_gdtask &g = gt[i];
         g.q_off = qw; g.t_off = tw; g.qlen = t.l_query; g.tlen = rlen; g.w = q.band; g.pad = 0; g.z_off = 0;
     }
-    /* the reads: the caller's bytes as they lie (registered memory) or gathered forwards into pinned staging; either way a
-     * reverse-strand read's offset names its LAST byte and the pack kernel reads it backwards */
-    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
-    const bool direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * accb + (1u << 20) && is_registered(lo, spanb);
-    if (direct) {
-        for (size_t i = 0; i < n; ++i) {
-            if (cd[i].flags & BSW_CD_STATUS) continue;
-            const uint32_t o = (uint32_t)(tasks[i].query - lo);
-            if (cd[i].flags & BSW_CD_REV) st.h_roff.p[i].lq = o + (uint32_t)tasks[i].l_query - 1u;
-            else st.h_roff.p[i].rq = o;
-        }
-    } else if (accb) {
-        if ((he = st.h_raw.reserve((size_t)accb + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
-        for (size_t i = 0; i < n; ++i) {
-            if (cd[i].flags & BSW_CD_STATUS) continue;
-            const uint32_t o = (cd[i].flags & BSW_CD_REV) ? st.h_roff.p[i].lq + 1u - (uint32_t)tasks[i].l_query : st.h_roff.p[i].rq;
-            memcpy(st.h_raw.p + o, tasks[i].query, (size_t)tasks[i].l_query);
-        }
-    }
-    const size_t rawb = direct ? spanb : (size_t)accb;
+    /* the reads: either way a reverse-strand read's offset names its LAST byte and the pack kernel reads it backwards */
+    staged_raw raw;
+    rc = stage_raw(e, st, n, sp, acc, true, false, 1, [&](size_t i, int) {
+        if (cd[i].flags & BSW_CD_STATUS) return raw_piece{nullptr, 0, &bsw_rawoff::rq, false};
+        const bool rev = (cd[i].flags & BSW_CD_REV) != 0;
+        return raw_piece{tasks[i].query, (size_t)tasks[i].l_query, rev ? &bsw_rawoff::lq : &bsw_rawoff::rq, rev};
+    }, &raw);
+    if (rc) return rc;
     /* backtrack room: the widest band any try can reach is the formula's own (w_ only caps it) */
     uint64_t zmax = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -158,45 +127,34 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         const int wmax = gen_cigar_band(pp, cd[i].qlen, cd[i].tlen, INT_MAX);
         zmax += (uint64_t)std::min(cd[i].qlen, 2 * wmax + 1) * (uint64_t)cd[i].tlen;
     }
-    if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
-        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
-        (he = st.d_desc.reserve(n + 1)) != hipSuccess ||
-        (he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
+    if ((he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
         (he = L.g_res->reserve(n + 1)) != hipSuccess || (he = L.g_z->reserve((size_t)zmax + 64)) != hipSuccess ||
         (he = L.g_cig->reserve(n * (size_t)max_cigar + 1)) != hipSuccess ||
         (he = L.c_tasks->reserve(n + 1)) != hipSuccess || (he = L.c_res->reserve(n + 1)) != hipSuccess ||
         (md && (he = L.c_md->reserve(n * (size_t)max_md + 1)) != hipSuccess))
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
     /* a slot reads back into pinned memory: the scores of a try, then results | CIGARs | MD slots */
-    const size_t back_cig = n * sizeof(bsw_cresult), back_md = back_cig + (cigars ? n * (size_t)max_cigar * sizeof(uint32_t) : 0),
-                 back_end = back_md + (md ? n * (size_t)max_md : 0);
+    const size_t cigb = cigars ? n * (size_t)max_cigar * sizeof(uint32_t) : 0, mdb = md ? n * (size_t)max_md : 0;
     const size_t in_gt = (n + 1) * sizeof(bsw_cdtask), in_order = in_gt + (n + 1) * sizeof(bsw_gdtask);
-    if (L.h_back && ((he = L.h_back->reserve(std::max(back_end, n * sizeof(bsw_gresult)) + 16)) != hipSuccess ||
+    if (L.h_back && ((he = L.h_back->reserve(std::max(n * sizeof(bsw_cresult) + cigb + mdb, n * sizeof(bsw_gresult)) + 16)) != hipSuccess ||
                      (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
         return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     /* what the tries need (declared here: the guard behind them is destroyed first) */
-    const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
-    const bool force_long = cigar_force_long();
     std::vector<bsw_gresult> gr(L.h_back ? 0 : n);
     const bsw_gresult *grp = L.h_back ? (const bsw_gresult *)L.h_back->p : gr.data();
-    std::vector<uint32_t> order, cnt((size_t)(ncls + nlong) + 1), cls;
-    std::vector<uint32_t> live;
+    class_lists cl;
+    const global_route route;
+    std::vector<uint32_t> cls, live;
     drain_on_failure drain(ctx, s, L.ev);
-    if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
+    if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
     HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), n * sizeof(bsw_cdtask), 0), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
-    L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_cdtask));
-    if (rd) { const int orc = reads_order(e, rd, L.dev, s); if (orc) return orc; }      /* (an upload in flight: s waits for this device's copy) */
-    HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
-                               BSW_PACK_REV_LEFT | (rd ? BSW_PACK_STORE : 0), ref->d_pac[L.dev], l_pac, st.d_desc.p, st.d_seq.p, nullptr, s));
+    L.h2d += n * sizeof(bsw_cdtask);
+    if ((rc = stage_pack(e, L, n, BSW_PACK_REV_LEFT, ref, rd)) != BSW_OK) return rc;
 
     /* the tries: each launches the global kernels on the tasks still in the loop, then reads their scores */
     for (size_t i = 0; i < n; ++i) if (cs[i].live) live.push_back((uint32_t)i);
     while (!live.empty()) {
         if (L.abort && L.abort->load()) return fail(e, BSW_E_HIP, "aborted: another chunk failed");
-        std::fill(cnt.begin(), cnt.end(), 0u);
         cls.assign(live.size(), 0u);
         uint64_t zacc = 0;
         for (size_t k = 0; k < live.size(); ++k) {
@@ -205,32 +163,14 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
             g.z_off = zacc;
             const int n_col = g.qlen < 2 * g.w + 1 ? g.qlen : 2 * g.w + 1;
             zacc += (uint64_t)n_col * (uint64_t)g.tlen;
-            int c = 0;                    /* bsw_global_batch's routing */
-            while (c < ncls && g.qlen + 1 > bsw::global_class_cols(c)) ++c;
-            if (c == ncls || force_long) c = ncls + bsw::global_long_class_of(n_col);
-            cls[k] = (uint32_t)c;
-            ++cnt[(size_t)c + 1];
+            cls[k] = (uint32_t)route(g.qlen, n_col);     /* bsw_global_batch's routing */
         }
-        for (int c = 0; c < ncls + nlong; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
-        order.assign(live.size(), 0u);
-        {
-            std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
-            for (size_t k = 0; k < live.size(); ++k) order[pos[cls[k]]++] = live[k];
-        }
+        cl.build(route.classes(), cls.data(), live.data(), live.size());
         HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, L.dma_src(gt.data(), n * sizeof(bsw_gdtask), in_gt), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(order.data(), order.size() * sizeof(uint32_t), in_order), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        L.h2d += n * sizeof(bsw_gdtask) + order.size() * sizeof(uint32_t);
-        for (int c = 0; c < ncls + nlong; ++c) {
-            const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
-            if (!k) continue;
-            HIPCHK(e, bsw::launch_global(c, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.g_z->p, L.g_cig->p,
-                                         max_cigar, L.g_res->p, s));
-        }
-        if (L.h_back) HIPCHK(e, hipMemcpyAsync(L.h_back->p, L.g_res->p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost, s));
-        int rc = sync_stream(ctx, e, s, L.ev);
-        if (rc) return rc;
-        if (!L.h_back) HIPCHK(e, hipMemcpy(gr.data(), L.g_res->p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost));
-        L.d2h += n * sizeof(bsw_gresult);
+        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(cl.order.data(), live.size() * sizeof(uint32_t), in_order), live.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        L.h2d += n * sizeof(bsw_gdtask) + live.size() * sizeof(uint32_t);
+        if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p, L.g_z->p, L.g_cig->p, max_cigar, L.g_res->p, s)) != BSW_OK) return rc;
+        if ((rc = lane_read_back(ctx, e, L, {{L.h_back ? nullptr : gr.data(), L.g_res->p, n * sizeof(bsw_gresult)}})) != BSW_OK) return rc;
         /* mem_reg2aln: if (score == last || w2 == w_cap) break; last = score; w2 <<= 1; } while (++i < max_tries && score < min_score) */
         std::vector<uint32_t> next;
         for (uint32_t i : live) {
@@ -257,24 +197,8 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     }
     HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.c_tasks->p, (uint32_t)n, L.g_cig->p, max_cigar, L.g_res->p,
                                    md ? L.c_md->p : nullptr, max_md, L.c_res->p, s));
-    if (L.h_back) {
-        uint8_t *hb = L.h_back->p;
-        HIPCHK(e, hipMemcpyAsync(hb, L.c_res->p, n * sizeof(bsw_cresult), hipMemcpyDeviceToHost, s));
-        if (cigars) HIPCHK(e, hipMemcpyAsync(hb + back_cig, L.g_cig->p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        if (md) HIPCHK(e, hipMemcpyAsync(hb + back_md, L.c_md->p, n * (size_t)max_md, hipMemcpyDeviceToHost, s));
-        int rc = sync_stream(ctx, e, s, L.ev);
-        if (rc) return rc;
-        memcpy(res, hb, n * sizeof(bsw_cresult));
-        if (cigars) memcpy(cigars, hb + back_cig, n * (size_t)max_cigar * sizeof(uint32_t));
-        if (md) memcpy(md, hb + back_md, n * (size_t)max_md);
-    } else {
-        int rc = sync_stream(ctx, e, s, L.ev);
-        if (rc) return rc;
-        HIPCHK(e, hipMemcpy(res, L.c_res->p, n * sizeof(bsw_cresult), hipMemcpyDeviceToHost));
-        if (cigars) HIPCHK(e, hipMemcpy(cigars, L.g_cig->p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (md) HIPCHK(e, hipMemcpy(md, L.c_md->p, n * (size_t)max_md, hipMemcpyDeviceToHost));
-    }
-    L.d2h += back_end;
+    rc = lane_read_back(ctx, e, L, {{res, L.c_res->p, n * sizeof(bsw_cresult)}, {cigars, L.g_cig->p, cigb}, {md, L.c_md->p, mdb}});
+    if (rc) return rc;
     for (size_t i = 0; i < n; ++i) {
         bsw_cresult &r = res[i];
         if (cd[i].flags & BSW_CD_STATUS) {
@@ -345,22 +269,15 @@ extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
     HIPCHK(e, hipSetDevice(ctx->device0()));
     f4_lane L = ctx_lane(ctx);
     /* sub-batches: bounded backtrack memory (the widest band of any try) and sequence arena, as bsw_global_batch */
-    const uint64_t zcap = 4ull << 30;
-    for (size_t a = 0; a < n;) {
-        size_t b = a;
-        uint64_t zb = 0, sb = 0;
-        while (b < n && b - a < (1u << 20)) {
-            uint64_t nz, ns;
-            cigar_task_cost(pp, tasks[b], nz, ns);
-            if (b > a && (zb + nz > zcap || sb + ns > (1ull << 31))) break;
-            zb += nz;
-            sb += ns;
-            ++b;
-        }
-        rc = cigar_chunk(ctx, e, L, pp, dp, ref, tasks + a, b - a, max_cigar, cigars ? cigars + a * (size_t)max_cigar : nullptr, max_md,
-                         md ? md + a * (size_t)max_md : nullptr, res + a);
+    const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) {
+        uint64_t nz, ns;
+        cigar_task_cost(pp, tasks[i], nz, ns);
+        return span_cost{nz, ns, 0, 0, nz, 0};
+    }, span_caps());
+    for (const chunk_span &c : spans) {
+        rc = cigar_chunk(ctx, e, L, pp, dp, ref, tasks + c.base, c.cnt, max_cigar, cigars ? cigars + c.base * (size_t)max_cigar : nullptr, max_md,
+                         md ? md + c.base * (size_t)max_md : nullptr, res + c.base);
         if (rc) return rc;
-        a = b;
     }
     return BSW_OK;
 }
@@ -401,21 +318,11 @@ static int cigar_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, c
     std::vector<uint64_t> nz(n), ns(n);               /* one walk over the tasks: the band formula is the cost of this pass */
     uint64_t total = 0;
     for (size_t i = 0; i < n; ++i) { cigar_task_cost(f.pp, ctask_of(tasks, rtasks, i), nz[i], ns[i]); total += nz[i]; }
-    const uint64_t wcap = std::min<uint64_t>(f4_chunk_work(ctx, total, cigar_chunk_work()), 4ull << 30);
-    const uint64_t per_out = std::max<uint64_t>((uint64_t)max_cigar * sizeof(uint32_t), md ? (uint64_t)max_md : 0);
-    for (size_t a = 0; a < n;) {
-        size_t b = a;
-        uint64_t zb = 0, sb = 0;
-        while (b < n && b - a < (1u << 20)) {
-            /* (a chunk is closed once it HOLDS its share of the work, so no sliver is left over; the 4 GiB of backtrack bytes stay a hard bound) */
-            if (b > a && (zb >= wcap || zb + nz[b] > (4ull << 30) || sb + ns[b] > (1ull << 31) || (uint64_t)(b - a + 1) * per_out > F4_CIGAR_OUT_MAX)) break;
-            zb += nz[b];
-            sb += ns[b];
-            ++b;
-        }
-        f.spans.push_back(chunk_span{a, b - a});
-        a = b;
-    }
+    span_caps caps;                                   /* the batch call's bounds, the room of the outputs, and the work of a chunk */
+    caps.work = std::min<uint64_t>(f4_chunk_work(ctx, total, cigar_chunk_work()), 4ull << 30);
+    caps.out_per_task = std::max<uint64_t>((uint64_t)max_cigar * sizeof(uint32_t), md ? (uint64_t)max_md : 0);
+    caps.out = F4_CIGAR_OUT_MAX;
+    f.spans = cut_spans(n, [&](size_t i) { return span_cost{nz[i], ns[i], 0, nz[i], nz[i], 0}; }, caps);
     return pipeline_submit_f4(ctx, std::move(f), ticket, what);
 }
 

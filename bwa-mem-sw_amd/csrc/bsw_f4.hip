@@ -1,102 +1,149 @@
-/*
- * bsw_f4.hip — hosts of the two other Smith-Waterman users of bwa: bsw_global_batch / ksw_global2 / ksw_global and bsw_align_batch / ksw_align2 / ksw_align
- * (part of the host side of libbwasw_mi355.so; shared types and the functions that cross files: bsw_internal.h)
- */
-#include "bsw_internal.h"
+/* bsw_f4.hip — hosts of the two other Smith-Waterman users of bwa: bsw_global_batch / ksw_global2 / ksw_global and
+ * bsw_align_batch / ksw_align2 / ksw_align, and the bodies of what they share with bsw_cigar.hip and bsw_matesw.hip (bsw_f4_host.h:
+ * spans, class lists, routing, launch loops, staging, read-back, the sub-batch cutter).  Host-specific here: the device records
+ * (bsw_gdtask with its slice of the backtrack matrix, bsw_adtask with its slice of the sub-optimal list scratch) and the checks of
+ * the entry points.  (part of the host side of libbwasw_mi355.so) */
+#include "bsw_f4_host.h"
 
-/* ---- banded global alignment with CIGAR (SURVEY.md §8f F4: bwa ksw_global2) ------------------------------
- * Host side: lay the alignments out as right-side-only seeds so the byte-per-base sequences travel and are packed
- * exactly like extension tasks (registered arenas are DMA'd as they are), give every alignment its slice of the
- * backtrack matrix, sort by eh[] columns per lane, launch bsw_global_kernel, bring scores and CIGARs back.
- * Queries of 1 024 bases and more (every query under BSW_GLOBAL_LONG=1) go to bsw_global_long_kernel instead, sorted by
- * the LDS ring their band needs. */
-static bool global_force_long()
+/* ---- bsw_f4_host.h: the shared bodies ---- */
+BSW_LOCAL bool global_force_long()
 {
-    static const bool on = getenv("BSW_GLOBAL_LONG") && atoi(getenv("BSW_GLOBAL_LONG")) != 0;     /* (fuzzing, rate A/B) */
+    static const bool on = [] { const char *v = getenv("BSW_GLOBAL_LONG"); return v && atoi(v) != 0; }();
     return on;
 }
 
+BSW_LOCAL int launch_global_lists(errs &e, const class_lists &cl, const bsw_dparams &dp, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *d_order,
+                                  uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
+{
+    for (int c = 0; c < cl.classes(); ++c)
+        if (cl.count(c)) HIPCHK(e, bsw::launch_global(c, dp, seq, tasks, d_order + cl.begin(c), cl.count(c), z, cigars, max_cigar, out, s));
+    return BSW_OK;
+}
+
+BSW_LOCAL int launch_align_lists(errs &e, const class_lists &cl, const align_long_ops *alo, const bsw_dparams &dp, const uint64_t *seq, const bsw_adtask *tasks,
+                                 const uint32_t *d_order, unsigned long long *blist, bsw_kswr *out, hipStream_t s)
+{
+    const int ncls = bsw::align_class_count();
+    for (int c = 0; c < cl.classes(); ++c) {
+        if (!cl.count(c)) continue;
+        if (c < ncls) HIPCHK(e, bsw::launch_align(c, dp, seq, tasks, d_order + cl.begin(c), cl.count(c), blist, out, s));
+        else HIPCHK(e, alo->launch(c - ncls, dp, seq, tasks, d_order + cl.begin(c), cl.count(c), blist, out, s));
+    }
+    return BSW_OK;
+}
+
+BSW_LOCAL int stage_records(errs &e, stage_t &st, size_t n, bool desc)
+{
+    hipError_t he;
+    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
+        (desc && (he = st.h_desc.reserve(n + 1)) != hipSuccess))
+        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    return BSW_OK;
+}
+
+BSW_LOCAL int stage_upload(errs &e, f4_lane &L, const staged_raw &r, size_t n)
+{
+    stage_t &st = *L.st;
+    if (r.bytes) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, r.src, r.bytes, hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, L.s));
+    if (r.desc) HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, L.s));
+    L.h2d += r.bytes + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + (r.desc ? sizeof(bsw_refx) : 0));
+    return BSW_OK;
+}
+
+BSW_LOCAL int stage_pack(errs &e, f4_lane &L, size_t n, int flags, const bsw_ref *ref, const bsw_reads *rd)
+{
+    stage_t &st = *L.st;
+    if (rd) { const int orc = reads_order(e, rd, L.dev, L.s); if (orc) return orc; }       /* (an upload in flight: the stream waits for this device's copy) */
+    HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
+                               flags | (rd ? BSW_PACK_STORE : 0), ref ? ref->d_pac[L.dev] : nullptr, ref ? ref->l_pac : 0, ref ? st.d_desc.p : nullptr,
+                               st.d_seq.p, nullptr, L.s));
+    return BSW_OK;
+}
+
+BSW_LOCAL int lane_read_back(bsw_ctx *ctx, errs &e, f4_lane &L, std::initializer_list<back_copy> list)
+{
+    size_t off = 0;
+    for (const back_copy &c : list) {
+        if (L.h_back && c.bytes) HIPCHK(e, hipMemcpyAsync(L.h_back->p + off, c.src, c.bytes, hipMemcpyDeviceToHost, L.s));
+        off += c.bytes;
+    }
+    const int rc = sync_stream(ctx, e, L.s, L.ev);
+    if (rc) return rc;
+    off = 0;
+    for (const back_copy &c : list) {
+        if (L.h_back) { if (c.bytes && c.dst) memcpy(c.dst, L.h_back->p + off, c.bytes); }
+        else if (c.bytes) HIPCHK(e, hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost));
+        off += c.bytes;
+    }
+    L.d2h += off;
+    return BSW_OK;
+}
+
+/* ---- both hosts of this file: task i as a right-side-only seed of the query and target the caller holds, so that the byte-per-base
+ * sequences travel and are packed exactly like extension tasks ---- */
+static inline const bsw_dtask &stage_pair(stage_t &st, size_t i, uint64_t &acc, raw_span &sp, const uint8_t *query, int qlen, const uint8_t *target, int tlen)
+{
+    bsw_dtask &d = st.h_tasks.p[i];
+    bsw_rawoff &r = st.h_roff.p[i];
+    memset(&d, 0, sizeof(d));
+    memset(&r, 0, sizeof(r));
+    d.rq_off = (uint32_t)acc; acc += nwords(qlen);
+    d.rt_off = (uint32_t)acc; acc += nwords(tlen);
+    d.rqlen = (uint16_t)qlen; d.rtlen = (uint16_t)tlen;
+    r.rq = (uint32_t)sp.bytes; sp.add(query, (size_t)qlen);
+    r.rt = (uint32_t)sp.bytes; sp.add(target, (size_t)tlen);
+    return d;
+}
+template <class T>
+static inline raw_piece pair_piece(const T &t, int k)
+{
+    return k ? raw_piece{t.target, (size_t)t.tlen, &bsw_rawoff::rt, false} : raw_piece{t.query, (size_t)t.qlen, &bsw_rawoff::rq, false};
+}
+
+/* ---- banded global alignment with CIGAR (SURVEY.md §8f F4: bwa ksw_global2) ------------------------------
+ * Host side: give every alignment its slice of the backtrack matrix, sort by class (global_route), launch bsw_global_kernel /
+ * bsw_global_long_kernel, bring scores and CIGARs back. */
 static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_gtask *tasks, size_t n, int max_cigar,
                         bsw_gresult *res, uint32_t *cigars)
 {
-    stage_t &st = ctx->small;
-    hipStream_t s = ctx->stream0();
+    f4_lane L = ctx_lane(ctx);
+    stage_t &st = *L.st;
     hipError_t he;
-    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess)
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    int rc = stage_records(e, st, n, false);
+    if (rc) return rc;
     std::vector<bsw_gdtask> gt(n);
-    const int ncls = bsw::global_class_count(), nlong = bsw::GLOBAL_LONG_CLASSES;
-    const bool force_long = global_force_long();
-    std::vector<uint32_t> order(n), cnt((size_t)(ncls + nlong) + 1, 0), cls(n);
-    uint64_t acc = 0, accb = 0, zacc = 0;
-    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    std::vector<uint32_t> cls(n);
+    class_lists cl;
+    const global_route route;
+    uint64_t acc = 0, zacc = 0;
+    raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_gtask &t = tasks[i];
-        bsw_dtask &d = st.h_tasks.p[i];
-        bsw_rawoff &r = st.h_roff.p[i];
-        memset(&d, 0, sizeof(d));
-        memset(&r, 0, sizeof(r));
-        d.rq_off = (uint32_t)acc; acc += nwords(t.qlen);
-        d.rt_off = (uint32_t)acc; acc += nwords(t.tlen);
-        d.rqlen = (uint16_t)t.qlen; d.rtlen = (uint16_t)t.tlen;
-        r.rq = (uint32_t)accb; accb += (uint64_t)t.qlen;
-        r.rt = (uint32_t)accb; accb += (uint64_t)t.tlen;
-        if (t.qlen) { if (t.query < lo) lo = t.query; if (t.query + t.qlen > hi) hi = t.query + t.qlen; }
-        if (t.tlen) { if (t.target < lo) lo = t.target; if (t.target + t.tlen > hi) hi = t.target + t.tlen; }
+        const bsw_dtask &d = stage_pair(st, i, acc, sp, t.query, t.qlen, t.target, t.tlen);
         bsw_gdtask &g = gt[i];
         g.q_off = d.rq_off; g.t_off = d.rt_off; g.qlen = t.qlen; g.tlen = t.tlen; g.w = t.w; g.pad = 0; g.z_off = zacc;
         const int n_col = t.qlen < 2 * t.w + 1 ? t.qlen : 2 * t.w + 1;
         if (cigars) zacc += (uint64_t)n_col * (uint64_t)t.tlen;
-        int c = 0;
-        while (c < ncls && t.qlen + 1 > bsw::global_class_cols(c)) ++c;
-        if (c == ncls || force_long) c = ncls + bsw::global_long_class_of(n_col);   /* classes ncls.. : the LDS ring kernel */
-        cls[i] = (uint32_t)c;
-        ++cnt[(size_t)c + 1];
+        cls[i] = (uint32_t)route(t.qlen, n_col);
     }
-    for (int c = 0; c < ncls + nlong; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
-    {
-        std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
-        for (size_t i = 0; i < n; ++i) order[pos[cls[i]]++] = (uint32_t)i;
-    }
-    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
-    const bool direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * accb + (1u << 20) && is_registered(lo, spanb);
-    if (direct) {
-        for (size_t i = 0; i < n; ++i) {
-            bsw_rawoff &r = st.h_roff.p[i];
-            r.rq = tasks[i].qlen ? (uint32_t)(tasks[i].query - lo) : 0;
-            r.rt = tasks[i].tlen ? (uint32_t)(tasks[i].target - lo) : 0;
-        }
-    } else {
-        if ((he = st.h_raw.reserve((size_t)accb + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
-        for (size_t i = 0; i < n; ++i) {
-            if (tasks[i].qlen) memcpy(st.h_raw.p + st.h_roff.p[i].rq, tasks[i].query, (size_t)tasks[i].qlen);
-            if (tasks[i].tlen) memcpy(st.h_raw.p + st.h_roff.p[i].rt, tasks[i].target, (size_t)tasks[i].tlen);
-        }
-    }
-    const size_t rawb = direct ? spanb : (size_t)accb;
-    if ((he = st.d_raw.reserve(rawb + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
-        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->g_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->g_res.reserve(n + 1)) != hipSuccess || (cigars && (he = ctx->g_z.reserve((size_t)zacc + 64)) != hipSuccess) ||
-        (cigars && (he = ctx->g_cig.reserve(n * (size_t)max_cigar + 1)) != hipSuccess))
+    cl.build(route.classes(), cls.data(), nullptr, n);
+    staged_raw raw;
+    if ((rc = stage_raw(e, st, n, sp, acc, false, true, 2, [&](size_t i, int k) { return pair_piece(tasks[i], k); }, &raw)) != BSW_OK) return rc;
+    if ((he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
+        (he = L.g_res->reserve(n + 1)) != hipSuccess || (cigars && (he = L.g_z->reserve((size_t)zacc + 64)) != hipSuccess) ||
+        (cigars && (he = L.g_cig->reserve(n * (size_t)max_cigar + 1)) != hipSuccess))
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
-    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
-    if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(ctx->g_tasks.p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(e, bsw::launch_pack(st.d_raw.p, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, nullptr, 0, nullptr, st.d_seq.p, nullptr, s));
-    for (int c = 0; c < ncls + nlong; ++c) {
-        const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
-        if (!k) continue;
-        HIPCHK(e, bsw::launch_global(c, dp, st.d_seq.p, ctx->g_tasks.p, ctx->g_order.p + cnt[(size_t)c], k,
-                                     cigars ? ctx->g_z.p : nullptr, cigars ? ctx->g_cig.p : nullptr, max_cigar, ctx->g_res.p, s));
-    }
-    int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
-    if (rc) return rc;
-    HIPCHK(e, hipMemcpy(res, ctx->g_res.p, n * sizeof(bsw_gresult), hipMemcpyDeviceToHost));
-    if (cigars) HIPCHK(e, hipMemcpy(cigars, ctx->g_cig.p, n * (size_t)max_cigar * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    drain_on_failure drain(ctx, L.s, L.ev);
+    if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
+    HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.g_order->p, cl.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
+    if ((rc = stage_pack(e, L, n, 0, nullptr, nullptr)) != BSW_OK) return rc;
+    if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p, cigars ? L.g_z->p : nullptr, cigars ? L.g_cig->p : nullptr, max_cigar,
+                                  L.g_res->p, L.s)) != BSW_OK) return rc;
+    const size_t cigb = cigars ? n * (size_t)max_cigar * sizeof(uint32_t) : 0;
+    if ((rc = lane_read_back(ctx, e, L, {{res, L.g_res->p, n * sizeof(bsw_gresult)}, {cigars, L.g_cig->p, cigb}})) != BSW_OK) return rc;
     drain.done();
     return BSW_OK;
 }
@@ -123,21 +170,14 @@ extern "C" int bsw_global_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_gta
     HIPCHK(e, hipSetDevice(ctx->device0()));
     /* sub-batches: bounded backtrack memory (1 byte per banded cell) and sequence arena; the largest single task
      * (8 191 x 65 535 bytes of z, 73 726 sequence bytes) fits both bounds on its own */
-    const uint64_t zcap = 4ull << 30;
-    for (size_t a = 0; a < n;) {
-        size_t b = a;
-        uint64_t zb = 0, sb = 0;
-        while (b < n && b - a < (1u << 20)) {
-            const bsw_gtask &t = tasks[b];
-            const uint64_t nz = (uint64_t)(t.qlen < 2 * t.w + 1 ? t.qlen : 2 * t.w + 1) * (uint64_t)t.tlen;
-            if (b > a && (zb + nz > zcap || sb + (uint64_t)(t.qlen + t.tlen) > (1ull << 31))) break;
-            zb += cigars ? nz : 0;
-            sb += (uint64_t)(t.qlen + t.tlen);
-            ++b;
-        }
-        rc = global_chunk(ctx, e, dp, tasks + a, b - a, max_cigar, res + a, cigars ? cigars + a * (size_t)max_cigar : nullptr);
+    const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) {
+        const bsw_gtask &t = tasks[i];
+        const uint64_t nz = (uint64_t)(t.qlen < 2 * t.w + 1 ? t.qlen : 2 * t.w + 1) * (uint64_t)t.tlen;
+        return span_cost{cigars ? nz : 0, (uint64_t)(t.qlen + t.tlen), 0, 0, nz, 0};
+    }, span_caps());
+    for (const chunk_span &c : spans) {
+        rc = global_chunk(ctx, e, dp, tasks + c.base, c.cnt, max_cigar, res + c.base, cigars ? cigars + c.base * (size_t)max_cigar : nullptr);
         if (rc) return rc;
-        a = b;
     }
     return BSW_OK;
 }
@@ -182,9 +222,8 @@ extern "C" int ksw_global(int qlen, const uint8_t *query, int tlen, const uint8_
 }
 
 /* ---- local alignment with start / second-best search (bwa ksw_align2, mate rescue) -----------
- * Host side as for the global alignment: the byte-per-base sequences travel and are packed like extension tasks
- * (registered arenas DMA'd as they are), every alignment gets its slice of the sub-optimal list scratch, tasks are
- * sorted by kernel class (mode x vectors per lane), bsw_align_kernel runs per class.
+ * Host side as for the global alignment; every alignment gets its slice of the sub-optimal list scratch, tasks are sorted by
+ * kernel class (align_route), bsw_align_kernel runs per class.
  * Under bsw_set_align_long a query of more than BSW_ALIGN_MAX_QLEN bases (mode 2: every query) is sorted into the classes of
  * bsw_align_long_kernel, which follow the ten of bsw_align_kernel in g_order; the route is the call's snapshot al_mode, and a chunk
  * without such a task makes the HIP calls it made before the route existed. */
@@ -194,86 +233,42 @@ BSW_LOCAL const align_long_ops *align_long_registered() { return g_align_long_op
 
 static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_atask *tasks, size_t n, bsw_kswr *out, int al_mode)
 {
-    stage_t &st = ctx->small;
-    hipStream_t s = ctx->stream0();
+    f4_lane L = ctx_lane(ctx);
+    stage_t &st = *L.st;
     hipError_t he;
-    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess)
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    int rc = stage_records(e, st, n, false);
+    if (rc) return rc;
     std::vector<bsw_adtask> at(n);
     const int ncls = bsw::align_class_count();
     const align_long_ops *alo = al_mode ? align_long_registered() : nullptr;
     const int nall = ncls + (alo ? alo->class_count() : 0);
-    std::vector<uint32_t> order(n), cnt((size_t)nall + 1, 0), cls(n);
-    uint64_t acc = 0, accb = 0, bacc = 0;
-    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    std::vector<uint32_t> cls(n);
+    class_lists cl;
+    uint64_t acc = 0, bacc = 0;
+    raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_atask &t = tasks[i];
-        bsw_dtask &d = st.h_tasks.p[i];
-        bsw_rawoff &r = st.h_roff.p[i];
-        memset(&d, 0, sizeof(d));
-        memset(&r, 0, sizeof(r));
-        d.rq_off = (uint32_t)acc; acc += nwords(t.qlen);
-        d.rt_off = (uint32_t)acc; acc += nwords(t.tlen);
-        d.rqlen = (uint16_t)t.qlen; d.rtlen = (uint16_t)t.tlen;
-        r.rq = (uint32_t)accb; accb += (uint64_t)t.qlen;
-        r.rt = (uint32_t)accb; accb += (uint64_t)t.tlen;
-        if (t.qlen) { if (t.query < lo) lo = t.query; if (t.query + t.qlen > hi) hi = t.query + t.qlen; }
-        if (t.tlen) { if (t.target < lo) lo = t.target; if (t.target + t.tlen > hi) hi = t.target + t.tlen; }
+        const bsw_dtask &d = stage_pair(st, i, acc, sp, t.query, t.qlen, t.target, t.tlen);
         bsw_adtask &a = at[i];
         a.q_off = d.rq_off; a.t_off = d.rt_off; a.qlen = t.qlen; a.tlen = t.tlen; a.xtra = t.xtra; a.pad = 0; a.b_off = bacc;
         if (t.xtra & KSW_XSUBO) bacc += (uint64_t)t.tlen;
-        const int lc = align_long_route(al_mode, t.qlen, (t.xtra & KSW_XBYTE) != 0);
-        const int c = lc == -1 ? bsw::align_class_of(t.qlen, (t.xtra & KSW_XBYTE) != 0) : lc < 0 ? -1 : ncls + lc;
-        if (c < 0 || c >= nall) return fail(e, BSW_E_LIMIT, "align task %zu: no kernel class takes %d query bases", i, t.qlen);
+        const int c = align_route(al_mode, t.qlen, (t.xtra & KSW_XBYTE) != 0, ncls, nall);
+        if (c < 0) return fail(e, BSW_E_LIMIT, "align task %zu: no kernel class takes %d query bases", i, t.qlen);
         cls[i] = (uint32_t)c;
-        ++cnt[(size_t)c + 1];
     }
-    for (int c = 0; c < nall; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
-    {
-        std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
-        for (size_t i = 0; i < n; ++i) order[pos[cls[i]]++] = (uint32_t)i;
-    }
-    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
-    const bool direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * accb + (1u << 20) && is_registered(lo, spanb);
-    if (direct) {
-        for (size_t i = 0; i < n; ++i) {
-            bsw_rawoff &r = st.h_roff.p[i];
-            r.rq = tasks[i].qlen ? (uint32_t)(tasks[i].query - lo) : 0;
-            r.rt = tasks[i].tlen ? (uint32_t)(tasks[i].target - lo) : 0;
-        }
-    } else {
-        if ((he = st.h_raw.reserve((size_t)accb + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
-        for (size_t i = 0; i < n; ++i) {
-            if (tasks[i].qlen) memcpy(st.h_raw.p + st.h_roff.p[i].rq, tasks[i].query, (size_t)tasks[i].qlen);
-            if (tasks[i].tlen) memcpy(st.h_raw.p + st.h_roff.p[i].rt, tasks[i].target, (size_t)tasks[i].tlen);
-        }
-    }
-    const size_t rawb = direct ? spanb : (size_t)accb;
-    if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
-        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->a_tasks.reserve(n + 1)) != hipSuccess || (he = ctx->g_order.reserve(n + 1)) != hipSuccess ||
-        (he = ctx->a_res.reserve(n + 1)) != hipSuccess || (he = ctx->a_bl.reserve((size_t)bacc + 64)) != hipSuccess)
+    cl.build(nall, cls.data(), nullptr, n);
+    staged_raw raw;
+    if ((rc = stage_raw(e, st, n, sp, acc, false, true, 2, [&](size_t i, int k) { return pair_piece(tasks[i], k); }, &raw)) != BSW_OK) return rc;
+    if ((he = L.a_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
+        (he = L.a_res->reserve(n + 1)) != hipSuccess || (he = L.a_bl->reserve((size_t)bacc + 64)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
-    drain_on_failure drain(ctx, s, ctx->devs[0].events[0]);
-    if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(ctx->a_tasks.p, at.data(), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(ctx->g_order.p, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(e, bsw::launch_pack(st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n, 0, nullptr, 0, nullptr, st.d_seq.p, nullptr, s));
-    for (int c = 0; c < ncls; ++c) {
-        const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
-        if (!k) continue;
-        HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, ctx->a_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->a_bl.p, ctx->a_res.p, s));
-    }
-    for (int c = ncls; c < nall; ++c) {               /* the LDS-row kernel's classes: launched only where a task was routed */
-        const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
-        if (!k) continue;
-        HIPCHK(e, alo->launch(c - ncls, dp, st.d_seq.p, ctx->a_tasks.p, ctx->g_order.p + cnt[(size_t)c], k, ctx->a_bl.p, ctx->a_res.p, s));
-    }
-    int rc = sync_stream(ctx, e, s, ctx->devs[0].events[0]);
-    if (rc) return rc;
-    HIPCHK(e, hipMemcpy(out, ctx->a_res.p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
+    drain_on_failure drain(ctx, L.s, L.ev);
+    if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
+    HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, at.data(), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.g_order->p, cl.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
+    if ((rc = stage_pack(e, L, n, 0, nullptr, nullptr)) != BSW_OK) return rc;
+    if ((rc = launch_align_lists(e, cl, alo, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p, L.a_bl->p, L.a_res->p, L.s)) != BSW_OK) return rc;
+    if ((rc = lane_read_back(ctx, e, L, {{out, L.a_res->p, n * sizeof(bsw_kswr)}})) != BSW_OK) return rc;
     drain.done();
     return BSW_OK;
 }
@@ -309,19 +304,14 @@ BSW_LOCAL int align_batch_mode(bsw_ctx *ctx, const bsw_params *p, const bsw_atas
         if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "align task %zu: unknown xtra flag", i);
     }
     HIPCHK(e, hipSetDevice(ctx->device0()));
-    for (size_t a = 0; a < n;) {                      /* sub-batches: bounded sequence arena and sub-optimal list scratch */
-        size_t b = a;
-        uint64_t sb = 0, bb = 0;
-        while (b < n && b - a < (1u << 20)) {
-            const bsw_atask &t = tasks[b];
-            if (b > a && (sb + (uint64_t)(t.qlen + t.tlen) > (1ull << 31) || bb + (uint64_t)t.tlen > (1ull << 28))) break;
-            sb += (uint64_t)(t.qlen + t.tlen);
-            bb += (t.xtra & KSW_XSUBO) ? (uint64_t)t.tlen : 0;
-            ++b;
-        }
-        rc = align_chunk(ctx, e, dp, tasks + a, b - a, out + a, al_mode);
+    /* sub-batches: bounded sequence arena and sub-optimal list scratch */
+    const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) {
+        const bsw_atask &t = tasks[i];
+        return span_cost{0, (uint64_t)(t.qlen + t.tlen), (t.xtra & KSW_XSUBO) ? (uint64_t)t.tlen : 0, 0, 0, (uint64_t)t.tlen};
+    }, span_caps());
+    for (const chunk_span &c : spans) {
+        rc = align_chunk(ctx, e, dp, tasks + c.base, c.cnt, out + c.base, al_mode);
         if (rc) return rc;
-        a = b;
     }
     return BSW_OK;
 }

@@ -1,0 +1,166 @@
+/* bsw_f4_host.h — internal: what global_chunk / align_chunk (bsw_f4.hip), cigar_chunk (bsw_cigar.hip) and matesw_chunk
+ * (bsw_matesw.hip) share, each written once: the span of the caller's bytes with the direct-DMA test, per-class task lists, kernel
+ * routing and launch loops, staging the sequences on a lane, reading a lane back, cutting a call into sub-batches.  Nothing here
+ * keeps state (but the one getenv of global_force_long): chunks run concurrently on slot threads.  Non-inline bodies: bsw_f4.hip. */
+#ifndef BSW_F4_HOST_H
+#define BSW_F4_HOST_H
+
+#include "bsw_internal.h"
+
+#include <initializer_list>
+
+/* ---- the caller's bytes a chunk references: their span and sum ---- */
+struct raw_span {
+    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    uint64_t bytes = 0;               /* (before add(): the piece's offset in a gather) */
+    void add(const uint8_t *p, size_t len)
+    {
+        if (!len) return;
+        bytes += len;
+        if (p < lo) lo = p;
+        if (p + len > hi) hi = p + len;
+    }
+    size_t span() const { return hi ? (size_t)(hi - lo) : 0; }
+    /* DMA the caller's arena as it lies: registered, addressable in 32 bits with `slack` bytes of read-ahead, not much larger than what it holds */
+    bool direct(size_t slack) const
+    {
+        const size_t spanb = span();
+        return spanb > 0 && spanb < (1ull << 32) - slack && spanb <= 2 * bytes + (1u << 20) && is_registered(lo, spanb);
+    }
+};
+
+/* ---- tasks sorted by kernel class: class c owns order[begin(c) .. begin(c) + count(c)), in input order (a stable counting
+ * sort).  Owns host memory a queued copy reads: declare it in front of the drain_on_failure guard. ---- */
+struct class_lists {
+    std::vector<uint32_t> order, cnt;
+    /* entry i of k has class cls[i] and names task ids[i] (ids == NULL: task i) */
+    void build(int n_classes, const uint32_t *cls, const uint32_t *ids, size_t k)
+    {
+        cnt.assign((size_t)n_classes + 1, 0u);
+        for (size_t i = 0; i < k; ++i) ++cnt[(size_t)cls[i] + 1];
+        for (int c = 0; c < n_classes; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
+        order.assign(k, 0u);
+        std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
+        for (size_t i = 0; i < k; ++i) order[pos[cls[i]]++] = ids ? ids[i] : (uint32_t)i;
+    }
+    int classes() const { return (int)cnt.size() - 1; }
+    uint32_t begin(int c) const { return cnt[(size_t)c]; }
+    uint32_t count(int c) const { return cnt[(size_t)c + 1] - cnt[(size_t)c]; }
+};
+
+/* ---- routing.  launch_global's class for a query of qlen bases under a band of n_col columns: the register classes by qlen,
+ * behind them the LDS ring classes by n_col (every task under BSW_GLOBAL_LONG=1: fuzzing, rate A/B).  One per chunk. ---- */
+BSW_LOCAL bool global_force_long();   /* the one read of BSW_GLOBAL_LONG */
+struct global_route {
+    const int ncls = bsw::global_class_count();
+    const bool force_long = global_force_long();
+    int classes() const { return ncls + bsw::GLOBAL_LONG_CLASSES; }
+    int operator()(int qlen, int n_col) const
+    {
+        int c = 0;
+        while (c < ncls && qlen + 1 > bsw::global_class_cols(c)) ++c;
+        if (c == ncls || force_long) c = ncls + bsw::global_long_class_of(n_col);
+        return c;
+    }
+};
+/* an alignment's class among nall = ncls (bsw_align_kernel) + the LDS-row classes behind them; negative: none (the caller's BSW_E_LIMIT) */
+inline int align_route(int al_mode, int qlen, bool byte_mode, int ncls, int nall)
+{
+    const int lc = align_long_route(al_mode, qlen, byte_mode);
+    const int c = lc == -1 ? bsw::align_class_of(qlen, byte_mode) : lc < 0 ? -1 : ncls + lc;
+    return c < nall ? c : -1;
+}
+
+/* ---- one launch per class that holds a task, ascending; d_order: the device copy of cl.order; alo: the LDS-row kernel's classes
+ * behind the ncls of bsw_align_kernel ---- */
+BSW_LOCAL int launch_global_lists(errs &e, const class_lists &cl, const bsw_dparams &dp, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *d_order,
+                                  uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s);
+BSW_LOCAL int launch_align_lists(errs &e, const class_lists &cl, const align_long_ops *alo, const bsw_dparams &dp, const uint64_t *seq, const bsw_adtask *tasks,
+                                 const uint32_t *d_order, unsigned long long *blist, bsw_kswr *out, hipStream_t s);
+
+/* ---- staging the sequences of a chunk on a lane.  The caller: stage_records, fills h_tasks / h_roff (/ h_desc) with offsets of a gather
+ * (raw_span::bytes as it goes), stage_raw, its own reservations, its drain_on_failure, stage_upload, its own records, stage_pack. ---- */
+BSW_LOCAL int stage_records(errs &e, stage_t &st, size_t n, bool desc);
+/* a task's sequence as the caller holds it: p[0..len), the field of its bsw_rawoff that names it (last: names its LAST byte, read backwards); len == 0: none */
+struct raw_piece { const uint8_t *p; size_t len; uint32_t bsw_rawoff::*at; bool last; };
+struct staged_raw {                   /* what crosses PCIe: the caller's arena from raw_span::lo, or h_raw (resident reads: nothing) */
+    const uint8_t *src = nullptr;
+    size_t bytes = 0;
+    bool desc = false;
+};
+/* decides direct or gather; rewrites the offsets relative to the span, or gathers into h_raw (gather_empty: h_raw is reserved for a chunk without
+ * a byte too — the host's own HIP call sequence); reserves the device side.  piece(i, k): piece k of the `pieces` of task i. */
+template <class F>
+inline int stage_raw(errs &e, stage_t &st, size_t n, const raw_span &sp, uint64_t words, bool desc, bool gather_empty, int pieces, F piece, staged_raw *out)
+{
+    hipError_t he;
+    const bool direct = sp.direct(RAW_SLACK);
+    if (direct) {
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < pieces; ++k) {
+                const raw_piece pc = piece(i, k);
+                st.h_roff.p[i].*pc.at = pc.len ? (uint32_t)(pc.p - sp.lo) + (pc.last ? (uint32_t)pc.len - 1u : 0u) : 0u;
+            }
+    } else if (gather_empty || sp.bytes) {
+        if ((he = st.h_raw.reserve((size_t)sp.bytes + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < pieces; ++k) {
+                const raw_piece pc = piece(i, k);
+                if (pc.len) memcpy(st.h_raw.p + (st.h_roff.p[i].*pc.at - (pc.last ? (uint32_t)pc.len - 1u : 0u)), pc.p, pc.len);
+            }
+    }
+    out->bytes = direct ? sp.span() : (size_t)sp.bytes;
+    out->src = direct ? sp.lo : st.h_raw.p;
+    out->desc = desc;
+    if ((he = st.d_raw.reserve(out->bytes + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)words + 4)) != hipSuccess ||
+        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
+        (desc && (he = st.d_desc.reserve(n + 1)) != hipSuccess))
+        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    return BSW_OK;
+}
+/* queues the raw bytes (behind RAW_FRONT), the task records, the offsets and the reference positions; counts them in L.h2d */
+BSW_LOCAL int stage_upload(errs &e, f4_lane &L, const staged_raw &r, size_t n);
+/* queues bsw_pack_kernel.  ref: targets fetched from the lane's copy of the reference at h_desc; rd: queries from the lane's copy of the resident
+ * read block (BSW_PACK_STORE), behind an upload of it still in flight */
+BSW_LOCAL int stage_pack(errs &e, f4_lane &L, size_t n, int flags, const bsw_ref *ref, const bsw_reads *rd);
+
+/* ---- results back from a lane, behind everything queued on it: a slot lane copies into h_back at running offsets in front of the
+ * wait that carries the watchdog, then into dst (dst == NULL: the caller reads them in h_back); the context's lane waits, then
+ * copies blocking.  An entry without bytes is skipped.  The caller has reserved h_back. ---- */
+struct back_copy { void *dst; const void *src; size_t bytes; };
+BSW_LOCAL int lane_read_back(bsw_ctx *ctx, errs &e, f4_lane &L, std::initializer_list<back_copy> list);
+
+/* ---- cutting a call's n tasks into sub-batches ---- */
+struct span_cost {                    /* what one task adds to a sub-batch */
+    uint64_t z, seq, bl, work;        /* backtrack bytes, sequence bytes, sub-optimal-list entries, work */
+    /* What the bounds are probed with.  The hosts probe z and bl with the task's full size and accumulate only what the task is
+     * given (bsw_global_batch without CIGARs: no backtrack bytes; a task without KSW_XSUBO: no list slice): kept as it is. */
+    uint64_t z_probe, bl_probe;
+};
+struct span_caps {
+    uint64_t tasks = 1u << 20, z = 4ull << 30, seq = 1ull << 31, bl = 1ull << 28;      /* hard: a sub-batch exceeds one only as a single task */
+    uint64_t out_per_task = 0, out = UINT64_MAX;      /* hard: bytes of output per task x tasks */
+    uint64_t work = UINT64_MAX;       /* soft: a sub-batch is closed once it HOLDS its share of the work, so no sliver is left over */
+};
+template <class F>
+inline std::vector<chunk_span> cut_spans(size_t n, F cost_of, const span_caps &caps)
+{
+    std::vector<chunk_span> spans;
+    for (size_t a = 0; a < n;) {
+        size_t b = a;
+        uint64_t zb = 0, sb = 0, bb = 0, wb = 0;
+        while (b < n && b - a < caps.tasks) {
+            const span_cost c = cost_of(b);
+            if (b > a && (wb >= caps.work || zb + c.z_probe > caps.z || sb + c.seq > caps.seq || bb + c.bl_probe > caps.bl ||
+                          (uint64_t)(b - a + 1) * caps.out_per_task > caps.out))
+                break;
+            zb += c.z; sb += c.seq; bb += c.bl; wb += c.work;
+            ++b;
+        }
+        spans.push_back(chunk_span{a, b - a});
+        a = b;
+    }
+    return spans;
+}
+
+#endif

@@ -1,21 +1,16 @@
-/*
- * bsw_matesw.hip — host of bsw_matesw_ref_batch: mem_matesw's ksw_align2 (bwamem_pair.c) against the device-resident
- * reference (part of the host side of libbwasw_mi355.so; shared types: bsw_internal.h).
- *
- * Per chunk of tasks:
- *   1. the mates cross PCIe as the caller holds them, in read order (registered memory is DMA'd as it lies, anything else is
- *      gathered into pinned staging, neither reversed nor complemented) and bsw_pack_kernel packs them next to the windows it
- *      fetches from the resident pac: every task is a right-side-only seed, the mate read forwards and the target fetched
- *      upwards from rb, which is bns_get_seq on both strands;
- *   2. bsw_align_kernel (unchanged launch, bsw_align_batch's classes) runs once per class; a task with is_rev carries
- *      BSW_AD_QRC and the kernel builds its query profile from the reverse complement of the stored mate, in the main pass
- *      and in the KSW_XSTART pass, so one launch per class serves both orientations;
+/* bsw_matesw.hip — host of bsw_matesw_ref_batch: mem_matesw's ksw_align2 (bwamem_pair.c) against the device-resident
+ * reference (part of the host side of libbwasw_mi355.so).  Spans, class lists, routing, staging, read-back and the sub-batch
+ * cutter are bsw_f4_host.h's; host-specific here, per chunk of tasks:
+ *   1. how a task is laid out for bsw_pack_kernel: the mate as the caller holds it, in read order, neither reversed nor
+ *      complemented; every task is a right-side-only seed, the mate read forwards and the target fetched upwards from rb, which is
+ *      bns_get_seq on both strands;
+ *   2. bsw_align_kernel (bsw_align_batch's classes) runs once per class; a task with is_rev carries BSW_AD_QRC and the kernel
+ *      builds its query profile from the reverse complement of the stored mate, in the main pass and in the KSW_XSTART pass, so
+ *      one launch per class serves both orientations;
  *   3. mem_matesw's mapping of kswr_t to the region and its keep decision run here on the copied-back results.
- *
  * A chunk runs on a LANE (f4_lane, bsw_internal.h): the context's own for bsw_matesw_ref_batch, a pipeline slot's for the chunks
- * of bsw_matesw_ref_submit_t (bsw_batch.hip: process_f4).
- */
-#include "bsw_internal.h"
+ * of bsw_matesw_ref_submit_t (bsw_batch.hip: process_f4). */
+#include "bsw_f4_host.h"
 
 /* the pack kernel reads a word of a sequence as 20 bytes from the dword below its first byte: forwards up to 16 + 3 bytes past
  * a mate's end */
@@ -45,17 +40,17 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     hipStream_t s = L.s;
     hipError_t he;
     const int64_t l_pac = ref->l_pac;
-    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
-        (he = st.h_desc.reserve(n + 1)) != hipSuccess)
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    int rc = stage_records(e, st, n, true);
+    if (rc) return rc;
     std::vector<bsw_adtask> at(n);
     std::vector<uint8_t> runs(n);
     const int ncls = bsw::align_class_count();
     const align_long_ops *alo = al_mode ? align_long_registered() : nullptr;       /* (al_mode: the call's or the submit's snapshot) */
     const int nall = ncls + (alo ? alo->class_count() : 0);
-    std::vector<uint32_t> order, cnt((size_t)nall + 1, 0), cls(n);
-    uint64_t acc = 0, accb = 0, bacc = 0;
-    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
+    std::vector<uint32_t> cls, ids;                  /* of the tasks that run */
+    class_lists cl;
+    uint64_t acc = 0, bacc = 0;
+    raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
         bsw_dtask &d = st.h_tasks.p[i];
@@ -72,42 +67,24 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
         d.rqlen = (uint16_t)t.l_ms; d.rtlen = (uint16_t)tlen;
         x.xr = t.rb;
         if (rd) r.rq = rd->pos(rtasks[i].read);      /* the mate's first base in the store: read forwards */
-        else {
-            r.rq = (uint32_t)accb; accb += (uint64_t)t.l_ms;
-            if (t.mate < lo) lo = t.mate;
-            if (t.mate + t.l_ms > hi) hi = t.mate + t.l_ms;
-        }
+        else { r.rq = (uint32_t)sp.bytes; sp.add(t.mate, (size_t)t.l_ms); }
         bsw_adtask &a = at[i];
         a.q_off = d.rq_off; a.t_off = d.rt_off; a.qlen = t.l_ms; a.tlen = tlen; a.xtra = t.xtra;
         a.pad = t.is_rev ? BSW_AD_QRC : 0u;
         a.b_off = bacc;
         if (t.xtra & KSW_XSUBO) bacc += (uint64_t)tlen;
-        const int lc = align_long_route(al_mode, t.l_ms, (t.xtra & KSW_XBYTE) != 0);
-        const int c = lc == -1 ? bsw::align_class_of(t.l_ms, (t.xtra & KSW_XBYTE) != 0) : lc < 0 ? -1 : ncls + lc;
-        if (c < 0 || c >= nall) return fail(e, BSW_E_LIMIT, "mate task %zu: no kernel class takes %d bases", i, t.l_ms);
-        cls[i] = (uint32_t)c;
-        ++cnt[(size_t)c + 1];
+        const int c = align_route(al_mode, t.l_ms, (t.xtra & KSW_XBYTE) != 0, ncls, nall);
+        if (c < 0) return fail(e, BSW_E_LIMIT, "mate task %zu: no kernel class takes %d bases", i, t.l_ms);
+        cls.push_back((uint32_t)c);
+        ids.push_back((uint32_t)i);
     }
-    for (int c = 0; c < nall; ++c) cnt[(size_t)c + 1] += cnt[(size_t)c];
-    order.assign(cnt[(size_t)nall], 0u);
-    {
-        std::vector<uint32_t> pos(cnt.begin(), cnt.end() - 1);
-        for (size_t i = 0; i < n; ++i) if (runs[i]) order[pos[cls[i]]++] = (uint32_t)i;
-    }
-    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
-    const bool direct = spanb > 0 && spanb < (1ull << 32) - RAW_SLACK && spanb <= 2 * accb + (1u << 20) && is_registered(lo, spanb);
-    if (direct) {
-        for (size_t i = 0; i < n; ++i) if (runs[i]) st.h_roff.p[i].rq = (uint32_t)(tasks[i].mate - lo);
-    } else if (accb) {
-        if ((he = st.h_raw.reserve((size_t)accb + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
-        for (size_t i = 0; i < n; ++i)
-            if (runs[i]) memcpy(st.h_raw.p + st.h_roff.p[i].rq, tasks[i].mate, (size_t)tasks[i].l_ms);
-    }
-    const size_t rawb = direct ? spanb : (size_t)accb;
-    if ((he = st.d_raw.reserve(rawb + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)acc + 4)) != hipSuccess ||
-        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
-        (he = st.d_desc.reserve(n + 1)) != hipSuccess ||
-        (he = L.a_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
+    cl.build(nall, cls.data(), ids.data(), ids.size());
+    staged_raw raw;
+    rc = stage_raw(e, st, n, sp, acc, true, false, 1, [&](size_t i, int) {
+        return raw_piece{runs[i] ? tasks[i].mate : nullptr, runs[i] ? (size_t)tasks[i].l_ms : 0, &bsw_rawoff::rq, false};
+    }, &raw);
+    if (rc) return rc;
+    if ((he = L.a_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
         (he = L.a_res->reserve(n + 1)) != hipSuccess || (he = L.a_bl->reserve((size_t)bacc + 64)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
     const size_t in_order = (n + 1) * sizeof(bsw_adtask);
@@ -116,32 +93,14 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     std::vector<bsw_kswr> aln(L.h_back ? 0 : n);
     const bsw_kswr *alnp = L.h_back ? (const bsw_kswr *)L.h_back->p : aln.data();      /* a slot reads back into pinned memory */
     drain_on_failure drain(ctx, s, L.ev);
-    if (!order.empty()) {
-        if (rawb) HIPCHK(e, hipMemcpyAsync(st.d_raw.p + RAW_FRONT, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));     /* (resident reads: rawb == 0) */
-        HIPCHK(e, hipMemcpyAsync(st.d_tasks.p, st.h_tasks.p, n * sizeof(bsw_dtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(st.d_roff.p, st.h_roff.p, n * sizeof(bsw_rawoff), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(st.d_desc.p, st.h_desc.p, n * sizeof(bsw_refx), hipMemcpyHostToDevice, s));
+    if (!cl.order.empty()) {
+        if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
         HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, L.dma_src(at.data(), n * sizeof(bsw_adtask), 0), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(order.data(), order.size() * sizeof(uint32_t), in_order), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        L.h2d += rawb + n * (sizeof(bsw_dtask) + sizeof(bsw_rawoff) + sizeof(bsw_refx) + sizeof(bsw_adtask)) + order.size() * sizeof(uint32_t);
-        if (rd) { const int orc = reads_order(e, rd, L.dev, s); if (orc) return orc; }      /* (an upload in flight: s waits for this device's copy) */
-        HIPCHK(e, bsw::launch_pack(rd ? (const uint8_t *)rd->dev(L.dev) : st.d_raw.p + RAW_FRONT, st.d_tasks.p, st.d_roff.p, 0u, (uint32_t)n,
-                                   rd ? BSW_PACK_STORE : 0, ref->d_pac[L.dev], l_pac, st.d_desc.p, st.d_seq.p, nullptr, s));
-        for (int c = 0; c < ncls; ++c) {
-            const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
-            if (!k) continue;
-            HIPCHK(e, bsw::launch_align(c, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.a_bl->p, L.a_res->p, s));
-        }
-        for (int c = ncls; c < nall; ++c) {           /* bsw_align_long_kernel's classes: launched only where a mate was routed */
-            const uint32_t k = cnt[(size_t)c + 1] - cnt[(size_t)c];
-            if (!k) continue;
-            HIPCHK(e, alo->launch(c - ncls, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p + cnt[(size_t)c], k, L.a_bl->p, L.a_res->p, s));
-        }
-        if (L.h_back) HIPCHK(e, hipMemcpyAsync(L.h_back->p, L.a_res->p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost, s));
-        int rc = sync_stream(ctx, e, s, L.ev);
-        if (rc) return rc;
-        if (!L.h_back) HIPCHK(e, hipMemcpy(aln.data(), L.a_res->p, n * sizeof(bsw_kswr), hipMemcpyDeviceToHost));
-        L.d2h += n * sizeof(bsw_kswr);
+        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(cl.order.data(), cl.order.size() * sizeof(uint32_t), in_order), cl.order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        L.h2d += n * sizeof(bsw_adtask) + cl.order.size() * sizeof(uint32_t);
+        if ((rc = stage_pack(e, L, n, 0, ref, rd)) != BSW_OK) return rc;
+        if ((rc = launch_align_lists(e, cl, alo, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p, L.a_bl->p, L.a_res->p, s)) != BSW_OK) return rc;
+        if ((rc = lane_read_back(ctx, e, L, {{L.h_back ? nullptr : aln.data(), L.a_res->p, n * sizeof(bsw_kswr)}})) != BSW_OK) return rc;
     }
     /* mem_matesw: if (aln.score >= opt->min_seed_len && aln.qb >= 0) { b.qb = is_rev? l_ms - (aln.qe + 1) : aln.qb; ... } */
     for (size_t i = 0; i < n; ++i) {
@@ -171,6 +130,14 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     }
     drain.done();
     return BSW_OK;
+}
+
+/* what one task adds to a sub-batch: sequence bytes, a list slice under KSW_XSUBO (the bound is probed with the window either
+ * way), l_ms x (re - rb) cells of work */
+static span_cost mtask_cost(const bsw_mtask &t)
+{
+    const uint64_t tl = t.re > t.rb ? (uint64_t)(t.re - t.rb) : 0;
+    return span_cost{0, (uint64_t)t.l_ms + tl, (t.xtra & KSW_XSUBO) ? tl : 0, (uint64_t)t.l_ms * tl, 0, tl};
 }
 
 /* what both entry points check before anything runs or is queued: the parameters (band and variant are the call's own), then
@@ -215,20 +182,11 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(ctx->device0()));
     f4_lane L = ctx_lane(ctx);
-    for (size_t a = 0; a < n;) {                      /* sub-batches: bsw_align_batch's bounds on the sequence arena and b[] scratch */
-        size_t b = a;
-        uint64_t sb = 0, bb = 0;
-        while (b < n && b - a < (1u << 20)) {
-            const bsw_mtask &t = tasks[b];
-            const uint64_t tl = t.re > t.rb ? (uint64_t)(t.re - t.rb) : 0;
-            if (b > a && (sb + (uint64_t)t.l_ms + tl > (1ull << 31) || bb + tl > (1ull << 28))) break;
-            sb += (uint64_t)t.l_ms + tl;
-            bb += (t.xtra & KSW_XSUBO) ? tl : 0;
-            ++b;
-        }
-        rc = matesw_chunk(ctx, e, L, dp, ref, tasks + a, b - a, res + a, nullptr, nullptr, al_mode);
+    /* sub-batches: bsw_align_batch's bounds on the sequence arena and b[] scratch */
+    const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) { return mtask_cost(tasks[i]); }, span_caps());
+    for (const chunk_span &c : spans) {
+        rc = matesw_chunk(ctx, e, L, dp, ref, tasks + c.base, c.cnt, res + c.base, nullptr, nullptr, al_mode);
         if (rc) return rc;
-        a = b;
     }
     return BSW_OK;
 }
@@ -265,26 +223,10 @@ static int matesw_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, 
     if (rc) return ctx_fail(ctx, e, rc);
     f.ref = ref; f.mtasks = tasks; f.rd = rd; f.rd_mtasks = rtasks; f.n = n; f.mres = res;
     uint64_t total = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
-        if (t.re > t.rb) total += (uint64_t)t.l_ms * (uint64_t)(t.re - t.rb);
-    }
-    const uint64_t wcap = f4_chunk_work(ctx, total, matesw_chunk_work());
-    for (size_t a = 0; a < n;) {                      /* the batch call's bounds, and the work of a chunk */
-        size_t b = a;
-        uint64_t sb = 0, bb = 0, wb = 0;
-        while (b < n && b - a < (1u << 20)) {
-            const bsw_mtask t = mtask_of(tasks, rd, rtasks, b);
-            const uint64_t tl = t.re > t.rb ? (uint64_t)(t.re - t.rb) : 0;
-            if (b > a && (sb + (uint64_t)t.l_ms + tl > (1ull << 31) || bb + tl > (1ull << 28) || wb >= wcap)) break;      /* (a chunk is closed once it HOLDS its share: no sliver is left over) */
-            sb += (uint64_t)t.l_ms + tl;
-            bb += (t.xtra & KSW_XSUBO) ? tl : 0;
-            wb += (uint64_t)t.l_ms * tl;
-            ++b;
-        }
-        f.spans.push_back(chunk_span{a, b - a});
-        a = b;
-    }
+    for (size_t i = 0; i < n; ++i) total += mtask_cost(mtask_of(tasks, rd, rtasks, i)).work;
+    span_caps caps;                                   /* the batch call's bounds, and the work of a chunk */
+    caps.work = f4_chunk_work(ctx, total, matesw_chunk_work());
+    f.spans = cut_spans(n, [&](size_t i) { return mtask_cost(mtask_of(tasks, rd, rtasks, i)); }, caps);
     return pipeline_submit_f4(ctx, std::move(f), ticket, what);
 }
 

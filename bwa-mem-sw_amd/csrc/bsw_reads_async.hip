@@ -16,7 +16,7 @@
  *
  * An upload is no submit: no ticket, no place among BSW_MAX_INFLIGHT; at most BSW_READS_MAX_UPLOADS per context are in flight.
  */
-#include "bsw_internal.h"
+#include "bsw_f4_host.h"
 #include "bsw_reads_pack.h"
 
 #define READS_MAX_WORDS ((1ull << 28) - (1ull << 13))     /* (bsw_reads.hip) */
@@ -65,37 +65,29 @@ static int up_enqueue(errs &e, f4_lane &L, bsw_reads *r, size_t k, bool *queued)
         HIPCHK(e, hipMemsetAsync(r->d_words[L.dev], 0, BSW_READS_SLACK * sizeof(uint64_t), s));
         HIPCHK(e, hipMemsetAsync(store + r->words, 0, BSW_READS_SLACK * sizeof(uint64_t), s));
     }
-    uint64_t bytes = 0;
-    const uint8_t *lo = (const uint8_t *)UINTPTR_MAX, *hi = nullptr;
-    for (size_t i = a; i < b; ++i) {
-        const int32_t len = r->rd[i].len;
-        if (!len) continue;
-        bytes += (uint64_t)len;
-        if (u.src[i] < lo) lo = u.src[i];
-        if (u.src[i] + len > hi) hi = u.src[i] + len;
-    }
+    raw_span sp;
+    for (size_t i = a; i < b; ++i) sp.add(u.src[i], (size_t)r->rd[i].len);
     if ((he = L.h_in->reserve((n + 1) * sizeof(bsw_rdpack_rec))) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     bsw_rdpack_rec *rec = (bsw_rdpack_rec *)L.h_in->p;
-    const size_t spanb = hi ? (size_t)(hi - lo) : 0;
-    const bool direct = spanb > 0 && spanb < (1ull << 32) - BSW_RDPACK_RAW_SLACK && spanb <= 2 * bytes + (1u << 20) && is_registered(lo, spanb);
-    if (!direct && bytes && (he = st.h_raw.reserve((size_t)bytes + BSW_RDPACK_RAW_SLACK)) != hipSuccess)
+    const bool direct = sp.direct(BSW_RDPACK_RAW_SLACK);
+    if (!direct && sp.bytes && (he = st.h_raw.reserve((size_t)sp.bytes + BSW_RDPACK_RAW_SLACK)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     uint64_t acc = 0;
     for (size_t i = a; i < b; ++i) {
         const int32_t len = r->rd[i].len;
         bsw_rdpack_rec &x = rec[i - a];
         x.woff = r->rd[i].woff; x.len = len; x.pad = 0;
-        x.raw_off = !len ? 0u : direct ? (uint32_t)(u.src[i] - lo) : (uint32_t)acc;
+        x.raw_off = !len ? 0u : direct ? (uint32_t)(u.src[i] - sp.lo) : (uint32_t)acc;
         if (len && !direct) memcpy(st.h_raw.p + acc, u.src[i], (size_t)len);
         acc += (uint64_t)len;
     }
-    const size_t rawb = direct ? spanb : (size_t)bytes;
+    const size_t rawb = direct ? sp.span() : (size_t)sp.bytes;
     const size_t rec_words = (n * sizeof(bsw_rdpack_rec) + 7) / 8;
     if ((he = st.d_raw.reserve(rawb + BSW_RDPACK_RAW_SLACK)) != hipSuccess || (he = st.d_blob.reserve(rec_words + 2)) != hipSuccess)
         return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
     *queued = true;
     if (rawb) {
-        HIPCHK(e, hipMemcpyAsync(st.d_raw.p, direct ? lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(st.d_raw.p, direct ? sp.lo : st.h_raw.p, rawb, hipMemcpyHostToDevice, s));
         HIPCHK(e, hipMemcpyAsync(st.d_blob.p, rec, n * sizeof(bsw_rdpack_rec), hipMemcpyHostToDevice, s));
         HIPCHK(e, bsw::launch_reads_pack(st.d_raw.p, (const bsw_rdpack_rec *)st.d_blob.p, (uint32_t)n, store, s));
         L.h2d += rawb + n * sizeof(bsw_rdpack_rec);

@@ -6,6 +6,7 @@
  *   host_f4 f4split WHICH FILE   WHICH = count | z | b: batches that cross one bound of the hosts' sub-batch loops
  *   host_f4 f4scalar             ksw_global2 / ksw_global / ksw_align2 / ksw_align / ksw_extend2 from 12 threads and an offender
  *   host_f4 faults CALL          CALL = global | align | cigar | matesw: every single HIP failure inside that batch call
+ *   host_f4 cuts                 cut_spans (csrc/bsw_f4_host.h), the hosts' sub-batch cutter, with small caps on made-up costs
  *
  * Expected values do not travel the path under test.  The stand-ins compute from the words the host staged; for the global and
  * the local alignment this program calls the oracle on the caller's byte-per-base sequences.  For CIGAR / NM / MD / retries and
@@ -17,6 +18,7 @@
 #include <chrono>
 #include <climits>
 #include "host_common.h"
+#include "../../bwa-mem-sw_amd/csrc/bsw_f4_host.h"
 
 extern "C" void ksw_align2_ref(int qlen, const uint8_t *query, int tlen, const uint8_t *target, int m, const int8_t *mat, int o_del, int e_del,
                                int o_ins, int e_ins, int xtra, int32_t *out, uint64_t *cells);
@@ -910,6 +912,84 @@ static int f4faults_mode(const std::string &call)
     return 0;
 }
 
+/* ---- cuts: the sub-batch cutter on its own.  Every property is stated over the costs, not by cutting a second time: a task joins
+ * a span only while no bound objects (probed with its probe values against what the span has accumulated), and a span that ends
+ * before n ends because a bound objects to the next task.  A round keeps one bound tight and the others out of reach, so that the
+ * bound that closed a span is known. ---- */
+static int cuts_mode()
+{
+    enum { TASKS, Z, SEQ, BL, OUT, WORK, KINDS };
+    const char *names[KINDS] = {"tasks", "z", "seq", "bl", "out", "work"};
+    uint64_t closed_by[KINDS] = {0, 0, 0, 0, 0, 0}, spans_seen = 0;
+    rng_t r(2024);
+    for (int round = 0; round < 6000; ++round) {
+        const int tight = round % (KINDS + 1);                /* KINDS: every bound in reach at once */
+        const size_t n = round < 8 ? (size_t)round / 4 : (size_t)r.below(70);       /* n = 0 and n = 1 first */
+        std::vector<span_cost> c(n);
+        for (span_cost &x : c) {
+            x.z_probe = (uint64_t)r.below(50); x.z = r.below(4) ? x.z_probe : 0;
+            x.bl_probe = (uint64_t)r.below(50); x.bl = r.below(4) ? x.bl_probe : 0;
+            x.seq = (uint64_t)r.below(50); x.work = (uint64_t)r.below(60);
+        }
+        span_caps caps;                                       /* the hosts' own: out of reach of these costs */
+        auto in_reach = [&](int k) { return tight == k || tight == KINDS; };
+        if (in_reach(TASKS)) caps.tasks = (uint64_t)r.in(1, 9);
+        if (in_reach(Z)) caps.z = (uint64_t)r.in(30, 200);
+        if (in_reach(SEQ)) caps.seq = (uint64_t)r.in(30, 200);
+        if (in_reach(BL)) caps.bl = (uint64_t)r.in(30, 200);
+        if (in_reach(OUT)) { caps.out_per_task = (uint64_t)r.in(1, 16); caps.out = (uint64_t)r.in(8, 120); }
+        if (in_reach(WORK)) caps.work = (uint64_t)r.in(1, 300);
+        if (n == 1) {                                         /* one task over every cap: a span of its own */
+            c[0] = span_cost{1000, 1000, 1000, 1000, 1000, 1000};
+            caps.tasks = 1; caps.z = caps.seq = caps.bl = caps.work = 10; caps.out_per_task = 50; caps.out = 10;
+        }
+        const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) { return c[i]; }, caps);
+        CHECK(n || spans.empty(), "cuts: %zu spans for no task", spans.size());
+        CHECK(n != 1 || spans.size() == 1, "cuts: %zu spans for one task", spans.size());
+        size_t at = 0;
+        for (const chunk_span &s : spans) {
+            CHECK(s.base == at && s.cnt >= 1 && s.base + s.cnt <= n, "cuts: span [%zu, +%zu) behind %zu of %zu tasks", s.base, s.cnt, at, n);
+            at += s.cnt;
+            ++spans_seen;
+            /* objections to task j joining what the span holds by then; j == end: to the task behind the span */
+            uint64_t z = 0, sq = 0, bl = 0, wk = 0;
+            auto objections = [&](size_t j, bool *why) {
+                why[TASKS] = j - s.base >= caps.tasks;
+                why[Z] = z + c[j].z_probe > caps.z; why[SEQ] = sq + c[j].seq > caps.seq; why[BL] = bl + c[j].bl_probe > caps.bl;
+                why[OUT] = (uint64_t)(j - s.base + 1) * caps.out_per_task > caps.out;
+                why[WORK] = wk >= caps.work;
+                int k = 0;
+                for (int i = 0; i < KINDS; ++i) k += why[i] ? 1 : 0;
+                return k;
+            };
+            bool why[KINDS];
+            for (size_t j = s.base; j < s.base + s.cnt; ++j) {
+                if (j > s.base) {
+                    CHECK(objections(j, why) == 0, "cuts: task %zu joined span [%zu, +%zu) over a bound (round %d)", j, s.base, s.cnt, round);
+                    CHECK(wk < caps.work, "cuts: span [%zu, +%zu) went on at task %zu with its work target reached", s.base, s.cnt, j);
+                }
+                z += c[j].z; sq += c[j].seq; bl += c[j].bl; wk += c[j].work;
+            }
+            if (s.cnt > 1)                                    /* no hard cap is exceeded but by a single task */
+                CHECK(s.cnt <= caps.tasks && z <= caps.z && sq <= caps.seq && bl <= caps.bl && (uint64_t)s.cnt * caps.out_per_task <= caps.out,
+                      "cuts: span [%zu, +%zu) exceeds a hard cap (round %d)", s.base, s.cnt, round);
+            if (s.base + s.cnt < n) {
+                const int k = objections(s.base + s.cnt, why);
+                CHECK(k >= 1, "cuts: span [%zu, +%zu) of %zu tasks was closed with room for the next task (round %d)", s.base, s.cnt, n, round);
+                if (tight == WORK) CHECK(why[WORK] && wk >= caps.work && wk - c[s.base + s.cnt - 1].work < caps.work,
+                                         "cuts: span [%zu, +%zu) holds %llu of work under a target of %llu", s.base, s.cnt, (unsigned long long)wk, (unsigned long long)caps.work);
+                if (k == 1)
+                    for (int i = 0; i < KINDS; ++i) closed_by[i] += why[i] ? 1 : 0;
+            }
+        }
+        CHECK(at == n, "cuts: the spans cover %zu of %zu tasks", at, n);
+    }
+    for (int i = 0; i < KINDS; ++i) CHECK(closed_by[i] >= 20, "cuts: the %s bound alone closed %llu spans", names[i], (unsigned long long)closed_by[i]);
+    printf("cuts: ok, %llu spans, closed by tasks %llu z %llu seq %llu bl %llu out %llu work %llu\n", (unsigned long long)spans_seen, (unsigned long long)closed_by[TASKS],
+           (unsigned long long)closed_by[Z], (unsigned long long)closed_by[SEQ], (unsigned long long)closed_by[BL], (unsigned long long)closed_by[OUT], (unsigned long long)closed_by[WORK]);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const std::string mode = argc > 1 ? argv[1] : "";
@@ -917,6 +997,7 @@ int main(int argc, char **argv)
     if (mode == "f4split" && argc > 3) return f4split_mode(argv[2], argv[3]);
     if (mode == "f4scalar") return f4scalar_mode();
     if (mode == "faults" && argc > 2) return f4faults_mode(argv[2]);
-    fprintf(stderr, "usage: host_f4 f4 FILE | f4split count|z|b FILE | f4scalar | faults global|align|cigar|matesw\n");
+    if (mode == "cuts") return cuts_mode();
+    fprintf(stderr, "usage: host_f4 f4 FILE | f4split count|z|b FILE | f4scalar | faults global|align|cigar|matesw | cuts\n");
     return 2;
 }

@@ -19,6 +19,7 @@
 #include <climits>
 #include <memory>
 #include "host_common.h"
+#include "../../bwa-mem-sw_amd/csrc/bsw_f4_host.h"      /* (host_f4.cpp's, for its cuts mode: in before the namespace opens) */
 
 namespace f4s {                                      /* (its main() becomes f4s::main; the headers above are in already) */
 #include "host_f4_stream.cpp"

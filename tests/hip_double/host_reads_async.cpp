@@ -19,6 +19,7 @@
 #include <climits>
 #include <memory>
 #include "host_common.h"
+#include "../../bwa-mem-sw_amd/csrc/bsw_f4_host.h"      /* (host_f4.cpp's, for its cuts mode: in before the namespace opens) */
 #include "launchers_reads.h"
 
 namespace hr {                                       /* (its main() becomes hr::main; the headers above are in already) */

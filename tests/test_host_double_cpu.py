@@ -406,3 +406,15 @@ def test_every_single_hip_failure_in_an_f4_batch_call(san, call):
     out, _ = run(san, "host_f4", "faults", call)
     m = re.search(r"faults %s: C = (\d+), injection points visited = (\d+), failed calls (\d+), ignored releases (\d+), skipped 0" % call, out.stdout)
     assert m and int(m.group(1)) == int(m.group(2)) and int(m.group(1)) >= 40 and int(m.group(3)) >= 36, out.stdout[-800:]
+
+
+@pytest.mark.parametrize("san", SANS)
+def test_the_sub_batch_cutter_on_made_up_costs(san):
+    """cut_spans (csrc/bsw_f4_host.h), which cuts all four batch calls and both ticketed submits, called directly with small caps
+    on made-up costs: the spans are contiguous and cover [0, n); no span exceeds a hard cap unless it is a single task; a span
+    under a work target closes at the first task boundary at or past the target and not before; each of the five hard bounds
+    (tasks, backtrack bytes, sequence bytes, list entries, output bytes) and the work target closes spans on its own — the
+    sequence-byte bound too, which no batch of the other programs reaches; n = 0 yields no span, one task over every cap one."""
+    out, _ = run(san, "host_f4", "cuts")
+    m = re.search(r"cuts: ok, (\d+) spans, closed by tasks (\d+) z (\d+) seq (\d+) bl (\d+) out (\d+) work (\d+)", out.stdout)
+    assert m and all(int(x) >= 20 for x in m.groups()), out.stdout[-600:]

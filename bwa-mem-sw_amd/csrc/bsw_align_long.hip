@@ -1,7 +1,7 @@
 /*
  * bsw_align_long.hip — the switch of ksw_align2's long-query route (bsw_set_align_long, BSW_ALIGN_LONG), its launch counters,
- * and the one place that names the launcher of the companion library libbwasw_mi355_alnl.so (part of the host side of
- * libbwasw_mi355.so; shared types: bsw_internal.h).
+ * and the one place that names the launcher of bsw_align_long_kernel.hip (part of the host side of libbwasw_mi355.so; shared
+ * types: bsw_internal.h).
  *
  * The hosts of the local alignment (bsw_f4.hip, bsw_matesw.hip) never refer to launch_align_long: they hold a pointer to the
  * table below, which this unit registers when the library is loaded.  A program that links those two units without this one (the

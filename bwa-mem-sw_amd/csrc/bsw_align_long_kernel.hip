@@ -1,7 +1,6 @@
 /*
  * bsw_align_long_kernel.hip — bwa's striped local alignment ksw_align2 (ksw_u8 / ksw_i16) for queries the register kernel
- * (bsw_align_kernel.hip) cannot hold: up to BSW_ALIGN_LONG_MAX_QLEN = 8 191 bases.  The opt-in of bsw_set_align_long; built
- * into the companion library libbwasw_mi355_alnl.so, so that the kernel set of libbwasw_mi355.so stays what the tests pin.
+ * (bsw_align_kernel.hip) cannot hold: up to BSW_ALIGN_LONG_MAX_QLEN = 8 191 bases.  The opt-in of bsw_set_align_long.
  *
  * Everything the results depend on is bsw_align_kernel's: ONE 16-LANE DPP ROW PLAYS ONE __m128i (16 byte lanes, or two
  * alignments of 8 word lanes), query position k sits in vector k % slen, lane k / slen, E is taken from H before the lazy-F

@@ -505,7 +505,7 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
                            bsw_mresult *res, const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr, int al_mode = 0);
 
 /* ---- bsw_f4.hip: the long-query route of ksw_align2 (bsw_set_align_long).  bsw_align_long.hip, the unit that owns the switch and
- * names the launcher of the companion library, registers this table when the library is loaded; a program linked without that
+ * names the launcher of bsw_align_long_kernel.hip, registers this table when the library is loaded; a program linked without that
  * unit keeps the NULL pointer, which means "mode 0 only".  The hosts (align_chunk, matesw_chunk) read the mode ONCE per call or
  * submit, in the caller's thread, and route by that snapshot: a task of more than BSW_ALIGN_MAX_QLEN bases that passed the check goes
  * to `launch` whatever the switch says by the time its chunk runs. ---- */

@@ -10,11 +10,11 @@
  * dispatch, result records.  As in bsw_lane_kernel.hip only the first band try runs here; bsw_pair_finalize
  * sends seeds that need MAX_BAND_TRY's second pass to the wave-per-task kernel.
  *
- * Compiled a second time with -DBSW_L2_RTL_TU (Makefile) into the companion library libbwasw_mi355_rtl2.so: the same shell
- * — slot pair per lane, stand-in for empty slots, match words and N planes in LDS, target staging, row_begin2, pair_result —
- * around the variant-RTL row (l2::lane2r), as bsw_lane2_rtl_kernel<QB, WPS, SYM> for the 72- and the 136-column class.  That
- * unit holds nothing else: the kernel set of the main library stays what it is (bsw_quad_rtl.o is the precedent), and its
- * block bodies come from the C++ cell(), not from bsw_lane2_body_asm.inc.
+ * Compiled a second time with -DBSW_L2_RTL_TU (Makefile) into bsw_lane2_rtl.o: the same shell — slot pair per lane, stand-in
+ * for empty slots, match words and N planes in LDS, target staging, row_begin2, pair_result — around the variant-RTL row
+ * (l2::lane2r), as bsw_lane2_rtl_kernel<QB, WPS, SYM> for the 72- and the 136-column class.  That unit holds nothing else: the
+ * #ifdef below keeps each host function in one of the two objects (bsw_quad_rtl.o is the precedent), and its block bodies come
+ * from the C++ cell(), not from bsw_lane2_body_asm.inc.
  */
 #include <hip/hip_runtime.h>
 #include <limits.h>

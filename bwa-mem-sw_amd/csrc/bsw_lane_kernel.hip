@@ -478,8 +478,7 @@ static hipError_t launch_lane_k(int cls, int variant, const bsw_dparams &P, int 
                                 const uint32_t *order, uint32_t n, bsw_result *out, hipStream_t s, uint32_t *&tail_flag, uint32_t *tail_target, const bsw_fin *fin);
 
 /* ---- variant RTL on the packed kernels: a process-wide opt-in (bsw_set_rtl_packed, BSW_RTL_PACKED=1) ----
- * bsw_lane2_rtl_kernel lives in the companion library libbwasw_mi355_rtl2.so (bsw_lane2_kernel.hip compiled with
- * -DBSW_L2_RTL_TU).  The route sits below launch_lane: lane2_params_ok(P, RTL) stays false, so the fused launches, the group
+ * bsw_lane2_rtl_kernel is bsw_lane2_kernel.hip compiled a second time with -DBSW_L2_RTL_TU (bsw_lane2_rtl.o).  The route sits below launch_lane: lane2_params_ok(P, RTL) stays false, so the fused launches, the group
  * kernel, lane_class_finishes, the N-list policy and the launch-count planning see RTL as before, and with the switch off
  * every launch is the one it was. */
 hipError_t launch_lane2_rtl(int qb, const bsw_dparams &P, int side, const uint64_t *seq, const bsw_dtask *tasks, const uint32_t *order,

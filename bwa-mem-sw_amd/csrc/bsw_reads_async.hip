@@ -8,7 +8,7 @@
  * device on that device's queue (pipeline_submit_job, bsw_batch.hip).  A piece runs on a slot like a CIGAR or rescue chunk: the
  * slot's extension chunk in flight is handed over, the bytes cross PCIe as they lie (registered memory: one DMA of the span;
  * anything else: gathered into the slot's pinned staging), the records {raw offset, woff, len} follow through the slot's pinned
- * h_in, bsw_reads_pack_kernel (companion library) packs them into that device's copy, and an event is recorded behind it.
+ * h_in, bsw_reads_pack_kernel packs them into that device's copy, and an event is recorded behind it.
  * A chunk that names the block makes its stream wait for those events (reads_order, bsw_internal.h): the order is kept on the
  * GPU, the slot thread only waits until the pieces of its device — which sit ahead of it in the same FIFO queue and wait for
  * nothing — have been enqueued.  The piece then waits for its own work (watchdog), so the slot's staging and the caller's bases

@@ -81,7 +81,7 @@ BSW_HD uint64_t bsw_rdpack_word(const uint8_t *raw, uint32_t raw_off, int len, i
 #include <hip/hip_runtime.h>
 namespace bsw {
 /* store[rec[i].woff + k] = word k of read i, for the n reads of a piece; raw: 16-byte aligned, BSW_RDPACK_RAW_SLACK behind it.
- * (bsw_reads_pack_kernel.hip, in the companion library libbwasw_mi355_rdpack.so) */
+ * (bsw_reads_pack_kernel.hip) */
 hipError_t launch_reads_pack(const uint8_t *raw, const bsw_rdpack_rec *rec, uint32_t n, uint64_t *store, hipStream_t s);
 }  // namespace bsw
 #endif

@@ -1,7 +1,6 @@
 /*
  * bsw_reads_pack_kernel.hip — the device side of bsw_reads_upload_start: a piece of a read block, one byte per base as it crossed
- * PCIe, becomes its part of the resident read store (4 bits per base, every read on a word boundary).  Built into the companion
- * library libbwasw_mi355_rdpack.so, so that the kernel set of libbwasw_mi355.so stays what the tests pin.
+ * PCIe, becomes its part of the resident read store (4 bits per base, every read on a word boundary).
  *
  * Bound by memory: 1 byte per base in, half a byte out.  A group of BSW_RDPACK_GROUP lanes takes a read and lane l produces its
  * words l, l + 16, ...: the lanes of a group load neighbouring 16-byte lines of the read and store neighbouring 8-byte words.

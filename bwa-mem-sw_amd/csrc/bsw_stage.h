@@ -80,7 +80,7 @@ int align_class_count();
 int align_class_of(int qlen, int byte_mode);                 /* -1: query too long for the mode */
 hipError_t launch_align(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,
                         unsigned long long *blist, bsw_kswr *out, hipStream_t s);
-/* the same alignment with its rows in LDS (bsw_align_long_kernel.hip, in the companion library libbwasw_mi355_alnl.so): queries
+/* the same alignment with its rows in LDS (bsw_align_long_kernel.hip): queries
  * up to BSW_ALIGN_LONG_MAX_QLEN bases, classes by (mode, slen bound), launch_align's arguments.  The hosts reach these three
  * through align_long_ops (bsw_internal.h) only, never by name. */
 int align_long_class_count();

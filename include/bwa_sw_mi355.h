@@ -208,7 +208,7 @@ void bsw_scalar_stats(uint64_t *calls, uint64_t *trips);
  * Process-wide and atomic; applies to the launches enqueued afterwards.  Initially 1 when the environment variable
  * BSW_RTL_PACKED is "1", else 0.  With the switch on, the lane-list sides of variant RTL whose class is the 72- or the
  * 136-column 8-bit class, under scoring parameters in the packed range (a bwa-style matrix, a + b < 256, o + e < 256 per gap
- * kind), run on bsw_lane2_rtl_kernel (libbwasw_mi355_rtl2.so) instead of the one-seed-per-lane kernel, through every entry
+ * kind), run on bsw_lane2_rtl_kernel instead of the one-seed-per-lane kernel, through every entry
  * point that builds lane lists; results are the same bytes.  The 232-column and the 16-bit class, parameters outside that
  * range, and variants H and M are not affected. */
 void bsw_set_rtl_packed(int on);
@@ -224,7 +224,7 @@ int  bsw_rtl_packed_stats(uint64_t *launches, int cap);
  *   0  a query beyond BSW_ALIGN_MAX_QLEN is refused: BSW_E_LIMIT from the batch calls, score -1 from ksw_align2 / ksw_align.
  *   1  ksw_align2, ksw_align, bsw_align_batch, bsw_matesw_ref_batch, bsw_matesw_ref_submit_t and bsw_matesw_reads_submit_t accept
  *      queries (mates) up to BSW_ALIGN_LONG_MAX_QLEN bases; those beyond BSW_ALIGN_MAX_QLEN run on bsw_align_long_kernel
- *      (libbwasw_mi355_alnl.so: the rows of H, E and Hmax in LDS), shorter ones on bsw_align_kernel as before.  Results are the
+ *      (the rows of H, E and Hmax in LDS), shorter ones on bsw_align_kernel as before.  Results are the
  *      same bit-exact ksw_u8 / ksw_i16 values.  Beyond BSW_ALIGN_LONG_MAX_QLEN: BSW_E_LIMIT still.
  *   2  as 1, and every alignment runs on bsw_align_long_kernel, the short ones too (tests, rate comparisons).
  * Any other value sets 0. */

@@ -13,6 +13,7 @@ A case:
   ctx      BswContext settings (kernel, streams, chunk_tasks, result_format)
   entry    extend_pairs | upload_run (upload / run / download) | packed_registered (extend_pairs_packed from registered memory)
            | wire (bsw_refbatch_run) | global_batch | align_batch | cigar_ref_batch
+           | reads_upload_async (bsw_reads_upload_start / bsw_reads_wait / bsw_reads_image)
   params   overrides of default_params, and the matrix (a, b, n) in `mat`
   gen      seeded generator: gen(rng) -> the workload of the entry point
   ref      what the results are compared with, bit for bit
@@ -44,6 +45,18 @@ def lane(qb, v, sym, b8, wps):
 
 def lane2(qb, wps, vm, sym, fused):
     return NS + "bsw_lane2_kernel<%d, %d, %s, %s, %s>" % (qb, wps, _b(vm), _b(sym), _b(fused))
+
+
+def lane2_rtl(qb, wps, sym):
+    return NS + "bsw_lane2_rtl_kernel<%d, %d, %s>" % (qb, wps, _b(sym))
+
+
+def align_long(byte):
+    return NS + "bsw_align_long_kernel<%s>" % _b(byte)
+
+
+def reads_pack():
+    return NS + "bsw_reads_pack_kernel"
 
 
 def lane2l(qb, vm, sym):
@@ -250,6 +263,16 @@ for vm in (False, True):
         add(_ext("group_fused_wide_" + tag, [lane2g(4, 2, vm, sym, True)], 600, [(1, 135), (136, 231)], dict(bits=8),
                  dict(EXTP, **_pen(vm, sym)), env=dict(BSW_GROUP="1", BSW_GROUP_FUSE="1")))
 
+# BSW_RTL_PACKED=1: variant RTL on the two-seeds-per-lane kernels, shared and separate gap penalties.  As for lane2_72_* above
+# the 72-column class is launched only for a chunk whose 8-bit sides are all short (a mixed chunk folds it into the 136-column
+# class), so each penalty set takes a chunk of short sides and a mixed one.  Every default edge is kept: the RTL reference
+# produces each of them on these workloads.
+for sym in (True, False):
+    tag = "sym" if sym else "asym"
+    pen = dict(EXTP, mat=(1, 4, -1), variant=RTL, **(SYM if sym else ASYM))
+    add(_ext("rtl_packed_72_" + tag, [lane2_rtl(9, 3, sym)], 300, [(1, 71)], dict(bits=8), pen, env=dict(BSW_RTL_PACKED="1")))
+    add(_ext("rtl_packed_136_" + tag, [lane2_rtl(17, 2, sym)], 600, [(1, 71), (72, 135)], dict(bits=8), pen, env=dict(BSW_RTL_PACKED="1")))
+
 # BSW_NSPLIT=1: lane seeds with an N in a query go to the general kernel's N list (bsw_nlist_count sizes its launch)
 add(_ext("nsplit", [NS + "bsw_nlist_count"], 800, [(1, 135)], dict(bits=8, nrate=0.02), dict(EXTP, **ASYM),
          env=dict(BSW_NSPLIT="1")))
@@ -321,6 +344,65 @@ def align_pairs(rng):
 
 add(dict(name="align", targets=tuple(NS + "bsw_align_kernel<%d, %s>" % (s, _b(b)) for b, s in ALIGN_CLASSES), env={}, ctx=dict(kernel=AUTO),
          entry="align_batch", params=dict(SYM), gen=align_pairs, ref="oracle.align2_batch (every field)", seed=0, edges=()))
+
+
+ALIGN_LONG_QLENS = (1025, 2048, 2049, 4097, 8191)     # the first long query, and both sides of the class edges above it
+
+
+def align_long_pairs(rng):
+    """per length and mode two queries (the second with an N), flags drawn as in align_pairs; the target is a mutated piece of
+    the query between two flanks, a few hundred bases: the rows of the alignment are the query's, its time the target's"""
+    pairs, xt = [], []
+    for ql in ALIGN_LONG_QLENS:
+        for byte in (1, 0):
+            for k in range(2):
+                q = rng.integers(0, 4, ql).astype(np.uint8)
+                a0 = int(rng.integers(0, ql - 300 + 1))
+                piece = _mutated(rng, q[a0:a0 + 300], 300, 0.05, 0.02)
+                t = np.concatenate([rng.integers(0, 4, int(rng.integers(0, 60))), piece, rng.integers(0, 4, int(rng.integers(0, 60)))]).astype(np.uint8)
+                if k == 1:
+                    q[rng.integers(0, ql)] = 4
+                x = (XB if byte else 0) | int(rng.choice([0, XSTART, XSUBO | 19, XSUBO | XSTART | 19, XSTOP | 25]))
+                pairs.append((q, t))
+                xt.append(x)
+    return pairs, xt
+
+
+# BSW_ALIGN_LONG=1: queries of more than 1 024 bases on the LDS-row kernel, both modes
+add(dict(name="align_long", targets=(align_long(True), align_long(False)), env=dict(BSW_ALIGN_LONG="1"), ctx=dict(kernel=AUTO),
+         entry="align_batch", params=dict(SYM), gen=align_long_pairs, ref="oracle.align2_batch (every field)", seed=0, edges=()))
+
+READS_LENS = (1, 15, 16, 17, 31, 32, 33, 150, 250)
+
+
+def reads_block(rng):
+    """(raw, lens, offs): about 300 reads back to back in one raw buffer (read i = raw[offs[i]:offs[i] + lens[i]]), Ns at 2 %.
+    Sixteen reads of 17 bases in a row put a read's first byte at every offset modulo 16 of the raw buffer, whether the upload
+    sends the buffer as it lies or gathers the reads (both keep them back to back)."""
+    lens = [int(n) for n in READS_LENS] * 28 + [int(n) for n in rng.integers(1, 401, 32)]
+    rng.shuffle(lens)
+    lens = np.array(lens[:150] + [17] * 16 + lens[150:], dtype=np.int32)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    raw = rng.integers(0, 4, int(lens.sum())).astype(np.uint8)
+    raw[rng.random(len(raw)) < 0.02] = 4
+    return raw, lens, offs
+
+
+def reads_image(raw, lens, offs, slack):
+    """the block's device image in numpy: 16 bases per uint64, base k in bits [4k, 4k+3], codes above 4 stored as 4, every read
+    on a word boundary, the nibbles behind a read's last base zero, `slack` zero words in front and behind"""
+    words = [np.zeros(slack, np.uint64)]
+    for n, o in zip(lens, offs):
+        b = np.zeros((int(n) + 15) // 16 * 16, dtype=np.uint64)
+        b[:n] = np.minimum(raw[o:o + n], 4)
+        words.append((b.reshape(-1, 16) << (4 * np.arange(16, dtype=np.uint64))).sum(axis=1, dtype=np.uint64))
+    return np.concatenate(words + [np.zeros(slack, np.uint64)])
+
+
+# the asynchronous read-block upload: the raw bytes packed on the device.  (Every block with a base launches the kernel, from
+# any kind of host memory; the reads here lie in pageable memory.)
+add(dict(name="reads_upload_async", targets=(reads_pack(),), env={}, ctx=dict(kernel=AUTO), entry="reads_upload_async", params=dict(),
+         gen=reads_block, ref="the image of bsw_reads_upload and a numpy packing of the bases (byte for byte)", seed=0, edges=()))
 
 
 def cigar_specs(rng):

@@ -91,6 +91,25 @@ def run_other(host, orc, case):
             finally:
                 c.ref_free(ref)
             return len(specs)
+        if case["entry"] == "reads_upload_async":
+            raw, lens, offs = L.workload(case)
+            reads = [raw[o:o + n] for o, n in zip(offs, lens)]
+            rd = c.reads_upload_start(reads)
+            try:
+                c.reads_wait(rd)
+                got = c.reads_image(rd)
+            finally:
+                c.reads_free(rd)
+            rd = c.reads_upload(reads)
+            try:
+                sync = c.reads_image(rd)
+            finally:
+                c.reads_free(rd)
+            slack = (len(got) - sum((int(n) + 15) // 16 for n in lens)) // 2
+            want = L.reads_image(raw, lens, offs, slack)
+            assert slack > 0 and got.tobytes() == sync.tobytes(), np.nonzero(got != sync)[0][:5]
+            assert got.tobytes() == want.tobytes(), np.nonzero(got != want)[0][:5]
+            return len(reads)
     raise ValueError(case["entry"])
 
 

@@ -1,23 +1,19 @@
-"""Build audit of ksw_align2's long-query route: bsw_align_long_kernel lives in a companion library of its own next to
-libbwasw_mi355.so (whose kernel set is pinned by test_reads_build_cpu.py and test_kernel_ledger_cpu.py), the main library exports
-the three calls, lists the companion as needed and finds it next to itself, the ABI version is unchanged, and no kernel of the
-main library changed."""
-import json
+"""Build audit of ksw_align2's long-query route: libbwasw_mi355.so (whose kernel set is pinned by test_reads_build_cpu.py and
+test_kernel_ledger_cpu.py) holds the two instantiations of bsw_align_long_kernel without scratch, exports the three calls and
+needs no second library, and the ABI version is unchanged."""
 import os
 import re
 import subprocess
 
-from test_reads_build_cpu import kernel_metadata
+from test_reads_build_cpu import ALIGN_LONG_KERNEL, assert_no_second_library, kernel_metadata, kernels_matching
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-READELF = "/opt/rocm/llvm/bin/llvm-readelf"
-COMPANION = "libbwasw_mi355_alnl.so"
 NEW = ("bsw_set_align_long", "bsw_align_long", "bsw_align_long_stats")
 
 
 def class_geometry(so):
     """[(byte mode, slen bound, alignments per workgroup, LDS bytes per alignment, LDS bytes per workgroup)] per class, as the
-    built companion's launcher computes them (bsw_alnl_class_geometry)"""
+    built library's launcher computes them (bsw_alnl_class_geometry)"""
     import ctypes as C
     lib = C.CDLL(so)
     fn = lib.bsw_alnl_class_geometry
@@ -32,18 +28,14 @@ def class_geometry(so):
         cls += 1
 
 
-def test_companion_holds_only_the_long_kernel_without_scratch(built):
-    so = os.path.join(os.path.dirname(built.lib_path()), COMPANION)
-    assert os.path.exists(so)
-    meta = kernel_metadata(so)
+def test_library_holds_the_two_long_kernels_without_scratch(built):
+    meta = kernels_matching(kernel_metadata(built.lib_path()), ALIGN_LONG_KERNEL)
     assert len(meta) == 2, sorted(meta)                              # 8-bit and 16-bit mode
     for name, (vgpr, sgpr, scratch) in sorted(meta.items()):
         print("%s: vgpr_count %d sgpr_count %d scratch %d" % (name, vgpr, sgpr, scratch))
-        assert re.match(r"_ZN3bsw21bsw_align_long_kernelILb[01]EEE", name), name
         assert scratch == 0
         assert vgpr <= 64                                            # the rows live in LDS, not in registers: eight waves per SIMD fit
-    built.host.lib()                                                 # (the companion's own dependencies are loaded)
-    geo = class_geometry(so)
+    geo = class_geometry(built.lib_path())
     assert [(g[0], g[1]) for g in geo] == [(1, b) for b in (16, 32, 64, 128, 256, 512)] + [(0, b) for b in (32, 64, 128, 256, 512, 1024)]
     for byte, slen, apb, per, wg in geo:
         lanes = 16 if byte else 8
@@ -54,26 +46,15 @@ def test_companion_holds_only_the_long_kernel_without_scratch(built):
         assert wg == apb * per and wg <= 160 << 10 and 1 <= apb * lanes <= 256
         assert apb * lanes >= 64 or 2 * wg > 160 << 10               # less than a wavefront only where LDS leaves no room for more
     assert [g[2] for g in geo if g[1] * (16 if g[0] else 8) == 8192] == [2, 2]      # the largest class of each mode: two alignments
-    syms = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
-    assert re.search(r" T _ZN3bsw17launch_align_longE", syms)
-    assert re.search(r" T _ZN3bsw19align_long_class_ofE", syms) and re.search(r" T _ZN3bsw22align_long_class_countE", syms)
 
 
-def test_main_library_exports_the_three_calls_and_needs_the_companion(built):
+def test_main_library_exports_the_three_calls_and_stands_alone(built):
     syms = subprocess.check_output(["nm", "-D", "--defined-only", built.lib_path()], text=True)
     for f in NEW:
         assert re.search(r" T %s$" % f, syms, re.M), f
         assert f in built.host.EXPORTS, f
         assert hasattr(built.host.lib(), f)
-    dyn = subprocess.check_output([READELF, "-d", built.lib_path()], text=True)
-    assert re.search(r"NEEDED.*\[%s\]" % re.escape(COMPANION), dyn)
-    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn)
-    assert not [k for k in kernel_metadata(built.lib_path()) if "bsw_align_long_kernel" in k]
-
-
-def test_main_librarys_kernels_are_exactly_the_golden_set(built):
-    before = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_resources_before_reads.json")))
-    assert set(kernel_metadata(built.lib_path())) == set(before)
+    assert_no_second_library(built)
 
 
 def test_abi_version_stays_6_and_the_header_declares_the_calls(built):

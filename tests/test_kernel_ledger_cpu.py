@@ -65,7 +65,8 @@ def test_ledger_covers_the_build(build_kernels):
 def test_cases_are_well_formed():
     names = [c["name"] for c in L.CASES]
     assert len(names) == len(set(names)), "case names must be unique"
-    entries = {"extend_pairs", "upload_run", "packed_registered", "wire", "global_batch", "align_batch", "cigar_ref_batch"}
+    entries = {"extend_pairs", "upload_run", "packed_registered", "wire", "global_batch", "align_batch", "cigar_ref_batch",
+               "reads_upload_async"}
     for c in L.CASES:
         assert c["targets"] and c["ref"] and callable(c["gen"]), c["name"]
         assert c["entry"] in entries, c["name"]
@@ -114,3 +115,22 @@ def test_workload_is_non_vacuous(host, oracle, case):
         got["bound16"] = int(((top >= 64936) & (top < 65000) & (qm + 1 <= L.L16_COLS)).sum())
     print(case["name"], len(tasks), got)
     assert all(v > 0 for v in got.values()), (case["name"], sorted(got.items()))
+
+
+def test_reads_block_is_what_it_claims(host):
+    """every length the case names, Ns, a read at every offset modulo 16 of the raw buffer; and the numpy image is the device
+    sequence format as bsw_pack_bases makes it, read by read"""
+    case, = [c for c in L.CASES if c["entry"] == "reads_upload_async"]
+    raw, lens, offs = L.workload(case)
+    assert 290 <= len(lens) <= 310 and set(L.READS_LENS) <= set(lens.tolist()) and 250 < lens.max() <= 400
+    assert set((offs & 15).tolist()) == set(range(16))
+    assert 0.01 < (raw == 4).mean() < 0.03
+    img = L.reads_image(raw, lens, offs, 2)
+    assert len(img) == sum((int(n) + 15) // 16 for n in lens) + 4 and not img[:2].any() and not img[-2:].any()
+    at = 2
+    for n, o in zip(lens, offs):
+        w = np.full((int(n) + 15) // 16, 0xdeadbeef, dtype=np.uint64)
+        r = np.ascontiguousarray(raw[o:o + n])
+        host.lib().bsw_pack_bases(r.ctypes.data, int(n), w.ctypes.data)
+        assert (img[at:at + len(w)] == w).all(), (n, o)
+        at += len(w)

@@ -1,7 +1,12 @@
 """Build audit of the resident-read source of bsw_pack_kernel: the kernel may not need more register allocation blocks or
 scratch than before it learnt BSW_PACK_STORE, and no other kernel of the library may have changed at all.  The numbers of the
 parent build are code object metadata (vgpr_count, sgpr_count, private_segment_fixed_size) of its libbwasw_mi355.so:
-bsw_pack_kernel's below, every kernel's in tests/golden/kernel_resources_before_reads.json."""
+bsw_pack_kernel's below, every kernel's in tests/golden/kernel_resources_before_reads.json.
+
+This file is also the build pin of the library's kernel set: the golden kernels plus ADDED, the kernels that came after the
+golden file, each a mangled-name pattern with the exact number of instantiations (added_kernels).  A new kernel gets a line in
+ADDED (and a case in tests/_kernel_ledger.py); the audits of the features that brought the kernels import the pin from here."""
+import glob
 import json
 import os
 import re
@@ -14,6 +19,11 @@ READELF = "/opt/rocm/llvm/bin/llvm-readelf"
 BUNDLE = b"__CLANG_OFFLOAD_BUNDLE__"
 PACK = "_ZN3bsw15bsw_pack_kernelEPKhPK9bsw_dtaskPK10bsw_rawoffjjiS1_lPK8bsw_refxPmPh"
 PACK_BEFORE = (34, 43, 0)          # vgpr_count, sgpr_count, private_segment_fixed_size in the parent build
+# the kernels that are not in the golden file: (mangled-name pattern, number of instantiations)
+RTL2_KERNEL = r"_ZN3bsw20bsw_lane2_rtl_kernelILi(9|17)ELi(3|2)ELb[01]EEE"
+READS_PACK_KERNEL = r"_ZN3bsw21bsw_reads_pack_kernelE"
+ALIGN_LONG_KERNEL = r"_ZN3bsw21bsw_align_long_kernelILb[01]EEE"
+ADDED = ((RTL2_KERNEL, 4), (READS_PACK_KERNEL, 1), (ALIGN_LONG_KERNEL, 2))
 
 
 def kernel_metadata(so_path):
@@ -46,21 +56,60 @@ def kernel_metadata(so_path):
     return out
 
 
+def golden():
+    """read, not rewritten: the kernels of the build before the resident read store"""
+    return {k: tuple(v) for k, v in json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_resources_before_reads.json"))).items()}
+
+
+def kernels_matching(meta, pattern):
+    return {k: v for k, v in meta.items() if re.match(pattern, k)}
+
+
+def added_kernels(meta):
+    """the names in meta that ADDED's patterns match, each pattern with exactly its count"""
+    out = set()
+    for pattern, count in ADDED:
+        names = set(kernels_matching(meta, pattern))
+        assert len(names) == count, (pattern, sorted(names))
+        out |= names
+    return out
+
+
+def assert_kernel_set_is_pinned(got):
+    """the library's kernels are the golden ones plus ADDED, and bsw_pack_kernel alone may differ from the golden file"""
+    before = golden()
+    assert set(got) == set(before) | added_kernels(got)      # no kernel added or removed, instantiations included
+    changed = {k: (before[k], got[k]) for k in before if k != PACK and got[k] != before[k]}
+    assert not changed, changed
+
+
+def assert_no_second_library(built):
+    """every kernel is in libbwasw_mi355.so: it needs no library of the project's, none is built next to it, and `make clean`
+    removes the ones a build from before the single library left there"""
+    dyn = subprocess.check_output([READELF, "-d", built.lib_path()], text=True)
+    assert not re.search(r"NEEDED.*libbwasw_mi355_", dyn), dyn
+    here = os.path.dirname(built.lib_path())
+    assert glob.glob(os.path.join(here, "libbwasw_mi355*.so")) == [built.lib_path()]
+    dry = subprocess.check_output(["make", "-n", "-C", os.path.join(here, "csrc"), "clean"], text=True)
+    assert "../libbwasw_mi355_*.so" in dry
+
+
 def blocks(n, granule):
     return -(-n // granule)
 
 
 def test_pack_kernel_needs_no_more_blocks_and_nothing_else_changed(built):
     got = kernel_metadata(built.lib_path())
-    before = {k: tuple(v) for k, v in json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_resources_before_reads.json"))).items()}
-    assert before[PACK] == PACK_BEFORE
-    assert set(got) == set(before)                      # no kernel added or removed, instantiations included
+    assert golden()[PACK] == PACK_BEFORE
+    assert_kernel_set_is_pinned(got)
     v, s, p = got[PACK]
     print("bsw_pack_kernel: vgpr %d -> %d, sgpr %d -> %d, scratch %d -> %d" % (PACK_BEFORE[0], v, PACK_BEFORE[1], s, PACK_BEFORE[2], p))
     # occupancy follows the allocation blocks (8 VGPRs, 16 SGPRs on gfx950)
     assert blocks(v, 8) <= blocks(PACK_BEFORE[0], 8) and blocks(s, 16) <= blocks(PACK_BEFORE[1], 16) and p <= PACK_BEFORE[2]
-    changed = {k: (before[k], got[k]) for k in before if k != PACK and got[k] != before[k]}
-    assert not changed, changed
+
+
+def test_the_library_stands_alone(built):
+    assert_no_second_library(built)
 
 
 def test_the_library_has_the_store_source(built):

@@ -1,30 +1,22 @@
-"""Build audit of the packed variant-RTL kernels: they live in a companion library next to libbwasw_mi355.so — whose own kernel
-set is pinned by test_reads_build_cpu.py and test_kernel_ledger_cpu.py — that holds exactly the four instantiations of
-bsw_lane2_rtl_kernel; the main library exports the switch, lists the companion as needed and finds it next to itself."""
+"""Build audit of the packed variant-RTL kernels: libbwasw_mi355.so — whose kernel set is pinned by test_reads_build_cpu.py and
+test_kernel_ledger_cpu.py — holds exactly the four instantiations of bsw_lane2_rtl_kernel at the occupancy their launch bounds
+ask for, exports the switch and needs no second library."""
 import os
 import re
 import subprocess
 
-from test_reads_build_cpu import kernel_metadata
+from test_reads_build_cpu import RTL2_KERNEL, assert_no_second_library, kernel_metadata, kernels_matching
 
-READELF = "/opt/rocm/llvm/bin/llvm-readelf"
-COMPANION = "libbwasw_mi355_rtl2.so"
 # bsw_lane2_rtl_kernel<QB, WPS, SYM>: 72 columns at three waves per SIMD, 136 at two; shared / separate gap penalties
 WANT = {(9, 3, True), (9, 3, False), (17, 2, True), (17, 2, False)}
 
 
-def companion_path(built):
-    return os.path.join(os.path.dirname(built.lib_path()), COMPANION)
-
-
-def test_companion_holds_exactly_the_four_rtl_instantiations(built):
-    so = companion_path(built)
-    assert os.path.exists(so)
-    meta = kernel_metadata(so)
+def test_library_holds_exactly_the_four_rtl_instantiations(built):
+    meta = kernels_matching(kernel_metadata(built.lib_path()), RTL2_KERNEL)
     got = set()
     for name, (vgpr, sgpr, scratch) in sorted(meta.items()):
         m = re.match(r"_ZN3bsw20bsw_lane2_rtl_kernelILi(\d+)ELi(\d+)ELb([01])EEEv", name)
-        assert m, "unexpected kernel in %s: %s" % (COMPANION, name)
+        assert m, "unexpected instantiation: %s" % name
         got.add((int(m.group(1)), int(m.group(2)), m.group(3) == "1"))
         print("bsw_lane2_rtl_kernel<%s, %s, %s>: vgpr_count %d sgpr_count %d scratch %d" % (m.group(1), m.group(2), m.group(3), vgpr, sgpr, scratch))
         # the occupancy the launch bounds ask for: 512 VGPRs per SIMD lane in allocation blocks of 8, nothing in scratch
@@ -32,15 +24,11 @@ def test_companion_holds_exactly_the_four_rtl_instantiations(built):
     assert got == WANT and len(meta) == 4
 
 
-def test_main_library_exports_the_switch_and_needs_the_companion(built):
+def test_main_library_exports_the_switch_and_stands_alone(built):
     syms = subprocess.check_output(["nm", "-D", "--defined-only", built.lib_path()], text=True)
     for f in ("bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats"):
         assert re.search(r" T %s$" % f, syms, re.M), f
-    dyn = subprocess.check_output([READELF, "-d", built.lib_path()], text=True)
-    assert re.search(r"NEEDED.*\[%s\]" % re.escape(COMPANION), dyn)
-    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn)
-    # the main library keeps none of the new kernels (its set is pinned elsewhere)
-    assert not [k for k in kernel_metadata(built.lib_path()) if "bsw_lane2_rtl_kernel" in k]
+    assert_no_second_library(built)
 
 
 def test_switch_defaults_off_and_counts_nothing_without_launches(built):

@@ -19,6 +19,7 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "bsw_align_core.h"
 #include "bsw_device.h"
 #include "bsw_stage.h"
 
@@ -26,56 +27,11 @@ namespace bsw {
 
 namespace {
 
-#define A_XBYTE  0x10000
-#define A_XSTOP  0x20000
-#define A_XSUBO  0x40000
-#define A_XSTART 0x80000
-
-template <int CTRL>
-__device__ __forceinline__ int adpp(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, 0xf, 0xf, false);
-}
-/* max over the GW (16 or 8) lanes of a group, in every lane: (mirror,) half mirror, two quad permutes */
-template <int GW>
-__device__ __forceinline__ int row_max16(int v)
-{
-    if (GW == 16) v = max(v, adpp<0x140>(INT_MIN, v));   /* row_mirror      */
-    v = max(v, adpp<0x141>(INT_MIN, v));            /* row_half_mirror */
-    v = max(v, adpp<0x4e>(INT_MIN, v));             /* quad_perm [2,3,0,1] */
-    v = max(v, adpp<0xb1>(INT_MIN, v));             /* quad_perm [1,0,3,2] */
-    return v;
-}
-template <int GW>
-__device__ __forceinline__ unsigned long long row_max16_u64(unsigned long long v)
-{
-    /* two 32-bit butterflies would not keep (hi, lo) together: compare as 64 bits after moving both halves */
-    for (int s = GW == 16 ? 0 : 1; s < 4; ++s) {
-        int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32), lo2, hi2;
-        switch (s) {
-        case 0: lo2 = adpp<0x140>(0, lo); hi2 = adpp<0x140>(0, hi); break;
-        case 1: lo2 = adpp<0x141>(0, lo); hi2 = adpp<0x141>(0, hi); break;
-        case 2: lo2 = adpp<0x4e>(0, lo); hi2 = adpp<0x4e>(0, hi); break;
-        default: lo2 = adpp<0xb1>(0, lo); hi2 = adpp<0xb1>(0, hi); break;
-        }
-        const unsigned long long o = ((unsigned long long)(uint32_t)hi2 << 32) | (uint32_t)lo2;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int base_at(const uint64_t *__restrict__ seq, uint32_t off, int idx)
-{
-    const int c = (int)((seq[off + (uint32_t)(idx >> 4)] >> ((idx & 15) * 4)) & 7ull);
-    return c > 4 ? 4 : c;
-}
-
-struct akswr { int score, te, qe, score2, te2, tb, qb; };
-
 /* One run of ksw_u8 (BYTE) / ksw_i16 for the alignment of this 16-lane row.  `on`: the row takes part (row-uniform).
  * Query position k is q[qrev ? qlast - k : k]; target row i is t[i <= trev ? trev - i : i] (trev = -1: forwards).
  * qrc: q is the reverse complement of the stored sequence s of qn + 1 bases, q[idx] = comp(s[qn - idx]) (mem_matesw's is_rev). */
 template <int SLEN, bool BYTE>
-__device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const int tlen, const uint64_t *__restrict__ seq,
+__device__ __forceinline__ align_res align_pass(const bool on, const int qlen, const int tlen, const uint64_t *__restrict__ seq,
                                             const uint32_t q_off, const int qlast, const bool qrev, const bool qrc, const int qn,
                                             const uint32_t t_off, const int trev,
                                             const int xtra, const bsw_dparams &P, const int shift, const int mx,
@@ -87,9 +43,7 @@ __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const
     constexpr bool lane_on = true;
     const int slen = (qlen + NP - 1) / NP;
     const int oe_del = P.o_del + P.e_del, oe_ins = P.o_ins + P.e_ins, e_del = P.e_del, e_ins = P.e_ins;
-    const int hcap = BYTE ? 255 - shift : 32767;
-    const int minsc = (xtra & A_XSUBO) ? (xtra & 0xffff) : 0x10000;
-    const int endsc = (xtra & A_XSTOP) ? (xtra & 0xffff) : 0x10000;
+    const int hcap = align_hcap<BYTE>(shift), minsc = align_minsc(xtra), endsc = align_endsc(xtra);
     /* ksw_qinit: the score of (target base a, query position j + l * slen), 0 past the end of the query */
 #pragma unroll
     for (int j = 0; j < SLEN; ++j) {
@@ -104,7 +58,8 @@ __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const
     int H[SLEN], E[SLEN], Hmax[SLEN];
 #pragma unroll
     for (int j = 0; j < SLEN; ++j) H[j] = E[j] = Hmax[j] = 0;
-    int gmax = 0, te = -1, n_b = 0, last_i = -2, last_s = 0, hl = 0;       /* hl = H[slen - 1] of the previous row */
+    int gmax = 0, te = -1, hl = 0;       /* hl = H[slen - 1] of the previous row */
+    blist_at b{0, -2, 0};
     bool live = on && slen > 0;
     for (int i = 0;; ++i) {
         const bool ra = live && i < tlen;
@@ -112,7 +67,7 @@ __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const
         const int ti = ra ? (i <= trev ? trev - i : i) : 0;
         const int tb = ra ? base_at(seq, t_off, ti) : 0;
         int f = 0, mxv = 0;
-        int h = adpp<0x111>(0, hl);                                        /* H(i-1,-1): the last vector, one lane up */
+        int h = dpp_mov<0x111>(0, hl);                                     /* H(i-1,-1): the last vector, one lane up */
         h = l == 0 ? 0 : h;
 #pragma unroll
         for (int j = 0; j < SLEN; ++j) {
@@ -133,7 +88,7 @@ __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const
         bool lz = ra;
         for (int k = 0; k < 16; ++k) {
             if (__builtin_amdgcn_ballot_w64(lz) == 0) break;
-            const int fs = adpp<0x111>(0, f);
+            const int fs = dpp_mov<0x111>(0, f);
             f = lz ? (l == 0 ? 0 : fs) : f;
 #pragma unroll
             for (int j = 0; j < SLEN; ++j) {
@@ -144,63 +99,31 @@ __device__ __forceinline__ akswr align_pass(const bool on, const int qlen, const
                 hh = max(hh - oe_ins, 0);
                 const int fn = max(f - e_ins, 0);
                 f = go ? fn : f;
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(go && lane_on && fn > hh);
-                const bool any = ((m >> (tid & (64 - NP))) & (NP == 16 ? 0xffffull : 0xffull)) != 0;
+                const bool any = group_any<NP>(go && lane_on && fn > hh, tid);
                 lz = go ? any : lz;                                        /* (rows past their slen keep lz and skip on their own) */
             }
         }
 #pragma unroll
         for (int j = 0; j < SLEN; ++j) hl = (ra && j == slen - 1) ? H[j] : hl;
-        const int imax = row_max16<NP>(mxv);
-        if (ra && imax >= minsc) {                                         /* the b array of sub-optimal ends */
-            if (n_b == 0 || last_i + 1 != i) {
-                if (l == 0) bl[n_b] = ((unsigned long long)(uint32_t)imax << 32) | (uint32_t)i;
-                ++n_b; last_i = i; last_s = imax;
-            } else if (last_s < imax) {
-                if (l == 0) bl[n_b - 1] = ((unsigned long long)(uint32_t)imax << 32) | (uint32_t)i;
-                last_i = i; last_s = imax;
-            }
-        }
+        const int imax = group_max<NP>(mxv);
+        if (ra && imax >= minsc) b = blist_note(bl, l, i, imax, b);        /* the b array of sub-optimal ends */
         if (ra && imax > gmax) {
             gmax = imax; te = i;
 #pragma unroll
             for (int j = 0; j < SLEN; ++j) Hmax[j] = H[j];
-            if (BYTE ? (gmax + shift >= 255 || gmax >= endsc) : (gmax >= endsc)) live = false;
+            if (align_stops<BYTE>(gmax, shift, endsc)) live = false;
         }
     }
-    akswr r;
-    r.score = BYTE ? (gmax + shift < 255 ? gmax : 255) : gmax;
-    r.te = te; r.qe = -1; r.score2 = -1; r.te2 = -1; r.tb = -1; r.qb = -1;
+    align_res r = align_res_of<BYTE>(gmax, shift, te);
     if (!BYTE || r.score != 255) {
         /* qe: the first maximum of the kept column in memory order i = j * NP + lane -> position j + lane * slen */
         int key = -1;
 #pragma unroll
         for (int j = 0; j < SLEN; ++j)
-            if (lane_on && j < slen) key = max(key, (Hmax[j] << 16) | (0xffff - (j * NP + l)));
-        key = row_max16<NP>(key);
-        if (slen > 0) {
-            const int mi = 0xffff - (key & 0xffff);
-            r.qe = mi / NP + (mi % NP) * slen;
-        }
-        if (n_b > 0) {                                                     /* second best: the first strictly larger entry outside [low, high] wins */
-            __threadfence_block();
-            const int d = (r.score + mx - 1) / mx, low = te - d, high = te + d;
-            unsigned long long best = 0;                                   /* (score + 1) << 32 | ~index : 0 = none */
-            for (int x = l; x < n_b; x += NP) {
-                const unsigned long long ent = bl[x];
-                const int e = (int)(uint32_t)ent, sc = (int)(ent >> 32);
-                if (e < low || e > high) {
-                    const unsigned long long kk = ((unsigned long long)(uint32_t)(sc + 1) << 32) | (uint32_t)(0x7fffffff - x);
-                    best = kk > best ? kk : best;
-                }
-            }
-            best = row_max16_u64<NP>(best);
-            if (best != 0) {
-                const int x = 0x7fffffff - (int)(uint32_t)best;
-                const int sc = (int)(best >> 32) - 1;
-                if (sc > r.score2) { r.score2 = sc; r.te2 = (int)(uint32_t)bl[x]; }
-            }
-        }
+            if (lane_on && j < slen) key = max(key, qe_key(Hmax[j], j * NP + l));
+        key = group_max<NP>(key);
+        if (slen > 0) r.qe = qe_of_key<NP>(key, slen);
+        second_best<NP>(b.n_b > 0, bl, b.n_b, l, mx, r);
     }
     return r;
 }
@@ -220,26 +143,22 @@ __global__ __launch_bounds__(256) void bsw_align_kernel(const bsw_dparams P, con
     const bool valid = slot < n;
     const uint32_t ai = order[valid ? slot : 0];
     const bsw_adtask T = tasks[ai];
-    int smin = 127, smax = 0;
-#pragma unroll
+    int smin = 127, smax = 0;                                        /* (matrix_shift_max of bsw_align_core.h, stated here: through */
+#pragma unroll                                                       /* the shared function the 20-word kernel spills to scratch) */
     for (int a = 0; a < 25; ++a) { smin = min(smin, (int)P.mat[a]); smax = max(smax, (int)P.mat[a]); }
     const int shift = (256 - (smin & 0xff)) & 0xff, mx = smax;
     unsigned long long *bl = blist + T.b_off;
     const bool qrc = (T.pad & BSW_AD_QRC) != 0;
-    akswr r = align_pass<SLEN, BYTE>(valid, T.qlen, T.tlen, seq, T.q_off, 0, false, qrc, T.qlen - 1, T.t_off, -1, T.xtra, P, shift, mx,
+    align_res r = align_pass<SLEN, BYTE>(valid, T.qlen, T.tlen, seq, T.q_off, 0, false, qrc, T.qlen - 1, T.t_off, -1, T.xtra, P, shift, mx,
                                      prof, bl);
-    const bool second = valid && !((T.xtra & A_XSTART) == 0 || ((T.xtra & A_XSUBO) && r.score < (T.xtra & 0xffff)));
+    const bool second = valid && wants_start_pass(T.xtra, r.score);
     if (__builtin_amdgcn_ballot_w64(second) != 0) {
         /* (the profile is rebuilt for the mirrored prefix; every thread owns its column of it: no barrier) */
-        const akswr rr = align_pass<SLEN, BYTE>(second, r.qe + 1, T.tlen, seq, T.q_off, r.qe, true, qrc, T.qlen - 1, T.t_off, r.te,
-                                                A_XSTOP | r.score, P, shift, mx, prof, bl);
-        if (second && r.score == rr.score) { r.tb = r.te - rr.te; r.qb = r.qe - rr.qe; }
+        const align_res rr = align_pass<SLEN, BYTE>(second, r.qe + 1, T.tlen, seq, T.q_off, r.qe, true, qrc, T.qlen - 1, T.t_off, r.te,
+                                                XSTOP | r.score, P, shift, mx, prof, bl);
+        take_start(second, rr, r);
     }
-    if (valid && l == 0) {
-        bsw_kswr o;
-        o.score = r.score; o.te = r.te; o.qe = r.qe; o.score2 = r.score2; o.te2 = r.te2; o.tb = r.tb; o.qb = r.qb;
-        out[ai] = o;
-    }
+    if (valid && l == 0) store_kswr(&out[ai], r);
 }
 
 /* classes: (mode, vectors per lane) -> query length up to lanes * vectors */

@@ -33,6 +33,7 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "bsw_align_core.h"
 #include "bsw_device.h"
 #include "bsw_stage.h"
 
@@ -40,54 +41,10 @@ namespace bsw {
 
 namespace {
 
-#define AL_XBYTE  0x10000
-#define AL_XSTOP  0x20000
-#define AL_XSUBO  0x40000
-#define AL_XSTART 0x80000
-
-template <int CTRL>
-__device__ __forceinline__ int ldpp(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, 0xf, 0xf, false);
-}
-/* max over the GW (16 or 8) lanes of a group, in every lane */
-template <int GW>
-__device__ __forceinline__ int lrow_max(int v)
-{
-    if (GW == 16) v = max(v, ldpp<0x140>(INT_MIN, v));   /* row_mirror      */
-    v = max(v, ldpp<0x141>(INT_MIN, v));                 /* row_half_mirror */
-    v = max(v, ldpp<0x4e>(INT_MIN, v));                  /* quad_perm [2,3,0,1] */
-    v = max(v, ldpp<0xb1>(INT_MIN, v));                  /* quad_perm [1,0,3,2] */
-    return v;
-}
-template <int GW>
-__device__ __forceinline__ unsigned long long lrow_max_u64(unsigned long long v)
-{
-    for (int s = GW == 16 ? 0 : 1; s < 4; ++s) {
-        int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32), lo2, hi2;
-        switch (s) {
-        case 0: lo2 = ldpp<0x140>(0, lo); hi2 = ldpp<0x140>(0, hi); break;
-        case 1: lo2 = ldpp<0x141>(0, lo); hi2 = ldpp<0x141>(0, hi); break;
-        case 2: lo2 = ldpp<0x4e>(0, lo); hi2 = ldpp<0x4e>(0, hi); break;
-        default: lo2 = ldpp<0xb1>(0, lo); hi2 = ldpp<0xb1>(0, hi); break;
-        }
-        const unsigned long long o = ((unsigned long long)(uint32_t)hi2 << 32) | (uint32_t)lo2;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int lcode(uint64_t w, int idx)
-{
-    const int c = (int)((w >> ((idx & 15) * 4)) & 7ull);
-    return c > 4 ? 4 : c;
-}
-
-struct lkswr { int score, te, qe, score2, te2, tb, qb; };
-
 /* One run of ksw_u8 (BYTE) / ksw_i16 for the alignment of this lane group; the arguments are align_pass's of
  * bsw_align_kernel.hip.  he / hm / qc: the group's three LDS arrays at this lane's column, entry j at [j * NP]. */
 template <bool BYTE>
-__device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, const int tlen, const uint64_t *__restrict__ seq,
+__device__ __forceinline__ align_res align_long_pass(const bool on, const int qlen, const int tlen, const uint64_t *__restrict__ seq,
                                                  const uint32_t q_off, const int qlast, const bool qrev, const bool qrc, const int qn,
                                                  const uint32_t t_off, const int trev, const int xtra, const bsw_dparams &P,
                                                  const int shift, const int mx, const uint64_t (&rows)[5],
@@ -97,9 +54,7 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
     const int tid = threadIdx.x, l = tid & (NP - 1);
     const int slen = (qlen + NP - 1) / NP;
     const int oe_del = P.o_del + P.e_del, oe_ins = P.o_ins + P.e_ins, e_del = P.e_del, e_ins = P.e_ins;
-    const int hcap = BYTE ? 255 - shift : 32767;
-    const int minsc = (xtra & AL_XSUBO) ? (xtra & 0xffff) : 0x10000;
-    const int endsc = (xtra & AL_XSTOP) ? (xtra & 0xffff) : 0x10000;
+    const int hcap = align_hcap<BYTE>(shift), minsc = align_minsc(xtra), endsc = align_endsc(xtra);
     /* ksw_qinit: the code of query position j + l * slen, 5 past the end of the query (a zero score); H = E = Hmax = 0 */
     for (int j = 0;; ++j) {
         const bool act = on && j < slen;
@@ -109,7 +64,7 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
             int code = 5;
             if (k < qlen) {
                 const int idx = qrev ? qlast - k : k, si = qrc ? qn - idx : idx;
-                code = lcode(seq[q_off + (uint32_t)(si >> 4)], si);
+                code = base_code(seq[q_off + (uint32_t)(si >> 4)], si);
                 if (qrc) code = code < 4 ? 3 - code : 4;
             }
             he[j * NP] = 0u;
@@ -117,7 +72,8 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
             qc[j * NP] = (uint8_t)(code * 8);
         }
     }
-    int gmax = 0, te = -1, n_b = 0, last_i = -2, last_s = 0;
+    int gmax = 0, te = -1;
+    blist_at b{0, -2, 0};
     bool live = on && slen > 0;
     int tw_at = -1;
     uint64_t tw = 0;                                                      /* the target's word of 16 bases in use */
@@ -126,11 +82,11 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
         if (__builtin_amdgcn_ballot_w64(ra) == 0) break;
         const int ti = ra ? (i <= trev ? trev - i : i) : 0;
         if (ra && (ti >> 4) != tw_at) { tw_at = ti >> 4; tw = seq[t_off + (uint32_t)tw_at]; }
-        const int tb = ra ? lcode(tw, ti) : 0;
+        const int tb = ra ? base_code(tw, ti) : 0;
         const uint64_t sp = tb == 0 ? rows[0] : tb == 1 ? rows[1] : tb == 2 ? rows[2] : tb == 3 ? rows[3] : rows[4];
         int f = 0, mxv = 0;
         const int hl = ra ? (int)(he[(slen - 1) * NP] & 0xffffu) : 0;    /* H(i-1,-1): the last vector, one lane up */
-        int h = ldpp<0x111>(0, hl);
+        int h = dpp_mov<0x111>(0, hl);
         h = l == 0 ? 0 : h;
         for (int j = 0;; ++j) {
             const bool act = ra && j < slen;
@@ -153,7 +109,7 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
         bool lz = ra;
         for (int k = 0; k < 16; ++k) {
             if (__builtin_amdgcn_ballot_w64(lz) == 0) break;
-            const int fs = ldpp<0x111>(0, f);
+            const int fs = dpp_mov<0x111>(0, f);
             f = lz ? (l == 0 ? 0 : fs) : f;
             for (int j = 0;; ++j) {
                 const bool go = lz && j < slen;
@@ -167,21 +123,12 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
                     fn = max(f - e_ins, 0);
                     f = fn;
                 }
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(go && fn > hh);
-                const bool any = ((m >> (tid & (64 - NP))) & (NP == 16 ? 0xffffull : 0xffull)) != 0;
+                const bool any = group_any<NP>(go && fn > hh, tid);
                 lz = go ? any : lz;
             }
         }
-        const int imax = lrow_max<NP>(mxv);
-        if (ra && imax >= minsc) {                                         /* the b array of sub-optimal ends */
-            if (n_b == 0 || last_i + 1 != i) {
-                if (l == 0) bl[n_b] = ((unsigned long long)(uint32_t)imax << 32) | (uint32_t)i;
-                ++n_b; last_i = i; last_s = imax;
-            } else if (last_s < imax) {
-                if (l == 0) bl[n_b - 1] = ((unsigned long long)(uint32_t)imax << 32) | (uint32_t)i;
-                last_i = i; last_s = imax;
-            }
-        }
+        const int imax = group_max<NP>(mxv);
+        if (ra && imax >= minsc) b = blist_note(bl, l, i, imax, b);        /* the b array of sub-optimal ends */
         const bool better = ra && imax > gmax;
         if (__builtin_amdgcn_ballot_w64(better) != 0) {
             for (int j = 0;; ++j) {
@@ -191,33 +138,30 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
             }
             if (better) {
                 gmax = imax; te = i;
-                if (BYTE ? (gmax + shift >= 255 || gmax >= endsc) : (gmax >= endsc)) live = false;
+                if (align_stops<BYTE>(gmax, shift, endsc)) live = false;
             }
         }
     }
-    lkswr r;
-    r.score = BYTE ? (gmax + shift < 255 ? gmax : 255) : gmax;
-    r.te = te; r.qe = -1; r.score2 = -1; r.te2 = -1; r.tb = -1; r.qb = -1;
+    align_res r = align_res_of<BYTE>(gmax, shift, te);
     const bool fin = on && (!BYTE || r.score != 255);
     /* qe: the first maximum of the kept column in memory order i = j * NP + lane -> position j + lane * slen */
     int key = -1;
     for (int j = 0;; ++j) {
         const bool act = fin && j < slen;
         if (__builtin_amdgcn_ballot_w64(act) == 0) break;
-        if (act) key = max(key, ((int)hm[j * NP] << 16) | (0xffff - (j * NP + l)));
+        if (act) key = max(key, qe_key((int)hm[j * NP], j * NP + l));
     }
-    key = lrow_max<NP>(key);
-    if (fin && slen > 0) {
-        const int mi = 0xffff - (key & 0xffff);
-        r.qe = mi / NP + (mi % NP) * slen;
-    }
-    const bool scan = fin && n_b > 0;                                      /* second best: the first strictly larger entry outside [low, high] wins */
+    key = group_max<NP>(key);
+    if (fin && slen > 0) r.qe = qe_of_key<NP>(key, slen);
+    /* second best: second_best of bsw_align_core.h, stated here (through the shared function this kernel is allotted one SGPR
+     * less, and the build pin is exact) */
+    const bool scan = fin && b.n_b > 0;
     if (__builtin_amdgcn_ballot_w64(scan) != 0) {
         __threadfence_block();
         const int d = (r.score + mx - 1) / mx, low = te - d, high = te + d;
         unsigned long long best = 0;                                       /* (score + 1) << 32 | ~index : 0 = none */
         if (scan)
-            for (int x = l; x < n_b; x += NP) {
+            for (int x = l; x < b.n_b; x += NP) {
                 const unsigned long long ent = bl[x];
                 const int e = (int)(uint32_t)ent, sc = (int)(ent >> 32);
                 if (e < low || e > high) {
@@ -225,7 +169,7 @@ __device__ __forceinline__ lkswr align_long_pass(const bool on, const int qlen, 
                     best = kk > best ? kk : best;
                 }
             }
-        best = lrow_max_u64<NP>(best);
+        best = group_max_u64<NP>(best);
         if (scan && best != 0) {
             const int x = 0x7fffffff - (int)(uint32_t)best;
             const int sc = (int)(best >> 32) - 1;
@@ -255,10 +199,8 @@ __global__ __launch_bounds__(256) void bsw_align_long_kernel(const bsw_dparams P
     const uint32_t ai = order[listed ? slot : 0];
     const bsw_adtask T = tasks[ai];
     const bool valid = listed && T.qlen >= 0 && (uint32_t)((T.qlen + GW - 1) / GW) * (uint32_t)GW <= pmax;
-    int smin = 127, smax = 0;
-#pragma unroll
-    for (int a = 0; a < 25; ++a) { smin = min(smin, (int)P.mat[a]); smax = max(smax, (int)P.mat[a]); }
-    const int shift = (256 - (smin & 0xff)) & 0xff, mx = smax;
+    int shift, mx;
+    matrix_shift_max(P, shift, mx);
     uint64_t rows[5];                                                      /* the five scores of a target base, a byte each; byte 5 = 0 */
 #pragma unroll
     for (int a = 0; a < 5; ++a) {
@@ -272,20 +214,15 @@ __global__ __launch_bounds__(256) void bsw_align_long_kernel(const bsw_dparams P
     uint8_t *qc = (uint8_t *)(al_lds + (size_t)g * stride + pmax + pmax / 2) + l;
     unsigned long long *bl = blist + T.b_off;
     const bool qrc = (T.pad & BSW_AD_QRC) != 0;
-    lkswr r = align_long_pass<BYTE>(valid, T.qlen, T.tlen, seq, T.q_off, 0, false, qrc, T.qlen - 1, T.t_off, -1, T.xtra, P, shift, mx,
+    align_res r = align_long_pass<BYTE>(valid, T.qlen, T.tlen, seq, T.q_off, 0, false, qrc, T.qlen - 1, T.t_off, -1, T.xtra, P, shift, mx,
                                     rows, he, hm, qc, bl);
-    const bool second = valid && !((T.xtra & AL_XSTART) == 0 || ((T.xtra & AL_XSUBO) && r.score < (T.xtra & 0xffff)));
+    const bool second = valid && wants_start_pass(T.xtra, r.score);
     if (__builtin_amdgcn_ballot_w64(second) != 0) {
-        const lkswr rr = align_long_pass<BYTE>(second, r.qe + 1, T.tlen, seq, T.q_off, r.qe, true, qrc, T.qlen - 1, T.t_off, r.te,
-                                               AL_XSTOP | r.score, P, shift, mx, rows, he, hm, qc, bl);
-        if (second && r.score == rr.score) { r.tb = r.te - rr.te; r.qb = r.qe - rr.qe; }
+        const align_res rr = align_long_pass<BYTE>(second, r.qe + 1, T.tlen, seq, T.q_off, r.qe, true, qrc, T.qlen - 1, T.t_off, r.te,
+                                               XSTOP | r.score, P, shift, mx, rows, he, hm, qc, bl);
+        take_start(second, rr, r);
     }
-    if (listed && l == 0) {
-        bsw_kswr o;
-        if (valid) { o.score = r.score; o.te = r.te; o.qe = r.qe; o.score2 = r.score2; o.te2 = r.te2; o.tb = r.tb; o.qb = r.qb; }
-        else { o.score = 0; o.te = -1; o.qe = -1; o.score2 = -1; o.te2 = -1; o.tb = -1; o.qb = -1; }
-        out[ai] = o;
-    }
+    if (listed && l == 0) store_kswr(&out[ai], valid ? r : align_res_of<BYTE>(0, 0, -1));   /* (not valid: the empty result) */
 }
 
 /* classes: (mode, slen bound), powers of two; the bound decides the LDS an alignment gets and with it the alignments a workgroup holds */
@@ -330,21 +267,14 @@ extern "C" int bsw_alnl_class_geometry(int cls, int *byte_mode, int *slen_bound,
 
 /* The dynamic-LDS limit is a property of the kernel ON A DEVICE.  It is ONE constant for every class, the 160 KiB of a CU, so
  * that threads launching different classes at once (the slot threads of a pipeline, the scalar queue's leader, a second context)
- * can never lower it below a launch on its way; it is set on the current device, remembered per device only once it has
- * succeeded, and a failure is returned, never cached (as bsw_long_kernel.hip and bsw_global_long_kernel.hip do). */
+ * can never lower it below a launch on its way; set per device by set_lds_ceiling (bsw_band_scan.h), as bsw_long_kernel.hip
+ * and bsw_global_long_kernel.hip do. */
 #define ALNL_LDS_CEILING (160 * 1024)
 template <bool BYTE>
 static hipError_t align_long_lds_attr()
 {
-    static std::atomic<uint64_t> set_on{0};                            /* bit d: set on device d */
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
-    if (bit && (set_on.load(std::memory_order_acquire) & bit)) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bsw_align_long_kernel<BYTE>), hipFuncAttributeMaxDynamicSharedMemorySize, ALNL_LDS_CEILING);
-    if (e == hipSuccess) set_on.fetch_or(bit, std::memory_order_release);
-    return e;
+    static std::atomic<uint64_t> set_on{0};                            /* per instantiation */
+    return set_lds_ceiling(reinterpret_cast<const void *>(&bsw_align_long_kernel<BYTE>), ALNL_LDS_CEILING, set_on);
 }
 
 hipError_t launch_align_long(int cls, const bsw_dparams &P, const uint64_t *seq, const bsw_adtask *tasks, const uint32_t *order, uint32_t n,

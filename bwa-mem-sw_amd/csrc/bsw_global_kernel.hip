@@ -17,7 +17,9 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "bsw_band_scan.h"
 #include "bsw_device.h"
+#include "bsw_global_core.h"
 #include "bsw_stage.h"
 
 namespace bsw {
@@ -26,22 +28,6 @@ namespace {
 
 constexpr int GMINF = -0x40000000;
 constexpr int GNEG = INT_MIN + (1 << 26);                  /* below anything the recurrence can produce, with headroom for -(j-1)*e_ins */
-
-template <int CTRL, int ROW_MASK = 0xf, int BANK_MASK = 0xf>
-__device__ __forceinline__ int gdpp(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
-}
-__device__ __forceinline__ int gscan_max(int x)            /* inclusive max-scan over the 64 lanes */
-{
-    x = max(x, gdpp<0x111>(GNEG, x));
-    x = max(x, gdpp<0x112>(GNEG, x));
-    x = max(x, gdpp<0x114>(GNEG, x));
-    x = max(x, gdpp<0x118>(GNEG, x));
-    x = max(x, gdpp<0x142, 0xa>(GNEG, x));
-    x = max(x, gdpp<0x143, 0xc>(GNEG, x));
-    return x;
-}
 
 }  // namespace
 
@@ -73,17 +59,15 @@ __global__ __launch_bounds__(256) void bsw_global_kernel(const bsw_dparams P, co
         uint32_t cp_lo[5];
         int cp_hi[5];
 #pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            cp_lo[q] = (uint32_t)(uint8_t)P.mat[q] | ((uint32_t)(uint8_t)P.mat[5 + q] << 8) |
-                       ((uint32_t)(uint8_t)P.mat[10 + q] << 16) | ((uint32_t)(uint8_t)P.mat[15 + q] << 24);
-            cp_hi[q] = P.mat[20 + q];
-        }
+        for (int q = 0; q < 5; ++q) matrix_column(P, q, cp_lo[q], cp_hi[q]);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const int j = jbase + c;
             const uint64_t wv = __shfl(qw, (j >> 4) & 63);
             int qb = (int)((wv >> ((j & 15) * 4)) & 7);
             qb = (j < qlen && qb < 4) ? qb : 4;
+            /* matrix_column_of (bsw_band_scan.h), stated here: through the shared function the SGPR count of the C = 2
+             * kernel changes (55 to 52), and the build pin is exact */
             uint32_t lo = cp_lo[4];
             int hi = cp_hi[4];
 #pragma unroll
@@ -108,19 +92,7 @@ __global__ __launch_bounds__(256) void bsw_global_kernel(const bsw_dparams P, co
     uint32_t twl = 0, twh = 0, cur_lo = 0, cur_hi = 0;
 
     for (int i = 0; i < tlen; ++i) {
-        if ((i & 1023) == 0) {                               /* coalesced refill: 64 words = 1024 target bases */
-            const int wi = (i >> 4) + lane;
-            const uint64_t tv = wi < ntw ? seq[T.t_off + wi] : 0ull;
-            twl = (uint32_t)tv;
-            twh = (uint32_t)(tv >> 32);
-        }
-        if ((i & 15) == 0) {
-            const int src = (i >> 4) & 63;
-            cur_lo = __builtin_amdgcn_readlane(twl, src);
-            cur_hi = __builtin_amdgcn_readlane(twh, src);
-        }
-        int tb = (int)((((i & 8) ? cur_hi : cur_lo) >> ((i & 7) * 4)) & 7);
-        tb = tb < 4 ? tb : 4;
+        const int tb = target_base(seq, T.t_off, ntw, i, lane, twl, twh, cur_lo, cur_hi);
         const int beg = i > w ? i - w : 0;
         const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
         const int h1_init = beg == 0 ? -(o_del + e_del * (i + 1)) : GMINF;
@@ -142,8 +114,8 @@ __global__ __launch_bounds__(256) void bsw_global_kernel(const bsw_dparams P, co
         pl[0] = g[0];
 #pragma unroll
         for (int c = 1; c < C; ++c) pl[c] = max(pl[c - 1], g[c]);
-        const int incl = gscan_max(pl[C - 1]);
-        const int carry = gdpp<0x138>(GNEG, incl);           /* wave_shr:1 -> exclusive */
+        const int incl = wave_scan_max<GNEG>(pl[C - 1]);
+        const int carry = dpp_mov<0x138>(GNEG, incl);        /* wave_shr:1 -> exclusive */
         const int g_init = GMINF + (beg - 1) * e_ins;        /* f enters column beg as MINUS_INF */
 
         /* phase 3: H, direction bits, E' */
@@ -154,6 +126,8 @@ __global__ __launch_bounds__(256) void bsw_global_kernel(const bsw_dparams P, co
             const int j = jbase + c;
             const int pex = max(c == 0 ? carry : max(carry, pl[c - 1]), g_init);
             const int f = pex - (j - 1) * e_ins;
+            /* global_cell (bsw_global_core.h), stated here: through the shared function the compiler allots this kernel other
+             * registers, by reference fewer SGPRs from C = 4 up, by value one VGPR less at C = 1, and the build pin is exact */
             const int m = Mv[c], e = E[c];
             uint32_t d = m >= e ? 0u : 1u;
             int h = m >= e ? m : e;
@@ -177,7 +151,7 @@ __global__ __launch_bounds__(256) void bsw_global_kernel(const bsw_dparams P, co
                 if (inr[c]) zi[jbase + c - beg] = (uint8_t)dbits[c];
         }
         /* phase 4: eh[j].h <- H(i,j-1) for j in [beg,end]; eh[end].e <- -inf */
-        const int hleft = gdpp<0x138>(0, hv[C - 1]);
+        const int hleft = dpp_mov<0x138>(0, hv[C - 1]);
 #pragma unroll
         for (int c = C - 1; c >= 0; --c) {
             const int j = jbase + c;
@@ -199,32 +173,19 @@ __global__ __launch_bounds__(256) void bsw_global_kernel(const bsw_dparams P, co
     if (lane == 0) {
         int n_cigar = 0;
         if (zt) {                                            /* backtrack from the last cell, ops pushed in reverse */
-            uint32_t *cg = cigars + (size_t)ti * (size_t)max_cigar;
-            uint32_t last = 0xffffffffu;
+            cigar_writer cw{cigars + (size_t)ti * (size_t)max_cigar, max_cigar, true};
             int which = 0, i = tlen - 1, k = (i + w + 1 < qlen ? i + w + 1 : qlen) - 1;
-            auto push = [&](uint32_t op, int len) {
-                if (n_cigar == 0 || op != (last & 0xf)) {
-                    if (n_cigar > 0 && n_cigar <= max_cigar) cg[n_cigar - 1] = last;
-                    last = ((uint32_t)len << 4) | op;
-                    ++n_cigar;
-                } else last += (uint32_t)len << 4;
-            };
             while (i >= 0 && k >= 0) {
                 /* a band narrower than |qlen - tlen| cannot hold the path: bwa then walks through z entries of other
                  * cells (unspecified result); here such a step reads as "diagonal" and never leaves the matrix */
                 const int col = k - (i > w ? i - w : 0);
                 const uint8_t d = (col >= 0 && col < n_col) ? zt[(size_t)i * (size_t)n_col + (size_t)col] : (uint8_t)0;
                 which = (d >> (which << 1)) & 3;
-                if (which == 0) { push(0u, 1); --i; --k; }
-                else if (which == 1) { push(2u, 1); --i; }
-                else { push(1u, 1); --k; }
+                if (which == 0) { cw.push(0u, 1); --i; --k; }
+                else if (which == 1) { cw.push(2u, 1); --i; }
+                else { cw.push(1u, 1); --k; }
             }
-            if (i >= 0) push(2u, i + 1);
-            if (k >= 0) push(1u, k + 1);
-            if (n_cigar > 0 && n_cigar <= max_cigar) cg[n_cigar - 1] = last;
-            if (n_cigar <= max_cigar)
-                for (int a = 0; a < n_cigar >> 1; ++a) { const uint32_t t = cg[a]; cg[a] = cg[n_cigar - 1 - a]; cg[n_cigar - 1 - a] = t; }
-            else n_cigar = -n_cigar;                         /* did not fit: the caller retries with more room */
+            n_cigar = cw.finish(i, k);
         }
         bsw_gresult r;
         r.score = score;

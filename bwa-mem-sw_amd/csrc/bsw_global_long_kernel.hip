@@ -38,6 +38,7 @@
 
 #include "bsw_band_scan.h"
 #include "bsw_device.h"
+#include "bsw_global_core.h"
 #include "bsw_stage.h"
 
 namespace bsw {
@@ -101,19 +102,7 @@ __global__ __launch_bounds__(64 * WPB) void bsw_global_long_kernel(const bsw_dpa
     const int ntw = (tlen + 15) >> 4;
     uint32_t twl = 0, twh = 0, cur_lo = 0, cur_hi = 0;
     for (int i = 0; i < tlen; ++i) {
-        if ((i & 1023) == 0) {                               /* coalesced refill: 64 words = 1024 target bases */
-            const int wi = (i >> 4) + lane;
-            const uint64_t tv = wi < ntw ? seq[T.t_off + wi] : 0ull;
-            twl = (uint32_t)tv;
-            twh = (uint32_t)(tv >> 32);
-        }
-        if ((i & 15) == 0) {
-            const int src = (i >> 4) & 63;
-            cur_lo = __builtin_amdgcn_readlane(twl, src);
-            cur_hi = __builtin_amdgcn_readlane(twh, src);
-        }
-        int tb = (int)((((i & 8) ? cur_hi : cur_lo) >> ((i & 7) * 4)) & 7);
-        tb = tb < 4 ? tb : 4;
+        const int tb = target_base(seq, T.t_off, ntw, i, lane, twl, twh, cur_lo, cur_hi);
         uint32_t rowp = rp[4];
         int rowq = rn[4];
 #pragma unroll
@@ -145,23 +134,16 @@ __global__ __launch_bounds__(64 * WPB) void bsw_global_long_kernel(const bsw_dpa
             const int s = qb < 4 ? (int)(int8_t)(rowp >> (qb * 8)) : rowq;
             const int m = X + s;
             const int g = inr ? m - oe_ins + r * e_ins : INT_MIN;
-            const int incl = band_scan_max(g);
-            const int pex = max(max(bdpp<0x138>(INT_MIN, incl), carry), LMINF - e_ins);     /* wave_shr:1 -> exclusive */
+            const int incl = wave_scan_max(g);
+            const int pex = max(max(dpp_mov<0x138>(INT_MIN, incl), carry), LMINF - e_ins);  /* wave_shr:1 -> exclusive */
             const int f = pex - (r - 1) * e_ins;
-            uint32_t d = m >= E ? 0u : 1u;
-            int h = m >= E ? m : E;
-            d = h >= f ? d : 2u;
-            h = h >= f ? h : f;
-            int t = m - oe_del;
-            const int e2 = E - e_del;
-            d |= e2 > t ? 1u << 2 : 0u;
-            const int en = e2 > t ? e2 : t;
-            t = m - oe_ins;
-            d |= (f - e_ins) > t ? 2u << 4 : 0u;
+            int h, en;
+            uint32_t d;
+            global_cell(m, E, f, oe_del, e_del, oe_ins, e_ins, h, en, d);
             if (zi && inr) zi[r] = (uint8_t)d;
             E = inr ? en : E;
             /* eh[j].h <- H(i,j-1) for j in [beg,end]; eh[end].e <- -inf */
-            const int hp = bdpp<0x138>(hprev, h);
+            const int hp = dpp_mov<0x138>(hprev, h);
             X = j == beg ? h1_init : hp;
             E = j == end ? LMINF : E;
             if (wr) eh[j & rmask] = make_uint2((uint32_t)X, (uint32_t)E);
@@ -176,15 +158,7 @@ __global__ __launch_bounds__(64 * WPB) void bsw_global_long_kernel(const bsw_dpa
     if (zt) {                                                /* backtrack from the last cell, ops pushed in reverse */
         __threadfence();                                     /* the wave's z stores are visible to its loads */
         uint8_t *tile = (uint8_t *)eh;                       /* the ring is dead: TILE_R x TILE_C bytes */
-        uint32_t *cg = cigars + (size_t)ti * (size_t)max_cigar;
-        uint32_t last = 0xffffffffu;
-        auto push = [&](uint32_t op, int len) {
-            if (n_cigar == 0 || op != (last & 0xf)) {
-                if (lane == 0 && n_cigar > 0 && n_cigar <= max_cigar) cg[n_cigar - 1] = last;
-                last = ((uint32_t)len << 4) | op;
-                ++n_cigar;
-            } else last += (uint32_t)len << 4;
-        };
+        cigar_writer cw{cigars + (size_t)ti * (size_t)max_cigar, max_cigar, lane == 0};
         int which = 0, i = tlen - 1, k = (i + w + 1 < qlen ? i + w + 1 : qlen) - 1;
         int tr0 = i + 1, tc0 = 0;                            /* tile origin (row, z column); none loaded yet */
         while (i >= 0 && k >= 0) {
@@ -204,18 +178,11 @@ __global__ __launch_bounds__(64 * WPB) void bsw_global_long_kernel(const bsw_dpa
             }
             const int d = __builtin_amdgcn_readfirstlane((int)tile[(i - tr0) * TILE_C + (col - tc0)]);
             which = (d >> (which << 1)) & 3;
-            if (which == 0) { push(0u, 1); --i; --k; }
-            else if (which == 1) { push(2u, 1); --i; }
-            else { push(1u, 1); --k; }
+            if (which == 0) { cw.push(0u, 1); --i; --k; }
+            else if (which == 1) { cw.push(2u, 1); --i; }
+            else { cw.push(1u, 1); --k; }
         }
-        if (i >= 0) push(2u, i + 1);
-        if (k >= 0) push(1u, k + 1);
-        if (lane == 0) {
-            if (n_cigar > 0 && n_cigar <= max_cigar) cg[n_cigar - 1] = last;
-            if (n_cigar <= max_cigar)
-                for (int a = 0; a < n_cigar >> 1; ++a) { const uint32_t t = cg[a]; cg[a] = cg[n_cigar - 1 - a]; cg[n_cigar - 1 - a] = t; }
-        }
-        if (n_cigar > max_cigar) n_cigar = -n_cigar;         /* did not fit: the caller retries with more room */
+        n_cigar = cw.finish(i, k);
     }
     if (lane == 0) {
         bsw_gresult res;
@@ -225,28 +192,13 @@ __global__ __launch_bounds__(64 * WPB) void bsw_global_long_kernel(const bsw_dpa
     }
 }
 
-/* The dynamic-LDS limit is set on every device the kernel is launched on (the current one), remembered per device only
- * once it has succeeded; a failure is returned, never cached (as long_lds_attr in bsw_long_kernel.hip). */
-template <int WPB>
-static hipError_t global_long_lds_attr()
-{
-    static std::atomic<uint64_t> set_on{0};                  /* bit d: set on device d */
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
-    if (bit && (set_on.load(std::memory_order_acquire) & bit)) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bsw_global_long_kernel<WPB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) set_on.fetch_or(bit, std::memory_order_release);
-    return e;
-}
-
 template <int WPB>
 static hipError_t launch_gl(int ring, const bsw_dparams &P, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *order,
                             uint32_t n, uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
 {
     const size_t lds = (size_t)(ring + QWORDS) * sizeof(uint2) * (size_t)WPB;
-    const hipError_t attr = global_long_lds_attr<WPB>();
+    static std::atomic<uint64_t> lds_set_on{0};              /* per instantiation (set_lds_ceiling, bsw_band_scan.h) */
+    const hipError_t attr = set_lds_ceiling(reinterpret_cast<const void *>(&bsw_global_long_kernel<WPB>), 160 * 1024, lds_set_on);
     if (attr != hipSuccess) return attr;
     hipLaunchKernelGGL((bsw_global_long_kernel<WPB>), dim3((n + (uint32_t)WPB - 1u) / (uint32_t)WPB), dim3(64 * WPB), lds, s,
                        P, seq, tasks, order, n, ring, z, cigars, max_cigar, out);

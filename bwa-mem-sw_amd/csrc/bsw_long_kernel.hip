@@ -61,22 +61,14 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
         uint32_t cp_lo[5];
         int cp_hi[5];
 #pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            cp_lo[q] = (uint32_t)(uint8_t)P.mat[q] | ((uint32_t)(uint8_t)P.mat[5 + q] << 8) |
-                       ((uint32_t)(uint8_t)P.mat[10 + q] << 16) | ((uint32_t)(uint8_t)P.mat[15 + q] << 24);
-            cp_hi[q] = P.mat[20 + q];
-        }
+        for (int q = 0; q < 5; ++q) matrix_column(P, q, cp_lo[q], cp_hi[q]);
         for (int j = lane; j < ncol; j += 64) {
             int qb = 4;
             if (j < qlen) qb = (int)((seq[q_off + (uint32_t)(j >> 4)] >> ((j & 15) * 4)) & 7);
             qb = qb < 4 ? qb : 4;
-            uint32_t lo = cp_lo[4];
-            int hi = cp_hi[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                lo = qb == q ? cp_lo[q] : lo;
-                hi = qb == q ? cp_hi[q] : hi;
-            }
+            uint32_t lo;
+            int hi;
+            matrix_column_of(qb, cp_lo, cp_hi, lo, hi);
             row[j] = make_uint4(0u, 0u, lo, (uint32_t)hi);
         }
     }
@@ -102,19 +94,7 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
         uint32_t cur_lo = 0, cur_hi = 0;
 
         for (int i = 0; i < tlen; ++i) {                    /* st4 row loop (:1891) */
-            if ((i & 1023) == 0) {                          /* coalesced refill: 64 words = 1024 target bases */
-                const int wi = (i >> 4) + lane;
-                const uint64_t tv = wi < ntw ? seq[t_off + wi] : 0ull;
-                twl = (uint32_t)tv;
-                twh = (uint32_t)(tv >> 32);
-            }
-            if ((i & 15) == 0) {
-                const int src = (i >> 4) & 63;
-                cur_lo = __builtin_amdgcn_readlane(twl, src);
-                cur_hi = __builtin_amdgcn_readlane(twh, src);
-            }
-            int ti = (int)((((i & 8) ? cur_hi : cur_lo) >> ((i & 7) * 4)) & 7);
-            ti = ti < 4 ? ti : 4;
+            const int ti = target_base(seq, t_off, ntw, i, lane, twl, twh, cur_lo, cur_hi);
             const int sh = (ti & 3) * 8;
 
             /* K3 band clamp (:1803,1894-1897,1842,1898) */
@@ -144,8 +124,8 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
                 const int gbase = VAR == BSW_VARIANT_M ? Mv : ht;
                 const int g = inr ? max(gbase - oe_ins, 0) + j * e_ins : NEGB;
                 /* exclusive prefix max over the columns left of j (F recurrence, :1863,1780-1781) */
-                const int incl = band_scan_max(g);
-                const int pex = max(bdpp<0x138>(NEGB, incl), carry);        /* wave_shr:1 -> exclusive; lane 0: the chunks before */
+                const int incl = wave_scan_max(g);
+                const int pex = max(dpp_mov<0x138>(NEGB, incl), carry);     /* wave_shr:1 -> exclusive; lane 0: the chunks before */
                 const int f = max(pex - (j - 1) * e_ins, 0);
                 const int hv = max(ht, f);                  /* (:1809,1944) */
                 const int ebase = VAR == BSW_VARIANT_M ? Mv : hv;
@@ -153,7 +133,7 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
                 E = inr ? en : E;
                 if (inr && hv >= lh) { lh = hv; lj = j; }                  /* ties -> later j (:1808,1816): a lane's columns ascend */
                 /* eh[j].h <- H(i,j-1) for j in [beg,end]; eh[end].e <- 0 (:1776,1775) */
-                const int hp = bdpp<0x138>(hprev, hv);      /* lane l-1's column; lane 0: the previous chunk's last one */
+                const int hp = dpp_mov<0x138>(hprev, hv);   /* lane l-1's column; lane 0: the previous chunk's last one */
                 const int xn = j == beg ? h1_init : hp;
                 X = wr ? xn : X;
                 E = j == end ? 0 : E;
@@ -167,8 +147,8 @@ __device__ __forceinline__ void band_side(const bsw_dparams &P, const uint64_t *
                 hprev = __builtin_amdgcn_readlane(hv, 63);
                 if ((unsigned)(end - j0) < 64u) hlast = __builtin_amdgcn_readlane(X, end - j0);
             }
-            const int mtop = __builtin_amdgcn_readlane(band_scan_max(lh), 63);
-            const int mjt = __builtin_amdgcn_readlane(band_scan_max(lh == mtop ? lj : -1), 63);
+            const int mtop = __builtin_amdgcn_readlane(wave_scan_max(lh), 63);
+            const int mjt = __builtin_amdgcn_readlane(wave_scan_max(lh == mtop ? lj : -1), 63);
             const int mrow = mtop < 0 ? 0 : mtop;
             const int mj = mtop < 0 ? -1 : mjt;
 
@@ -284,22 +264,6 @@ __global__ __launch_bounds__(64 * WPB) void bsw_long_kernel(const bsw_dparams P,
     }
 }
 
-/* The dynamic-LDS limit is a property of the kernel ON A DEVICE: it is set on every device the kernel is launched on (the
- * current one), remembered per device only once it has succeeded, and a failure is returned, never cached. */
-template <int VAR, int WPB>
-static hipError_t long_lds_attr()
-{
-    static std::atomic<uint64_t> set_on{0};                            /* bit d: set on device d */
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
-    if (bit && (set_on.load(std::memory_order_acquire) & bit)) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bsw_long_kernel<VAR, WPB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) set_on.fetch_or(bit, std::memory_order_release);
-    return e;
-}
-
 /* cols = eh[] columns of the seed class (1 024 < cols <= 8 192); n = seed count (or an upper bound of *n_dev).  Up to 2 048
  * columns four wavefronts share a workgroup's LDS (4 x 2 112 records x 16 B = 132 KiB), beyond that a wavefront has it alone. */
 template <int VAR, int WPB>
@@ -307,7 +271,8 @@ static hipError_t launch_long_t(int rec, const bsw_dparams &P, const uint64_t *s
                                 uint32_t n, const uint32_t *n_dev, bsw_result *out, hipStream_t s)
 {
     const size_t lds = (size_t)rec * 16u * (size_t)WPB;
-    const hipError_t attr = long_lds_attr<VAR, WPB>();
+    static std::atomic<uint64_t> lds_set_on{0};                         /* per instantiation (set_lds_ceiling, bsw_band_scan.h) */
+    const hipError_t attr = set_lds_ceiling(reinterpret_cast<const void *>(&bsw_long_kernel<VAR, WPB>), 160 * 1024, lds_set_on);
     if (attr != hipSuccess) return attr;
     uint32_t blocks = (n + (uint32_t)WPB - 1u) / (uint32_t)WPB;
     if (n_dev && blocks > 8192u) blocks = 8192u;                        /* device-side count: stride over the list */

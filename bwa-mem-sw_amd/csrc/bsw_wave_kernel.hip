@@ -24,27 +24,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "bsw_band_scan.h"
 #include "bsw_device.h"
 
 namespace bsw {
-
-template <int CTRL, int ROW_MASK = 0xf, int BANK_MASK = 0xf>
-__device__ __forceinline__ int dpp_mov(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, BANK_MASK, false);
-}
-
-/* inclusive max-scan over the 64 lanes (row_shr 1,2,4,8 + row_bcast 15/31) */
-__device__ __forceinline__ int wave_scan_max(int x)
-{
-    x = max(x, dpp_mov<0x111>(INT_MIN, x));
-    x = max(x, dpp_mov<0x112>(INT_MIN, x));
-    x = max(x, dpp_mov<0x114>(INT_MIN, x));
-    x = max(x, dpp_mov<0x118>(INT_MIN, x));
-    x = max(x, dpp_mov<0x142, 0xa>(INT_MIN, x));
-    x = max(x, dpp_mov<0x143, 0xc>(INT_MIN, x));
-    return x;
-}
 
 constexpr int NEGV = -(1 << 29);                       /* "minus infinity" that survives -1023*e_ins */
 
@@ -74,26 +57,14 @@ __device__ __forceinline__ void extend_side(const bsw_dparams &P, const uint64_t
         uint32_t cp_lo[5];
         int cp_hi[5];
 #pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            cp_lo[q] = (uint32_t)(uint8_t)P.mat[q] | ((uint32_t)(uint8_t)P.mat[5 + q] << 8) |
-                       ((uint32_t)(uint8_t)P.mat[10 + q] << 16) | ((uint32_t)(uint8_t)P.mat[15 + q] << 24);
-            cp_hi[q] = P.mat[20 + q];
-        }
+        for (int q = 0; q < 5; ++q) matrix_column(P, q, cp_lo[q], cp_hi[q]);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const int j = jbase + c;
             const uint64_t wv = __shfl(qw, (j >> 4) & 63);
             int qb = (int)((wv >> ((j & 15) * 4)) & 7);
             qb = (j < qlen && qb < 4) ? qb : 4;
-            uint32_t lo = cp_lo[4];
-            int hi = cp_hi[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                lo = qb == q ? cp_lo[q] : lo;
-                hi = qb == q ? cp_hi[q] : hi;
-            }
-            prof_lo[c] = lo;
-            prof_hi[c] = hi;
+            matrix_column_of(qb, cp_lo, cp_hi, prof_lo[c], prof_hi[c]);
         }
     }
 
@@ -121,19 +92,7 @@ __device__ __forceinline__ void extend_side(const bsw_dparams &P, const uint64_t
         uint32_t cur_lo = 0, cur_hi = 0;
 
         for (int i = 0; i < tlen; ++i) {                    /* st4 row loop (:1891) */
-            if ((i & 1023) == 0) {                          /* coalesced refill: 64 words = 1024 target bases */
-                const int wi = (i >> 4) + lane;
-                const uint64_t tv = wi < ntw ? seq[t_off + wi] : 0ull;
-                twl = (uint32_t)tv;
-                twh = (uint32_t)(tv >> 32);
-            }
-            if ((i & 15) == 0) {
-                const int src = (i >> 4) & 63;
-                cur_lo = __builtin_amdgcn_readlane(twl, src);
-                cur_hi = __builtin_amdgcn_readlane(twh, src);
-            }
-            int ti = (int)((((i & 8) ? cur_hi : cur_lo) >> ((i & 7) * 4)) & 7);
-            ti = ti < 4 ? ti : 4;
+            const int ti = target_base(seq, t_off, ntw, i, lane, twl, twh, cur_lo, cur_hi);
 
             /* K3 band clamp (:1803,1894-1897,1842,1898) */
             beg = max(beg, i - w);

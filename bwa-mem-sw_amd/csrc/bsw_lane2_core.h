@@ -499,6 +499,40 @@ struct lane2 {
 #endif
     }
 
+    /* The N-free block in two 4-column halves with a wave-uniform skip between them (bit BN of skl / skh, the row's masks):
+     *   skip-low:  the row's FIRST block when its columns 0..3 lie left of every active seed's beg and no active seed's
+     *              `end` lies below them: the block is entered at column 4.  The columns skipped would compute zeros from
+     *              zeros (block8_seq's argument); in an EDGE block their masks are all on, so column 4 takes the mask and the
+     *              masked H(i, j-1) that entered the block (mi_in, h1 & mi_in = 0).
+     *   skip-high: (EDGE) the row's LAST block when its columns 4..7 lie right of every active seed's `end` column: every
+     *              mask is off there, the block is left after column 3.
+     * The first column run must ASSIGN mk and nz where column 0 does: both are read-write here, and a block entered at
+     * column 4 folds into what they held — the zeros row_body sets before the row's first block.  On the GPU one asm
+     * statement with one scalar test and branch per skip (bsw_lane2_body_asm.inc), the halves list-scheduled each.
+     * SH: the block can take skip-high at all (not one whose last-block rows run column by column): elsewhere the
+     * statement is built without that test. */
+    template <bool EDGE, int BN, bool SH>
+    L2_MFN void block8h(uint32_t (&T)[8], const uint32_t Wc, const uint32_t Bv2s, const consts &k, const uint32_t END, const uint32_t mi_in,
+                        const uint32_t skl, const uint32_t skh, uint32_t &h1, uint32_t &f, uint32_t &mk, uint32_t &nz)
+    {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(BSW_L2_ASM_BODY)
+        if constexpr (EDGE) block8h_asm<true, VM, SYM>::template run<BN, SH>(T, Wc, Bv2s, k, END, mi_in, skl, skh, h1, f, mk, nz);
+        else block8h_asm<false, VM, SYM>::template run<BN>(T, Wc, Bv2s, k, skl, h1, f, mk, nz);
+#else
+        /* (both skips never meet in one block — jlo & 7 >= 4 and jhi & 7 < 4 there would mean jhi < jlo, which jem >= jlo
+         * excludes — so `&& !lo` here and the asm's jump past the skip-high test only agree on a case that does not occur) */
+        const bool lo = ((skl >> BN) & 1u) != 0, hi = EDGE && SH && ((skh >> BN) & 1u) != 0 && !lo;
+        uint32_t mi_prev = mi_in;
+        uint32_t hp = EDGE ? h1 & mi_in : 0u;
+        uint32_t &hpr = EDGE ? hp : h1;
+        sfor<8>([&](auto ci) {
+            constexpr int c = decltype(ci)::value;
+            if (c < 4 ? lo : hi) return;
+            cell<c, EDGE, false>(T[c], Wc, 0u, Bv2s, 0u, k, END, mi_prev, hpr, h1, f, mk, nz);
+        });
+#endif
+    }
+
     /* The ragged blocks of a row, column by column with a wave-uniform guard (no query N in the block):
      *   !EDGE: the row's FIRST block — columns below `guard` = jlo & 7 lie left of every active seed's beg; they would
      *          compute zeros from zeros (h1 = f = 0 there: a seed with beg > 0 starts its row from 0) and are skipped;
@@ -595,13 +629,18 @@ struct lane2 {
          * compiler rebuilt ~25 scalar instructions and five branches around every block — a sixth of a wave's time in
          * the blocks, during which the SIMD's other wave issues at the lone-wave rate.) */
 #ifndef BSW_L2_RAGGED_TOP
-#define BSW_L2_RAGGED_TOP 10        /* with the bit-mask dispatch: 4 / 8 / 10 / 12 / 17 -> headline 2681 / 2663 / 2675 / 2650 / 2619, 72-column bin 2127 / 2350 / 2345 / 2318 / 2317, mixed bins 2305 / 2330 / 2340 / 2319 / 2352 */
+#define BSW_L2_RAGGED_TOP 8         /* (the classes wider than 9 blocks; the 9-block class runs every last block column by column.)  8 since the
+                                     * half blocks below: every dense / edge block got 8 - 16 bytes longer, the row loop of <17,2> 676 bytes, and a row
+                                     * that runs all 17 blocks (the single-bin workload) lost 0.7 - 1.1 % to the instruction cache; two ragged-last
+                                     * bodies fewer give back 7 KB, and the blocks that lose them take the half-block skip instead (DESIGN A.0b).
+                                     * Before the half blocks, with the bit-mask dispatch: 4 / 8 / 10 / 12 / 17 -> headline 2681 / 2663 / 2675 / 2650 / 2619, 72-column bin 2127 / 2350 / 2345 / 2318 / 2317, mixed bins 2305 / 2330 / 2340 / 2319 / 2352 */
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BSW_L2_RAGGED_UNROLLED)
+        /* (BSW_L2_KERNEL_DISPATCH: the CPU model with the kernel's choice of bodies, not every ragged body everywhere) */
+#if (defined(__HIP_DEVICE_COMPILE__) || defined(BSW_L2_KERNEL_DISPATCH)) && !defined(BSW_L2_RAGGED_UNROLLED)
 #ifndef BSW_L2_RAGGED_FIRST
 #define BSW_L2_RAGGED_FIRST 0
 #endif
-        constexpr uint32_t RAG_F = (1u << BSW_L2_RAGGED_FIRST) - 1u, RAG_L = ((1u << QB) - 1u) & ~((1u << (QB > BSW_L2_RAGGED_TOP ? QB - BSW_L2_RAGGED_TOP : 0)) - 1u);   /* only the last block, only at the top of the class */
+        constexpr uint32_t RAG_F = (1u << BSW_L2_RAGGED_FIRST) - 1u, RAG_L = ((1u << QB) - 1u) & ~((1u << (QB > 9 && QB > BSW_L2_RAGGED_TOP ? QB - BSW_L2_RAGGED_TOP : 0)) - 1u);   /* only the last block, only at the top of the class */
 #else
         constexpr uint32_t RAG_F = (1u << QB) - 1u, RAG_L = (1u << QB) - 1u;
 #endif
@@ -615,12 +654,26 @@ struct lane2 {
         const uint32_t m_dnq = opaque_u(m_run & m_lt_em & nblk);
         const uint32_t m_enq = opaque_u(m_run & ~m_lt_em & nblk);
         const uint32_t m_sf = opaque_u(m_seqf), m_sl = opaque_u(m_seql), m_any = opaque_u(m_run), m_cold = opaque_u(m_run & nblk);
-        sfor<QB>([&](auto bi) {
+        /* half-block skips of the N-free dense / edge bodies (block8h): bit blo when the first block's columns 0..3 lie left
+         * of every active beg (and no active row is empty: jem >= jlo), bit bhi when the last block's columns 4..7 lie right
+         * of every active `end` column.  A block that takes another body ignores its bit. */
+        /* (HALF: the classes wider than 9 blocks.  bsw_lane2_kernel<9,3> is held to 168 VGPRs and keeps its whole-block
+         * bodies and its block-by-block dispatch as they are: its spills are pinned outside the row loop, and its rows are at
+         * most 9 blocks wide) */
+        constexpr bool HALF = QB > 9;
+        const uint32_t m_sklo = HALF ? opaque_u(((u.jlo & 7) >= 4 && u.jem >= u.jlo) ? (1u << imin(blo, 31)) & m_run : 0u) : 0u;
+        const uint32_t m_skhi = HALF ? opaque_u((u.jhi & 7) < 4 ? (1u << imin(bhi, 31)) & m_run & ~RAG_L : 0u) : 0u;
+        uint32_t mkr = 0, nzr = 0;                            /* (HALF) a block's row-max key and non-zero bits: zero at the row's first block (block8h) */
+#if defined(BSW_L2_SKIP_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+        BSW_L2_SKIP_STATS(u.jlo & 7, u.jhi & 7, (m_sklo & m_dense) != 0u, (m_sklo & m_edge) != 0u, (m_skhi & m_edge) != 0u, (m_sklo & m_skhi) != 0u);   /* (CPU model: what the tests' shapes reach) */
+#endif
+        const auto one_block = [&](auto bi) {
             constexpr int b = decltype(bi)::value, j0 = b * 8, g = j0 >> 6, c = j0 >> 4, wd = j0 >> 5;
             if (!((m_any >> b) & 1u)) return;                 /* j0 + 8 <= jlo or j0 > jhi */
+            uint32_t mkl = 0, nzl = 0;                        /* (!HALF) this block's row-max key and non-zero bits */
+            uint32_t &mkb = HALF ? mkr : mkl, &nz8 = HALF ? nzr : nzl;
             /* both seeds' match bits of this 16-column chunk: low half seed A, high half seed B */
             const uint32_t Wc = byte_pair<b & 3>(rmA[wd], rmB[wd]);   /* this block's 8 match bits of seed A / B in bits 0..7 of the low / high half */
-            uint32_t mkb = 0, nz8 = 0;                        /* this block's row-max key and non-zero bits */
             /* nested scalar branches (a combined condition would be materialised as lane masks for all 17 blocks
              * before the loop and spill) */
             /* four mutually exclusive bodies as four consecutive `if`s, not an if/else tree: a body that is simply run or
@@ -641,7 +694,13 @@ struct lane2 {
              * body for the top BSW_L2_RAGGED_TOP blocks of the class alone — where the queries of the class end — lifts it
              * to 2 478 (sweep 1 / 2 / 3 / 4 / 6 / 17 blocks: 2 384 / 2 461 / 2 478 / 2 478 / 2 377 / 2 313,
              * profiles/r3/ragged_top_sweep.txt) */
-            if ((m_dense >> b) & 1u) run8(no_t{}, no_t{}, 0u, END2, dummy);
+            const auto run8h = [&](auto edge, const uint32_t ENDx, const uint32_t mi_in) {
+                uint32_t T[8];
+                sfor<8>([&](auto ci) { T[decltype(ci)::value] = S.Pr[j0 + decltype(ci)::value]; });
+                block8h<decltype(edge)::value, b, ((RAG_L >> b) & 1u) == 0u>(T, Wc, Bv2, k, ENDx, mi_in, m_sklo, m_skhi, h1, f, mkb, nz8);
+                sfor<8>([&](auto ci) { S.Pr[j0 + decltype(ci)::value] = T[decltype(ci)::value]; });
+            };
+            if ((m_dense >> b) & 1u) { if constexpr (HALF) run8h(no_t{}, END2, dummy); else run8(no_t{}, no_t{}, 0u, END2, dummy); }
             if (RAG_F != 0u && ((m_sf >> b) & 1u)) {
                 uint32_t T[8];
                 sfor<8>([&](auto ci) { T[decltype(ci)::value] = S.Pr[j0 + decltype(ci)::value]; });
@@ -672,11 +731,17 @@ struct lane2 {
             if ((m_edge >> b) & 1u) {
                 const uint32_t d0 = pk_subs_vs(END2 + 0x00010001u, dup16(j0));     /* mi of column j0 - 1 */
                 const uint32_t ENDr = pk_subs_vs(END2, dup16(j0));      /* max(end - j0, 0): column constants stay block-relative */
-                run8(yes_t{}, no_t{}, 0u, ENDr, pk_nzmask(d0));
+                if constexpr (HALF) run8h(yes_t{}, ENDr, pk_nzmask(d0)); else run8(yes_t{}, no_t{}, 0u, ENDr, pk_nzmask(d0));
             }
             /* fold the block: its row-max key into its 64-column group (column offsets only touch the low key bits), its
              * non-zero bits into the first / last trackers (one statement of seven packed ops, none reading its predecessor) */
             fold8<false>(mkg[g], Fnz, Lnz, mkb, nz8, (uint32_t)(j0 & 63) * 0x00010001u, (uint32_t)(j0 << 8) * 0x00010001u, k.ONE2);
+        };
+        /* blocks outside [blo, bhi] are skipped four at a time: one test per group of four, then one per block of a group that runs */
+        sfor<(QB + 3) / 4>([&](auto gi) {
+            constexpr int b0 = decltype(gi)::value * 4, nb = QB - b0 < 4 ? QB - b0 : 4;
+            if (HALF && !((m_any >> b0) & ((1u << nb) - 1u))) return;
+            sfor<nb>([&](auto ci) { one_block(std::integral_constant<int, b0 + decltype(ci)::value>{}); });
         });
 
         L2_STAMP(3);

@@ -12,7 +12,8 @@ consumer is placed >= LAT issue slots behind its producer whenever anything else
 scan over the final order, and an s_nop 0 is emitted only where a packed result is read by the very next instruction.
 
 Variants: EDGE (the block holds some seed's `end`: per-column masks), NQ (some query has an N in the block), VM (variant M),
-SYM (one shared gap-open term).  Usage: gen_lane2_body.py > bsw_lane2_body_asm.inc"""
+SYM (one shared gap-open term).  The unrolled kernel's N-free bodies come a second time as two 4-column halves with a
+wave-uniform skip between them (emit_half, lane2::block8h).  Usage: gen_lane2_body.py > bsw_lane2_body_asm.inc"""
 import itertools, re
 import sys
 
@@ -28,10 +29,14 @@ class Op:
         self.preds, self.succs = set(), set()
 
 
-def build(edge, nq, vm, sym):
-    """The ops of one 8-column block in program order (SSA value names), plus which values are inputs / outputs."""
+def build(edge, nq, vm, sym, part=None):
+    """The ops of one 8-column block in program order (SSA value names), plus which values are inputs / outputs.
+    part: None = the whole block; "A" / "B" = its columns 0..3 / 4..7 alone (emit_half): what flows from A to B sits in
+    fixed registers (h1, f, mk, nz; EDGE: the column mask in mi_in's register, the masked H(i, j-1) in HPB), so B can be
+    entered without A and A left without B."""
     ops = []
-    ins = {"Wc", "B", "HI", "h1_in", "f_in"} | {"P%d" % c for c in range(8)}
+    cols = {None: range(8), "A": range(4), "B": range(4, 8)}[part]
+    ins = {"Wc", "B", "HI", "h1_in", "f_in"} | {"P%d" % c for c in cols}
     if nq:
         ins |= {"WN", "D2"}
     if edge:
@@ -43,9 +48,16 @@ def build(edge, nq, vm, sym):
 
     f, h1, mi_prev = "f_in", "h1_in", "mi_in"
     mk = nz = None
+    if part == "B":
+        mk, nz = "mk_in", "nz_in"
+        ins |= {"mk_in", "nz_in"}
     # EDGE: hp = the masked H(i, j-1) of the stored pair, h1 = the last H below end (lane2::cell)
-    hp = op("hp", "v_and_b32_e32 {d}, {0}, {1}", "hp_in", ["h1_in", "mi_in"], packed=False) if edge else h1
-    for c in range(8):
+    if edge and part:
+        hp = "hp_in"                                     # (emit_half computes it ahead of the skip test)
+        ins.add("hp_in")
+    else:
+        hp = op("hp", "v_and_b32_e32 {d}, {0}, {1}", "hp_in", ["h1_in", "mi_in"], packed=False) if edge else h1
+    for c in cols:
         P = "P%d" % c
         bit = (1 << c) * 0x00010001
         jj = "0" if c == 0 else "%%[JJ%d]" % c
@@ -81,10 +93,10 @@ def build(edge, nq, vm, sym):
         fs = op("fs", "v_pk_sub_u16 {d}, {0}, %%[%s] clamp" % ("ED" if sym else "EI"), "fs%d" % c, [f])
         f = op("f", "v_pk_max_u16 {d}, {0}, {1}", "f%d" % c, [fs, tI])
         key = op("key", "v_and_or_b32 {d}, {0}, {1}, %s" % jj, "key%d" % c, [h, "HI"])
-        mk = key if c == 0 else op("mk", "v_pk_max_u16 {d}, {0}, {1}", "mk%d" % c, [mk, key])
+        mk = key if mk is None else op("mk", "v_pk_max_u16 {d}, {0}, {1}", "mk%d" % c, [mk, key])
         np_ = op("np", "v_perm_b32 {d}, {0}, {1}, %[PERM]", "np%d" % c, [en, hp])
         nb = op("nb", "v_pk_min_u16 {d}, {0}, %[ONE]", "nb%d" % c, [np_])
-        nz = nb if c == 0 else op("nz", "v_lshl_or_b32 {d}, {0}, %d, {1}" % c, "nz%d" % c, [nb, nz])
+        nz = nb if nz is None else op("nz", "v_lshl_or_b32 {d}, {0}, %d, {1}" % c, "nz%d" % c, [nb, nz])
         if not edge:
             newP, h1, hp = np_, h, h
         else:
@@ -94,7 +106,9 @@ def build(edge, nq, vm, sym):
         # remember which SSA value becomes the new P of this column
         build.newP[c] = newP
     outs = {"h1": h1, "f": f, "mk": mk, "nz": nz}
-    for c in range(8):
+    if edge and part == "A":
+        outs["mi_in"], outs["HPB"] = mi_prev, hp
+    for c in cols:
         outs["P%d" % c] = build.newP[c]
     return ops, ins, outs
 
@@ -114,7 +128,7 @@ def schedule(ops, ins, outs):
                 o.preds.add(producer[s]); producer[s].succs.add(o)
     # anti-dependencies: an output value is written into its operand register, whose old content (the matching input)
     # must have been read by then
-    reg_in = {"h1": "h1_in", "f": "f_in"}
+    reg_in = {"h1": "h1_in", "f": "f_in", "mk": "mk_in", "nz": "nz_in", "mi_in": "mi_in", "HPB": "hp_in"}
     reg_in.update({"P%d" % c: "P%d" % c for c in range(8)})
     for r, v in outs.items():
         if r in reg_in and v in producer:
@@ -149,7 +163,7 @@ def allocate(order, ins, outs):
         for s in o.srcs:
             last_use[s] = i
     out_of = {v: r for r, v in outs.items()}
-    reg_in = {"h1_in": "h1", "f_in": "f"}
+    reg_in = {"h1_in": "h1", "f_in": "f", "mk_in": "mk", "nz_in": "nz", "hp_in": "HPB"}
     loc = {}
     for v in sorted(ins):
         loc[v] = reg_in.get(v, v)                       # input operands keep their own names (P0.., Wc, B, ...)
@@ -194,7 +208,7 @@ def on_grid(lines):
     The choice is made by three string macros the lines are written with: L2A, L2E, L2W."""
     out, nsalu = ["\x03"], 0
     for l in lines:
-        if l.endswith(":"):
+        if l.endswith(":") or l == "\x04":                 # (\x04: two scalar instructions or none)
             assert nsalu % 2 == 0
             out.append(l)
             continue
@@ -223,6 +237,8 @@ def c_string(l, last=False):
         return "L2A"
     if l == "\x02":
         return 'L2W "%s"' % end
+    if l == "\x04":
+        return "L2SKH(SH)"
     if "\x01" in l:
         h, t = l.split("\x01")
         return '"%s" L2E "%s%s"' % (h, t, end)
@@ -427,6 +443,96 @@ def emit_seq(edge, vm, sym):
     return "\n".join(body)
 
 
+def half_lines(edge, vm, sym, part):
+    """One 4-column half of an N-free body, list-scheduled on its own: (asm lines, instructions, wait states,
+    temporaries, first op, last op)."""
+    ops, ins, outs = build(edge, 0, vm, sym, part)
+    order = schedule(ops, ins, outs)
+    loc, ntmp = allocate(order, ins, outs)
+    lines = []
+    for o in order:
+        if o == "nop":
+            lines.append("s_nop 0")
+            continue
+        d = "%%[%s]" % loc[o.dst]
+        srcs = ["%%[%s]" % loc[s] for s in o.srcs]
+        lines.append(o.fmt.replace("{d}", d).format(*srcs))
+    real = [o for o in order if o != "nop"]
+    return lines, len(real), len(order) - len(real), ntmp, (real[0], loc), (real[-1], loc)
+
+
+def emit_half(edge, vm, sym):
+    """The N-free dense / edge body as two 4-column halves with a wave-uniform skip between them (lane2::block8h):
+      skip-low  (bit BN of SKL): the block is entered at column 4 — the row's first block when its columns 0..3 lie left of
+                every active seed's beg (they would compute zeros from zeros, h1 = f = 0);
+      skip-high (bit BN of SKH, EDGE only: a row's last block holds an `end`): the block is left after column 3 — the row's
+                last block when its columns 4..7 lie right of every active seed's `end` column (every mask off).
+    One statement, one scalar test and branch per skip, neither taken unless the skip applies.  mk and nz are read-write:
+    a block entered at column 4 folds into what they held, which is the row's zeros (it is the first block the row runs)."""
+    la, na, wa, ta, _, last_a = half_lines(edge, vm, sym, "A")
+    lb, nb, wb, tb, first_b, _ = half_lines(edge, vm, sym, "B")
+    lines = []
+    if edge:
+        lines.append("v_and_b32_e32 %[HPB], %[h1], %[mi_in]")       # the masked H(i, j0-1): column 0's, and column 4's on skip-low
+    lines += ["s_bitcmp1_b32 %[SKL], %[BN]", "s_cbranch_scc1 2f"]
+    lines += la
+    if edge:
+        lines += ["\x04"]                                   # (the skip-high test: only where the block can take it, L2SKH below)
+    else:
+        # the halves meet without a scalar instruction between them: the wait state of a packed result read at once
+        (oa, loca), (ob, locb) = last_a, first_b
+        if oa.packed and loca[oa.dst] in [locb[x] for x in ob.srcs]:
+            lines.append("s_nop 0")
+    lines.append("2:")
+    lines += lb
+    if edge:
+        lines.append("9:")
+    lines = on_grid(lines)
+    # The halves need 19 temporaries where the whole-block EDGE body has 31..34.  The statement still claims 33: told of
+    # fewer, the compiler sees less pressure in the row loop, hoists more cold-path constants (zero_dropped's column
+    # compares, staging addresses) into VGPRs and then spills them — bsw_lane2_kernel<17,2> went from 0 to 40..85 spilled
+    # VGPRs with 19 and 26 temporaries, <9,3> from 9..13 to 26..40, some reloaded inside the row loop; with 33 both are
+    # where they were (0, and 7..13 outside the row loop).
+    # This steers a heuristic of one compiler: re-check the figure (the kernels' vgpr_spill_count; tests/test_reads_build_cpu.py
+    # and tests/test_isa_audit.py pin the outcome) whenever the ROCm version changes.
+    ntmp = max(ta, tb, 33 if edge else 0)
+    sig = ["uint32_t (&P)[8]", "uint32_t Wc", "uint32_t B", "const consts &k"]
+    if edge:
+        sig += ["uint32_t END", "uint32_t mi_in"]
+    sig += ["uint32_t skl"] + (["uint32_t skh"] if edge else [])
+    sig += ["uint32_t &h1", "uint32_t &f", "uint32_t &mk", "uint32_t &nz"]
+    outs_c = ['[P%d] "+v"(P[%d])' % (c, c) for c in range(8)] + ['[h1] "+v"(h1)', '[f] "+v"(f)', '[mk] "+v"(mk)', '[nz] "+v"(nz)']
+    if edge:
+        outs_c += ['[mi_in] "+v"(mi_in)', '[HPB] "=&v"(hpb)']
+    outs_c += ['[T%d] "=&v"(t%d)' % (i, i) for i in range(ntmp)]
+    ins_c = ['[Wc] "v"(Wc)', '[B] "v"(B)', '[HI] "v"(k.HI2)', '[SKL] "s"(skl)']
+    if edge:
+        ins_c += ['[SKH] "s"(skh)', '[END] "v"(END)']
+    ins_c += ['[BN] "n"(BN)']
+    ins_c += ['[MC%d] "s"(k.MC[%d])' % (c, c) for c in range(8)]
+    ins_c += ['[JJ%d] "s"(0x%xu)' % (c, c * 0x00010001) for c in range(1, 8)]
+    ins_c += ['[OED] "s"(k.OED2s)', '[ED] "s"(k.ED2s)', '[ONE] "s"(k.ONE2)', '[PERM] "s"(0x07030501u)']
+    if not sym:
+        ins_c += ['[OEI] "s"(k.OEI2s)', '[EI] "s"(k.EI2s)']
+    body = ["/* halves, EDGE=%d VM=%d SYM=%d: %d + %d instructions, %d + %d s_nop, %d temporaries */" % (edge, vm, sym, na, nb, wa, wb, ntmp)]
+    body.append("template <> struct block8h_asm<%s, %s, %s> {" % tuple("true" if x else "false" for x in (edge, vm, sym)))
+    body.append("template <int BN%s> static __device__ __forceinline__ void run(%s)" % (", bool SH" if edge else "", ", ".join(sig)))
+    body.append("{")
+    body.append("    uint32_t %s;" % ", ".join(["t%d" % i for i in range(ntmp)] + (["hpb"] if edge else [])))
+    # SH: the block can be the row's last one outside the ragged-last range; elsewhere the skip-high test is left out
+    for sh in ((1, 0) if edge else (None,)):
+        if edge:
+            body.append("    if constexpr (%sSH)" % ("" if sh else "!"))
+        body.append("    asm volatile(")
+        for i, l in enumerate(lines):
+            body.append("        " + c_string(l, i == len(lines) - 1).replace("L2SKH(SH)", "L2SKH(%d)" % (sh or 0)))
+        body.append("        : " + ", ".join(outs_c))
+        body.append("        : " + ", ".join(ins_c) + " : \"scc\");")
+    body.append("}")
+    body.append("};")
+    return "\n".join(body)
+
+
 def main():
     print("/* GENERATED by tools/gen_lane2_body.py — do not edit.  The 8-column block bodies of the two-seeds-per-lane kernels as")
     print(" * one list-scheduled inline-asm statement per variant; arithmetic = lane2::cell() of bsw_lane2_core.h. */")
@@ -465,6 +571,12 @@ def main():
             *("true" if x else "false" for x in (edge, vm, sym)), ", ".join(sig)))
     for edge, vm, sym in itertools.product((0, 1), repeat=3):
         print(emit_seq(edge, vm, sym))
+    print('#define L2SKH(on) L2SKH_##on')
+    print('#define L2SKH_1 "s_bitcmp1_b32 %[SKH], %[BN]\\n\\ts_cbranch_scc1 9f\\n\\t"')
+    print('#define L2SKH_0 ""')
+    print("template <bool EDGE, bool VM, bool SYM> struct block8h_asm;")
+    for edge, vm, sym in itertools.product((0, 1), repeat=3):
+        print(emit_half(edge, vm, sym))
     print("/* instruction counts (EDGE, NQ, VM, SYM) -> (instructions, s_nop, temporaries): %s */" % stats)
 
 

@@ -302,6 +302,7 @@ BSW_LOCAL int align_batch_mode(bsw_ctx *ctx, const bsw_params *p, const bsw_atas
             return fail(e, BSW_E_LIMIT, "align task %zu: beyond %s/BSW_MAX_TLEN", i, al_mode ? "BSW_ALIGN_LONG_MAX_QLEN" : "BSW_ALIGN_MAX_QLEN");
         if ((t.qlen && !t.query) || (t.tlen && !t.target)) return fail(e, BSW_E_INVAL, "align task %zu: NULL sequence pointer", i);
         if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "align task %zu: unknown xtra flag", i);
+        if ((rc = align_byte_mode_check(e, p, t.xtra, "align", i)) != BSW_OK) return rc;
     }
     HIPCHK(e, hipSetDevice(ctx->device0()));
     /* sub-batches: bounded sequence arena and sub-optimal list scratch */

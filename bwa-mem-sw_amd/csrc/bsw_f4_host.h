@@ -70,6 +70,19 @@ inline int align_route(int al_mode, int qlen, bool byte_mode, int ncls, int nall
     const int c = lc == -1 ? bsw::align_class_of(qlen, byte_mode) : lc < 0 ? -1 : ncls + lc;
     return c < nall ? c : -1;
 }
+/* what ksw_u8 has no byte for (include/bwa_sw_mi355.h at KSW_XBYTE): a matrix whose smallest entry is above 0 (the shift
+ * 256 - min wraps and the stored profile byte with it), a gap open + extend beyond 255 (an 8-bit lane in bwa).  BSW_OK, or the
+ * rejection of `what` task i whose flags are xtra; 16-bit mode has neither limit. */
+inline int align_byte_mode_check(errs &e, const bsw_params *p, int xtra, const char *what, size_t i)
+{
+    if (!(xtra & KSW_XBYTE)) return BSW_OK;
+    int mn = p->mat[0];
+    for (int k = 1; k < 25; ++k) mn = std::min(mn, (int)p->mat[k]);
+    if (mn > 0) return fail(e, BSW_E_INVAL, "%s task %zu: KSW_XBYTE with a scoring matrix whose smallest entry is %d > 0 (the 8-bit shift wraps; run it in 16-bit mode)", what, i, mn);
+    if (p->o_del + p->e_del > 255 || p->o_ins + p->e_ins > 255)
+        return fail(e, BSW_E_LIMIT, "%s task %zu: KSW_XBYTE with a gap open + extend above 255 (an 8-bit lane in bwa; run it in 16-bit mode)", what, i);
+    return BSW_OK;
+}
 
 /* ---- one launch per class that holds a task, ascending; d_order: the device copy of cl.order; alo: the LDS-row kernel's classes
  * behind the ncls of bsw_align_kernel ---- */

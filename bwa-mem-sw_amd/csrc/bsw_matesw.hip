@@ -160,6 +160,7 @@ static int matesw_validate(errs &e, const bsw_params *p, const bsw_mtask *tasks,
         if (t.l_ms && !t.mate && !rd) return fail(e, BSW_E_INVAL, "mate task %zu: NULL mate", i);
         if (t.is_rev != 0 && t.is_rev != 1) return fail(e, BSW_E_INVAL, "mate task %zu: is_rev is neither 0 nor 1", i);
         if (t.xtra & ~(0xffff | KSW_XBYTE | KSW_XSTOP | KSW_XSUBO | KSW_XSTART)) return fail(e, BSW_E_INVAL, "mate task %zu: unknown xtra flag", i);
+        if ((rc = align_byte_mode_check(e, p, t.xtra, "mate", i)) != BSW_OK) return rc;
         if (t.l_ms > qmax || (t.re > t.rb && t.re - t.rb > BSW_MAX_TLEN))
             return fail(e, BSW_E_LIMIT, "mate task %zu: beyond %s / BSW_MAX_TLEN", i, al_mode ? "BSW_ALIGN_LONG_MAX_QLEN" : "BSW_ALIGN_MAX_QLEN");
     }

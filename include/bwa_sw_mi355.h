@@ -419,7 +419,14 @@ int      bsw_infer_bw(int l1, int l2, int score, int a, int q, int r);
  * Results are those of bwa's striped SSE2 code (ksw_u8 when KSW_XBYTE is set, else ksw_i16), bit for bit: score
  * (255 = the 8-bit run saturated, call again without KSW_XBYTE), te/qe (end on target / query, inclusive),
  * score2/te2 (best end at least ceil(score/max) rows away, needs KSW_XSUBO | threshold), tb/qb (start, needs
- * KSW_XSTART; -1 when the start pass did not run or disagrees).  xtra = flags | 16-bit threshold, as in bwa. */
+ * KSW_XSTART; -1 when the start pass did not run or disagrees).  xtra = flags | 16-bit threshold, as in bwa.
+ * The matrix is mat[target code * 5 + query code] and need not be symmetric; codes above 4 count as 4; 16-bit scores saturate at
+ * 32 767.  Two things ksw_u8 has no byte for are rejected, per task, by bsw_align_batch, bsw_matesw_ref_batch and its ticket forms
+ * and (as the call's failure, score -1) by ksw_align2 / ksw_align; the same task without KSW_XBYTE runs:
+ *   - KSW_XBYTE with a matrix whose smallest entry is above 0 -> BSW_E_INVAL.  ksw_qinit's shift 256 - min wraps there and the
+ *     SSE2 code adds a wrapped profile byte; a smallest entry of 0 (shift 0) is the last one that works;
+ *   - KSW_XBYTE with o_del + e_del > 255 or o_ins + e_ins > 255 -> BSW_E_LIMIT.  bwa keeps these sums in 8-bit lanes
+ *     (_mm_set1_epi8), so 256 would act as 0 there; 255 is accepted. */
 #define KSW_XBYTE  0x10000
 #define KSW_XSTOP  0x20000
 #define KSW_XSUBO  0x40000
@@ -475,7 +482,8 @@ typedef struct bsw_mresult {
 } bsw_mresult;               /* 72 bytes */
 /* Batched mem_matesw Smith-Waterman on the GPU (m = 5; p supplies mat and the four gap penalties).  The first malformed task
  * rejects the batch: negative l_ms, NULL mate, is_rev other than 0 / 1, an unknown xtra flag -> BSW_E_INVAL;
- * l_ms > BSW_ALIGN_MAX_QLEN (BSW_ALIGN_LONG_MAX_QLEN under bsw_set_align_long(1 / 2)) or re - rb > BSW_MAX_TLEN -> BSW_E_LIMIT. */
+ * l_ms > BSW_ALIGN_MAX_QLEN (BSW_ALIGN_LONG_MAX_QLEN under bsw_set_align_long(1 / 2)) or re - rb > BSW_MAX_TLEN -> BSW_E_LIMIT;
+ * KSW_XBYTE with a matrix minimum above 0 -> BSW_E_INVAL, with a gap open + extend above 255 -> BSW_E_LIMIT (at KSW_XBYTE above). */
 int      bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw_ref *ref, const bsw_mtask *tasks, size_t n,
                               bsw_mresult *res);
 /* The same as a TICKET of the context's pipeline: the contract of bsw_cigar_ref_submit_t above, with the checks and the results

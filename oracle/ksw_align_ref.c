@@ -13,8 +13,15 @@
  *   - 8-bit scores saturate, the run stops at gmax + shift >= 255 and reports score 255;
  *   - qe is the first maximum of the kept H column in MEMORY order (vector-major), not in query order;
  *   - the sub-optimal list b[] merges a row into the previous entry only if that entry's stored row is i - 1.
- * Pinned by analytic KATs, score bounds against an independent numpy local DP (oracle/py/full_dp.py) and the
- * re-scoring of the reported end points in tests/test_oracle_align.py.
+ * Two inputs of the 8-bit run are OUTSIDE what this file pins, and the library rejects them (include/bwa_sw_mi355.h at KSW_XBYTE):
+ *   - a matrix whose smallest entry is above 0: shift = 256 - min wraps, the stored profile byte is (s + shift) & 0xff as in
+ *     ksw_qinit, and every H stays 0 (score 0 for min >= 2, 255 for min == 1) — literal, but no alignment;
+ *   - o_del + e_del or o_ins + e_ins above 255: bwa holds them in 8-bit lanes (_mm_set1_epi8), where 256 acts as 0; this file
+ *     uses the full integer and does not emulate the wrap.
+ * The matrix is mat[target * m + query] and need not be symmetric; 16-bit scores saturate at 32 767 (sat_add_i16).
+ * Pinned by analytic KATs (the 8-bit shift up to 128 and the 16-bit cap among them), score bounds against an independent
+ * numpy local DP (oracle/py/full_dp.py, general matrices included) and the re-scoring of the reported end points in
+ * tests/test_oracle_align.py.
  */
 #include "ksw_extend_ref.h"
 

@@ -21,6 +21,24 @@ def mutate(rng, ref, n, sub, indel):
     return np.array(out, dtype=np.uint8)
 
 
+def general_matrix(rng, off_hi=9):
+    """A 5x5 scoring matrix mat[target][query] that no symmetry protects: entries in [-9, 9], the four base diagonals in 1..9,
+    the other base entries in [-9, off_hi], the N row and the N column drawn independently of each other.  Redrawn until it
+    differs from its transpose among the bases and on the N row / column, and from its image under complementing both codes
+    and under complementing either one: a kernel that swaps the indices, or complements the wrong one, reads another matrix."""
+    comp = [3, 2, 1, 0, 4]
+    while True:
+        m = rng.integers(-9, off_hi + 1, (5, 5)).astype(np.int8)
+        for k in range(4):
+            m[k, k] = rng.integers(1, 10)
+        m[4, :] = rng.integers(-9, 10, 5)
+        m[:4, 4] = rng.integers(-9, 10, 4)
+        both = m[comp][:, comp]
+        if ((m[:4, :4] != m[:4, :4].T).sum() >= 6 and (m[4, :4] != m[:4, 4]).sum() >= 2 and (m != both).sum() >= 6 and
+                (m != m[comp]).sum() >= 6 and (m != m[:, comp]).sum() >= 6 and (m != both.T).sum() >= 6):
+            return m
+
+
 def random_seeds(rng, n, qmin=1, qmax=140, tfac=2.0, sub=0.03, indel=0.01, junk=0.2, nrate=0.0, h0max=60,
                  both_sides=True, tmin=0):
     """List of seed dicts for host.make_tasks()."""

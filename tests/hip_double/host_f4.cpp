@@ -7,6 +7,7 @@
  *   host_f4 f4scalar             ksw_global2 / ksw_global / ksw_align2 / ksw_align / ksw_extend2 from 12 threads and an offender
  *   host_f4 faults CALL          CALL = global | align | cigar | matesw: every single HIP failure inside that batch call
  *   host_f4 cuts                 cut_spans (csrc/bsw_f4_host.h), the hosts' sub-batch cutter, with small caps on made-up costs
+ *   host_f4 rejects              the 8-bit-mode tasks the align hosts refuse (matrix minimum above 0, gap open + extend above 255)
  *
  * Expected values do not travel the path under test.  The stand-ins compute from the words the host staged; for the global and
  * the local alignment this program calls the oracle on the caller's byte-per-base sequences.  For CIGAR / NM / MD / retries and
@@ -990,14 +991,97 @@ static int cuts_mode()
     return 0;
 }
 
+/* ---- rejects: what bsw_align_batch, bsw_matesw_ref_batch and ksw_align2 / ksw_align refuse in 8-bit mode (include/bwa_sw_mi355.h
+ * at KSW_XBYTE), per task, and that the neighbouring cases run and equal the oracle ---- */
+static int rejects_mode()
+{
+    fresh(1);
+    genome_t g;
+    g.make(40001, 9);
+    rng_t r(4242);
+    bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256);
+    bsw_ref *ref = nullptr;
+    CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
+    const size_t N = 7;
+    arena_t ar(N * 1400 + 8192, false);
+    awork aw;
+    make_align(aw, ar, g, r, N);
+    mwork mw;
+    make_matesw(mw, ar, g, r, N);
+    for (size_t i = 0; i < N; ++i) {                                   /* every window runs */
+        bsw_mtask &t = mw.t[i];
+        if (t.l_ms == 0) { t.l_ms = 1; t.mate = g.bases.data(); }
+        t.rb = 100 + 50 * (int64_t)i; t.re = t.rb + t.l_ms + 120;
+    }
+    struct kase { const char *what; int lo; int od, ed, oi, ei; bool byte_last, byte_all; int want; const char *needle; };
+    /* lo: -1 the default matrix, else every entry drawn from lo + 1 .. 7 and one entry set to lo */
+    const kase K[] = {
+        {"min 2, one 8-bit task", 2, 6, 1, 6, 1, true, false, BSW_E_INVAL, "smallest entry is 2"},
+        {"min 2, 16-bit", 2, 6, 1, 6, 1, false, false, BSW_OK, ""},
+        {"min 1, one 8-bit task", 1, 6, 1, 6, 1, true, false, BSW_E_INVAL, "smallest entry is 1"},
+        {"min 0, 8-bit", 0, 6, 1, 6, 1, true, true, BSW_OK, ""},
+        {"o_del + e_del = 256, one 8-bit task", -1, 255, 1, 6, 1, true, false, BSW_E_LIMIT, "above 255"},
+        {"o_del + e_del = 256, 16-bit", -1, 255, 1, 6, 1, false, false, BSW_OK, ""},
+        {"o_ins + e_ins = 256, one 8-bit task", -1, 6, 1, 200, 56, true, false, BSW_E_LIMIT, "above 255"},
+        {"both sums 255, 8-bit", -1, 250, 5, 254, 1, true, true, BSW_OK, ""},
+    };
+    size_t refused = 0, ran = 0;
+    for (const kase &k : K) {
+        bsw_params p = default_params();
+        if (k.lo >= 0) {
+            for (int i = 0; i < 25; ++i) p.mat[i] = (int8_t)r.in(k.lo + 1, 7);
+            p.mat[7] = (int8_t)k.lo;
+        }
+        p.o_del = k.od; p.e_del = k.ed; p.o_ins = k.oi; p.e_ins = k.ei;
+        for (size_t i = 0; i < N; ++i) {
+            const int x = ((k.byte_all || (k.byte_last && i + 1 == N)) ? KSW_XBYTE : 0) | KSW_XSUBO | KSW_XSTART | 19;
+            aw.t[i].xtra = x; mw.t[i].xtra = x;
+        }
+        char tag[32];
+        snprintf(tag, sizeof(tag), "task %zu", N - 1);
+        if (k.want == BSW_OK) {
+            check_align(ctx, p, aw, k.what);                       /* runs, and equals the oracle */
+            run_matesw(ctx, p, ref, mw, nullptr, k.what);
+            ++ran;
+        } else {
+            std::vector<bsw_kswr> ares(N);
+            int rc = bsw_align_batch(ctx, &p, aw.t.data(), N, ares.data());
+            CHECK(rc == k.want && strstr(bsw_last_error(ctx), k.needle) && strstr(bsw_last_error(ctx), "KSW_XBYTE") && strstr(bsw_last_error(ctx), tag),
+                  "%s: bsw_align_batch -> %d (%s), wanted %d with '%s'", k.what, rc, bsw_last_error(ctx), k.want, k.needle);
+            std::vector<bsw_mresult> mres(N);
+            rc = bsw_matesw_ref_batch(ctx, &p, ref, mw.t.data(), N, mres.data());
+            CHECK(rc == k.want && strstr(bsw_last_error(ctx), k.needle) && strstr(bsw_last_error(ctx), "KSW_XBYTE") && strstr(bsw_last_error(ctx), tag),
+                  "%s: bsw_matesw_ref_batch -> %d (%s), wanted %d with '%s'", k.what, rc, bsw_last_error(ctx), k.want, k.needle);
+            ++refused;
+        }
+        /* the scalar ABI: the last task as ksw_align2's call (score -1 = the call's failure), ksw_align where both kinds share their penalties */
+        const bsw_atask &t = aw.t[N - 1];
+        int32_t want[7];
+        ksw_align2_ref(t.qlen, aw.q[N - 1].data(), t.tlen, aw.tg[N - 1].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, t.xtra, want, nullptr);
+        const kswr_t got = ksw_align2(t.qlen, (uint8_t *)aw.q[N - 1].data(), t.tlen, (uint8_t *)aw.tg[N - 1].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, t.xtra, nullptr);
+        const int32_t g7[7] = {got.score, got.te, got.qe, got.score2, got.te2, got.tb, got.qb};
+        if (k.want == BSW_OK) CHECK(memcmp(g7, want, sizeof(want)) == 0, "%s: ksw_align2 score %d te %d, the oracle's %d %d", k.what, got.score, got.te, want[0], want[1]);
+        else CHECK(got.score == -1, "%s: ksw_align2 answered score %d, not the call's failure", k.what, got.score);
+        if (k.od == k.oi && k.ed == k.ei) {
+            const kswr_t g1 = ksw_align(t.qlen, (uint8_t *)aw.q[N - 1].data(), t.tlen, (uint8_t *)aw.tg[N - 1].data(), 5, p.mat, p.o_del, p.e_del, t.xtra, nullptr);
+            CHECK(k.want == BSW_OK ? g1.score == want[0] : g1.score == -1, "%s: ksw_align answered score %d", k.what, g1.score);
+        }
+    }
+    bsw_ref_free(ctx, ref);
+    bsw_destroy(ctx);
+    printf("rejects: %zu cases refused, %zu ran\n", refused, ran);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const std::string mode = argc > 1 ? argv[1] : "";
+    if (mode == "rejects") return rejects_mode();
     if (mode == "f4" && argc > 2) return f4_mode(argv[2]);
     if (mode == "f4split" && argc > 3) return f4split_mode(argv[2], argv[3]);
     if (mode == "f4scalar") return f4scalar_mode();
     if (mode == "faults" && argc > 2) return f4faults_mode(argv[2]);
     if (mode == "cuts") return cuts_mode();
-    fprintf(stderr, "usage: host_f4 f4 FILE | f4split count|z|b FILE | f4scalar | faults global|align|cigar|matesw | cuts\n");
+    fprintf(stderr, "usage: host_f4 f4 FILE | f4split count|z|b FILE | f4scalar | faults global|align|cigar|matesw | cuts | rejects\n");
     return 2;
 }

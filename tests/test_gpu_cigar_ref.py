@@ -195,6 +195,40 @@ def test_other_penalties_and_longest_target(host, oracle, ctx, genome):
     check(host, oracle, ctx, host.default_params(o_del=5, e_del=2, o_ins=7, e_ins=1), genome, specs, max_cigar=256, max_md=70000)
 
 
+def general_specs(pac):
+    """200 reads of 150 bases with substitutions, indels and N on both strands, bands of 5 to 60 with up to three tries"""
+    rng = np.random.default_rng(11)
+    mat = _gen.general_matrix(rng, off_hi=-1)
+    specs = []
+    for i in range(200):
+        rb, re = interval(rng, int(rng.integers(140, 170)), i & 1)
+        q = read_of(rng, pac, rb, re, 150, 0.04, 0.02, 0.01 if i % 3 == 0 else 0.0)
+        specs.append(spec(q, rb, re, w=int(rng.integers(5, 60)), w_cap=120, min_score=int(rng.integers(100, 900)), max_tries=int(rng.integers(1, 4))))
+    return mat, specs
+
+
+def test_matrix_without_symmetry_on_both_strands(host, oracle, ctx, genome):
+    """On the reverse strand the read and the reference are both reversed before the global alignment: which of them is the row
+    and which the column of mat[target * 5 + query] is invisible under bwa's matrices.  Here the transposed matrix gives the CPU
+    restatement itself another score on 196 of 200 reads (measured; half is asserted)."""
+    pac, _ = genome
+    mat, specs = general_specs(pac)
+    p = host.default_params(o_del=5, e_del=2, o_ins=7, e_ins=1)
+    p["mat"][0] = mat.reshape(25)
+    _, _, _, want = check(host, oracle, ctx, p, genome, specs, max_cigar=128, max_md=2048)
+    for strand in (0, 1):
+        mine = [w for s, w in zip(specs, want) if (s["rb"] >= L_PAC) == strand]
+        assert len(mine) == 100 and sum(1 for w in mine if not w["status"] and len(w["cigar"]) >= 3) >= 40, strand
+    ops = {op for w in want if not w["status"] for op, _ in w["cigar"]}
+    assert {0, 1, 2} <= ops                                       # M, I and D
+    pt = host.default_params(o_del=5, e_del=2, o_ins=7, e_ins=1)
+    pt["mat"][0] = mat.T.reshape(25)
+    other = expected(oracle, pt, pac, specs)
+    differ = sum(1 for a, b in zip(want, other) if a["score"] != b["score"])
+    print("transposed matrix: %d of %d scores differ" % (differ, len(specs)))
+    assert differ >= 0.49 * len(specs)
+
+
 def test_cigar_and_md_overflow(host, oracle, ctx, genome):
     pac, _ = genome
     rng = np.random.default_rng(13)

@@ -201,6 +201,78 @@ def test_other_penalties_and_a_65535_base_window(host, oracle, ctx, genome):
     assert (res["status"][:4] == 0).all() and (res["aln"]["tb"][:4] > 59000).all()
 
 
+COMP = [3, 2, 1, 0, 4]
+
+
+def general_specs(pac):
+    """400 tasks under a matrix that is symmetric neither under transposition nor under complement (_gen.general_matrix): both
+    strands x both is_rev, mates of 24 to 250 bases with xtra as mem_matesw builds it from the matrix's a (8-bit mode for the short
+    ones), N in a third of the mates"""
+    rng = np.random.default_rng(10)
+    mat = _gen.general_matrix(rng, off_hi=-1)
+    a = int(mat.diagonal()[:4].max())
+    specs = []
+    for i in range(400):
+        strand, is_rev = i & 1, (i >> 1) & 1
+        l_ms = (24, 60, 150, 250)[(i >> 2) & 3]
+        rb, re = window(rng, strand, l_ms + int(rng.integers(100, 450)))
+        m = mate_in(rng, pac, rb, re, l_ms, is_rev, sub=0.04, indel=0.01, nrate=0.02 if i % 3 == 0 else 0.0, junk=0.05)
+        specs.append(task(m, is_rev, rb, re, xtra=mr.xtra_of(l_ms, a, 19), min_score=int(rng.choice([19, 19 * a]))))
+    return mat, specs
+
+
+def test_matrix_without_symmetry_on_both_strands_and_orientations(host, oracle, ctx, genome):
+    """The reverse complement of is_rev belongs to the QUERY index of mat[target * 5 + query] and nowhere else.  Under bwa's
+    matrices complementing the target index as well, or instead, or swapping the indices, changes nothing; here each reads another
+    matrix.  The guard: with both codes complemented the CPU restatement itself answers differently on 199 of 200 is_rev tasks
+    (measured; half is asserted)."""
+    pac, _ = genome
+    mat, specs = general_specs(pac)
+    p = host.default_params(o_del=5, e_del=2, o_ins=7, e_ins=1)
+    p["mat"][0] = mat.reshape(25)
+    res, want = check(host, oracle, ctx, p, genome, specs)
+    byte = np.array([(s["xtra"] & XBYTE) != 0 for s in specs])
+    for strand in (0, 1):
+        for is_rev in (0, 1):
+            sel = np.array([(s["rb"] >= L_PAC) == strand and s["is_rev"] == is_rev for s in specs])
+            assert sel.sum() == 100 and (res["status"][sel] == 0).sum() >= 60 and (res["status"][sel & byte] == 0).sum() >= 10, (strand, is_rev)
+    p2 = host.default_params(o_del=5, e_del=2, o_ins=7, e_ins=1)
+    p2["mat"][0] = mat[COMP][:, COMP].reshape(25)
+    other = expected(host, oracle, p2, pac, specs)
+    rev = np.array([s["is_rev"] == 1 for s in specs])
+    differ = ((other["aln"] != want["aln"]).any(axis=1) & rev).sum()
+    print("both codes complemented: %d of %d is_rev tasks differ" % (differ, rev.sum()))
+    assert differ >= 0.49 * rev.sum()
+
+
+def test_byte_mode_rejections(host, ctx, genome):
+    """what bsw_align_batch rejects in 8-bit mode (include/bwa_sw_mi355.h at KSW_XBYTE), here too, per task"""
+    _, ref = genome
+    m = np.zeros(200, dtype=np.uint8)
+
+    def rc_of(p, x1):
+        mt = np.zeros(2, dtype=host.MTASK)
+        for t, x in zip(mt, (XSUBO | XSTART | 19, x1)):
+            t["mate"], t["l_ms"], t["rb"], t["re"], t["xtra"] = m.ctypes.data, 100, 0, 500, x
+        try:
+            ctx.matesw_ref_batch(p, ref, mt)
+            return 0, ""
+        except host.BswError as e:
+            return e.code, str(e)
+
+    pos = host.default_params(mat=np.arange(1, 26, dtype=np.int8))
+    assert rc_of(pos, XSUBO | XSTART | 19)[0] == 0                           # 16-bit mode runs
+    code, text = rc_of(pos, XBYTE | XSUBO | XSTART | 19)
+    assert code == -2 and "mate task 1" in text and "KSW_XBYTE" in text and "smallest entry is 1" in text, text
+    zero = host.default_params(mat=np.arange(0, 25, dtype=np.int8))
+    assert rc_of(zero, XBYTE | XSUBO | XSTART | 19)[0] == 0                  # a smallest entry of 0 is accepted
+    assert rc_of(host.default_params(o_del=254, e_del=1, o_ins=250, e_ins=5), XBYTE | XSTART)[0] == 0
+    for over in (dict(o_del=255, e_del=1), dict(o_ins=250, e_ins=6)):
+        assert rc_of(host.default_params(**over), XSTART)[0] == 0
+        code, text = rc_of(host.default_params(**over), XBYTE | XSTART)
+        assert code == -3 and "mate task 1" in text and "KSW_XBYTE" in text, text
+
+
 @pytest.mark.parametrize("memory", ["pageable", "registered"])
 def test_registered_and_pageable_mates(host, oracle, ctx, genome, memory):
     pac, _ = genome

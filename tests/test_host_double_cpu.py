@@ -396,6 +396,15 @@ def test_scalar_queue_groups_of_three_kinds(san):
     assert m and int(m.group(2)) < int(m.group(1)) and int(m.group(3)) >= 3, out.stdout
 
 
+def test_byte_mode_tasks_the_align_hosts_reject():
+    """KSW_XBYTE with a matrix whose smallest entry is 1 or 2 (BSW_E_INVAL) or with a gap open + extend of 256 (BSW_E_LIMIT) through
+    bsw_align_batch, bsw_matesw_ref_batch, ksw_align2 and ksw_align: the code, a text that names KSW_XBYTE, the reason and the
+    task; the scalar calls answer score -1.  The same batches in 16-bit mode, a smallest entry of 0 and sums of 255 in 8-bit mode
+    run and equal the oracle (ASan)."""
+    out, _ = run("asan", "host_f4", "rejects", quiet_stderr=True)
+    assert re.search(r"rejects: 4 cases refused, 4 ran", out.stdout), out.stdout
+
+
 @pytest.mark.parametrize("san", SANS)
 @pytest.mark.parametrize("call", ["global", "align", "cigar", "matesw"])
 def test_every_single_hip_failure_in_an_f4_batch_call(san, call):

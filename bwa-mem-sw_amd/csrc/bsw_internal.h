@@ -370,8 +370,13 @@ struct reads_up {
     errs err;
     std::atomic<int> failed{0};                     /* a piece failed: the others give up */
     std::vector<const uint8_t *> src;               /* the reads as the caller holds them (theirs until the block is ready) */
+    int enc = 0;                                    /* how they are encoded (BSW_READS_*) */
     std::vector<size_t> cut;                        /* piece k = reads [cut[k], cut[k + 1]) */
 };
+
+/* the encodings a read block may be uploaded in, and the raw bytes a read of len bases has in each */
+inline bool reads_enc_known(int enc) { return enc == BSW_READS_CODES || enc == BSW_READS_ASCII || enc == BSW_READS_PACKED; }
+inline size_t reads_raw_bytes(int32_t len, int enc) { return enc == BSW_READS_PACKED ? 8 * (size_t)(((int64_t)len + 15) >> 4) : (size_t)len; }
 
 /* a *_reads_* submit takes its block: false for a block of another context, or one that is being freed.  The ticket gives it
  * back when it is destroyed, i.e. collected (ticket_t, bsw_batch.hip). */

@@ -14,6 +14,9 @@
  * nothing — have been enqueued.  The piece then waits for its own work (watchdog), so the slot's staging and the caller's bases
  * are free when it reports; the block is READY when every piece on every device has reported.
  *
+ * bsw_reads_upload_start_enc takes the reads as FASTQ letters or as 4-bit words too: the pieces are then cut, spanned, gathered and
+ * counted by the RAW bytes of a read as encoded (reads_raw_bytes), and the record tells the kernel which translation to run.
+ *
  * An upload is no submit: no ticket, no place among BSW_MAX_INFLIGHT; at most BSW_READS_MAX_UPLOADS per context are in flight.
  */
 #include "bsw_f4_host.h"
@@ -66,7 +69,7 @@ static int up_enqueue(errs &e, f4_lane &L, bsw_reads *r, size_t k, bool *queued)
         HIPCHK(e, hipMemsetAsync(store + r->words, 0, BSW_READS_SLACK * sizeof(uint64_t), s));
     }
     raw_span sp;
-    for (size_t i = a; i < b; ++i) sp.add(u.src[i], (size_t)r->rd[i].len);
+    for (size_t i = a; i < b; ++i) sp.add(u.src[i], reads_raw_bytes(r->rd[i].len, u.enc));
     if ((he = L.h_in->reserve((n + 1) * sizeof(bsw_rdpack_rec))) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
     bsw_rdpack_rec *rec = (bsw_rdpack_rec *)L.h_in->p;
     const bool direct = sp.direct(BSW_RDPACK_RAW_SLACK);
@@ -76,10 +79,12 @@ static int up_enqueue(errs &e, f4_lane &L, bsw_reads *r, size_t k, bool *queued)
     for (size_t i = a; i < b; ++i) {
         const int32_t len = r->rd[i].len;
         bsw_rdpack_rec &x = rec[i - a];
-        x.woff = r->rd[i].woff; x.len = len; x.pad = 0;
+        const size_t rb = reads_raw_bytes(len, u.enc);
+        x.woff = r->rd[i].woff; x.len = len; x.enc = (uint32_t)u.enc;
+        /* (a packed read stays on an 8-byte boundary: its pointer and sp.lo are on one, and a gather adds multiples of 8) */
         x.raw_off = !len ? 0u : direct ? (uint32_t)(u.src[i] - sp.lo) : (uint32_t)acc;
-        if (len && !direct) memcpy(st.h_raw.p + acc, u.src[i], (size_t)len);
-        acc += (uint64_t)len;
+        if (len && !direct) memcpy(st.h_raw.p + acc, u.src[i], rb);
+        acc += (uint64_t)rb;
     }
     const size_t rawb = direct ? sp.span() : (size_t)sp.bytes;
     const size_t rec_words = (n * sizeof(bsw_rdpack_rec) + 7) / 8;
@@ -132,42 +137,47 @@ static void up_piece(bsw_ctx *ctx, f4_lane &L, void *arg, size_t k)
     u.cv.notify_all();                               /* (under the lock: the block may be freed as soon as it is released) */
 }
 
-extern "C" int bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out)
+static int reads_start_any(const char *who, bsw_ctx *ctx, const void *const *reads, const int32_t *lens, size_t n_reads, int enc, bsw_reads **out)
 {
     if (!ctx) return BSW_E_INVAL;
     errs e;
-    if (!out || ((!reads || !lens) && n_reads)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_upload_start: NULL argument"));
+    if (!out || ((!reads || !lens) && n_reads)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: NULL argument", who));
     *out = nullptr;
-    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "bsw_reads_upload_start: context is dead (an earlier wait for the GPU timed out)"));
-    if (n_reads >= (1ull << 32)) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "bsw_reads_upload_start: more than 2^32 - 1 reads"));
+    if (!reads_enc_known(enc)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: encoding %d is none of BSW_READS_CODES, BSW_READS_ASCII, BSW_READS_PACKED", who, enc));
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", who));
+    if (n_reads >= (1ull << 32)) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "%s: more than 2^32 - 1 reads", who));
     std::unique_ptr<bsw_reads> r(new bsw_reads());
     r->owner = ctx;
     r->rd.resize(n_reads);
     uint64_t words = 0, bases = 0;
     for (size_t i = 0; i < n_reads; ++i) {
-        if (lens[i] < 0) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_upload_start: read %zu: negative length", i));
-        if (lens[i] && !reads[i]) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_reads_upload_start: read %zu: NULL read", i));
-        if (lens[i] > READS_MAX_LEN) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "bsw_reads_upload_start: read %zu: more than %d bases", i, READS_MAX_LEN));
+        if (lens[i] < 0) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: read %zu: negative length", who, i));
+        if (lens[i] && !reads[i]) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: read %zu: NULL read", who, i));
+        if (lens[i] > READS_MAX_LEN) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "%s: read %zu: more than %d bases", who, i, READS_MAX_LEN));
+        if (enc == BSW_READS_PACKED && lens[i] && ((uintptr_t)reads[i] & 7)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: read %zu: packed words not on an 8-byte boundary", who, i));
         r->rd[i] = bsw_reads::ent{(uint32_t)words, lens[i]};
         words += nwords(lens[i]);
         bases += (uint64_t)lens[i];
-        if (words > READS_MAX_WORDS) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "bsw_reads_upload_start: the block needs more than %llu packed words; split it", (unsigned long long)READS_MAX_WORDS));
+        if (words > READS_MAX_WORDS) return ctx_fail(ctx, e, fail(e, BSW_E_LIMIT, "%s: the block needs more than %llu packed words; split it", who, (unsigned long long)READS_MAX_WORDS));
     }
     r->words = words;
     r->bases = bases;
     const size_t G = ctx->devs.size();
     const size_t total = (size_t)words + 2 * BSW_READS_SLACK;
     r->d_words.assign(G, nullptr);
-    if (bases) {                                     /* the pieces: whole reads, up to up_piece_bytes() raw bytes each */
+    if (bases) {                                     /* the pieces: whole reads, up to up_piece_bytes() raw bytes (as encoded) each */
         r->up.reset(new reads_up());
         reads_up &u = *r->up;
-        u.src.assign(reads, reads + n_reads);
+        u.src.resize(n_reads);
+        for (size_t i = 0; i < n_reads; ++i) u.src[i] = (const uint8_t *)reads[i];
+        u.enc = enc;
         const size_t per = up_piece_bytes();
         size_t acc = 0;
         u.cut.push_back(0);
         for (size_t i = 0; i < n_reads; ++i) {
-            if (acc && acc + (size_t)lens[i] > per) { u.cut.push_back(i); acc = 0; }
-            acc += (size_t)lens[i];
+            const size_t rb = reads_raw_bytes(lens[i], enc);
+            if (acc && acc + rb > per) { u.cut.push_back(i); acc = 0; }
+            acc += rb;
         }
         u.cut.push_back(n_reads);
         u.npieces = u.cut.size() - 1;
@@ -176,7 +186,7 @@ extern "C" int bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads,
         u.left = G * u.npieces;
         if (ctx->uploads.fetch_add(1) >= BSW_READS_MAX_UPLOADS) {
             ctx->uploads.fetch_sub(1);
-            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "bsw_reads_upload_start: %d uploads in flight already; wait for one first", BSW_READS_MAX_UPLOADS));
+            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "%s: %d uploads in flight already; wait for one first", who, BSW_READS_MAX_UPLOADS));
         }
     }
     /* the device copies and the events, here in the caller's thread: a failed start leaves none on any device */
@@ -199,11 +209,11 @@ extern "C" int bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads,
         }
     }
     int rc = BSW_OK;
-    if (he != hipSuccess) rc = fail(e, BSW_E_HIP, "bsw_reads_upload_start: device allocation: %s", hipGetErrorString(he));
+    if (he != hipSuccess) rc = fail(e, BSW_E_HIP, "%s: device allocation: %s", who, hipGetErrorString(he));
     (void)hipSetDevice(ctx->device0());
     if (!rc && r->up) {
         rc = pipeline_submit_job(ctx, up_piece, r.get(), r->up->npieces);
-        if (rc) fail(e, rc, "bsw_reads_upload_start: the pipeline could not be started");
+        if (rc) fail(e, rc, "%s: the pipeline could not be started", who);
     }
     if (rc) {
         up_release(ctx, r.get());
@@ -212,6 +222,16 @@ extern "C" int bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads,
     }
     *out = r.release();
     return BSW_OK;
+}
+
+extern "C" int bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out)
+{
+    return reads_start_any("bsw_reads_upload_start", ctx, (const void *const *)reads, lens, n_reads, BSW_READS_CODES, out);
+}
+
+extern "C" int bsw_reads_upload_start_enc(bsw_ctx *ctx, const void *const *reads, const int32_t *lens, size_t n_reads, int encoding, bsw_reads **out)
+{
+    return reads_start_any("bsw_reads_upload_start_enc", ctx, reads, lens, n_reads, encoding, out);
 }
 
 extern "C" int bsw_reads_test(bsw_ctx *ctx, const bsw_reads *rd)

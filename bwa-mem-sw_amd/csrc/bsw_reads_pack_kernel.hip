@@ -4,8 +4,10 @@
  *
  * Bound by memory: 1 byte per base in, half a byte out.  A group of BSW_RDPACK_GROUP lanes takes a read and lane l produces its
  * words l, l + 16, ...: the lanes of a group load neighbouring 16-byte lines of the read and store neighbouring 8-byte words.
- * A word is bsw_rdpack_word (bsw_reads_pack.h): two aligned 16-byte loads, a funnel shift, two squeezes — no byte loads, no LDS,
- * nothing in scratch.  A read of length 0 writes nothing.
+ * A word is bsw_rdpack_word_enc (bsw_reads_pack.h): two aligned 16-byte loads, a funnel shift, two squeezes — no byte loads, no
+ * LDS, nothing in scratch.  A read of length 0 writes nothing.  The record says how a read's bases are encoded — codes, FASTQ
+ * letters (translated eight bytes at a time in front of the squeeze), or 4-bit words (one load, half a byte per base in) — the
+ * same for the 16 lanes of a read, so the branch on it never splits a group.
  */
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -26,7 +28,7 @@ __global__ __launch_bounds__(RDPACK_THREADS) void bsw_reads_pack_kernel(const ui
         const bsw_rdpack_rec rc = rec[r];
         const int nw = (rc.len + 15) >> 4;
         uint64_t *dst = store + rc.woff;
-        for (int k = lane; k < nw; k += BSW_RDPACK_GROUP) dst[k] = bsw_rdpack_word(raw, rc.raw_off, rc.len, k);
+        for (int k = lane; k < nw; k += BSW_RDPACK_GROUP) dst[k] = bsw_rdpack_word_enc(raw, rc.raw_off, rc.len, k, rc.enc);
     }
 }
 

@@ -55,6 +55,8 @@ RD_MTASK = np.dtype([("read", "<u4"), ("is_rev", "<i4"), ("rb", "<i8"), ("re", "
 RD_CTASK = np.dtype([("read", "<u4"), ("qb", "<i4"), ("qe", "<i4"), ("w", "<i4"), ("rb", "<i8"), ("re", "<i8"),
                      ("w_cap", "<i4"), ("min_score", "<i4"), ("max_tries", "<i4"), ("_pad", "<i4")])
 assert RD_TASK.itemsize == 48 and RD_MTASK.itemsize == 32 and RD_CTASK.itemsize == 48
+# how the reads of a block are encoded at its upload (BSW_READS_*): codes 0..4, FASTQ letters, 4-bit words
+READS_CODES, READS_ASCII, READS_PACKED = 0, 1, 2
 MAX_DEVICES = 16
 CONFIG = np.dtype([("device", "<i4"), ("kernel", "<i4"), ("streams", "<i4"), ("pack_threads", "<i4"),
                    ("chunk_tasks", "<u8"), ("n_devices", "<i4"), ("devices", "<i4", (MAX_DEVICES,)),
@@ -162,6 +164,8 @@ def lib():
             "bsw_matesw_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
             "bsw_reads_upload": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp)]),
             "bsw_reads_upload_start": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp)]),
+            "bsw_reads_upload_enc": (C.c_int, [vp, vp, vp, sz, C.c_int, C.POINTER(vp)]),
+            "bsw_reads_upload_start_enc": (C.c_int, [vp, vp, vp, sz, C.c_int, C.POINTER(vp)]),
             "bsw_reads_test": (C.c_int, [vp, vp]),
             "bsw_reads_wait": (C.c_int, [vp, vp]),
             "bsw_reads_image": (C.c_int, [vp, vp, C.c_int, vp, sz]),
@@ -206,7 +210,7 @@ def lib():
 
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
-           "bsw_reads_upload", "bsw_reads_upload_start", "bsw_reads_test", "bsw_reads_wait", "bsw_reads_image", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
+           "bsw_reads_upload", "bsw_reads_upload_start", "bsw_reads_upload_enc", "bsw_reads_upload_start_enc", "bsw_reads_test", "bsw_reads_wait", "bsw_reads_image", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
            "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats", "bsw_set_align_long", "bsw_align_long", "bsw_align_long_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
            "bsw_device_count", "bsw_create", "bsw_create_sized", "bsw_abi_version", "bsw_chain_timeouts", "bsw_device_placement", "bsw_destroy", "bsw_last_error", "bsw_submit", "bsw_wait",
@@ -584,26 +588,46 @@ class BswContext:
         return t.value, res
 
     # resident read blocks: upload once, then the three stages name a read by index
-    def reads_upload(self, reads):
-        """bsw_reads_upload: `reads` is a sequence of uint8 arrays (codes 0..4).  Returns the block's handle; synchronous."""
-        reads = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
-        ptrs = np.array([r.ctypes.data if len(r) else 0 for r in reads], dtype=np.uint64)
-        lens = np.array([len(r) for r in reads], dtype=np.int32)
+    @staticmethod
+    def _reads_table(reads, encoding):
+        """(arrays kept alive, pointers, lengths in bases) of a block: uint8 arrays (codes or letters; bytes objects too), or for
+        READS_PACKED (words, n_bases) pairs, words a uint64 array of at least ceil(n_bases / 16) entries"""
+        if encoding == READS_PACKED:
+            arrs = [np.ascontiguousarray(w, dtype=np.uint64) for w, _ in reads]
+            lens = np.array([n for _, n in reads], dtype=np.int32)
+            for a, n in zip(arrs, lens):
+                if len(a) < (int(n) + 15) // 16:
+                    raise ValueError("a packed read of %d bases needs %d words, got %d" % (n, (int(n) + 15) // 16, len(a)))
+        else:
+            arrs = [np.frombuffer(r, dtype=np.uint8) if isinstance(r, (bytes, bytearray)) else np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+            lens = np.array([len(r) for r in arrs], dtype=np.int32)
+        ptrs = np.array([r.ctypes.data if n else 0 for r, n in zip(arrs, lens)], dtype=np.uint64)
+        return arrs, ptrs, lens
+
+    def reads_upload(self, reads, encoding=0):
+        """bsw_reads_upload / bsw_reads_upload_enc: `reads` is a sequence of uint8 arrays — codes 0..4 (READS_CODES) or FASTQ letters
+        (READS_ASCII) — or of (uint64 words, n_bases) pairs (READS_PACKED).  Returns the block's handle; synchronous."""
+        arrs, ptrs, lens = self._reads_table(reads, encoding)
         h = C.c_void_p()
-        self._chk(lib().bsw_reads_upload(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(reads), C.byref(h)), "bsw_reads_upload")
+        if encoding == READS_CODES:
+            self._chk(lib().bsw_reads_upload(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(arrs), C.byref(h)), "bsw_reads_upload")
+        else:
+            self._chk(lib().bsw_reads_upload_enc(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(arrs), int(encoding), C.byref(h)), "bsw_reads_upload_enc")
         return h
 
-    def reads_upload_start(self, reads):
-        """bsw_reads_upload_start: returns the block's handle at once; it may be handed to the *_reads_* submits at once.  The
-        arrays in `reads` are kept alive here until the block is freed (their bases belong to the upload until it is ready)."""
-        reads = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
-        ptrs = np.array([r.ctypes.data if len(r) else 0 for r in reads], dtype=np.uint64)
-        lens = np.array([len(r) for r in reads], dtype=np.int32)
+    def reads_upload_start(self, reads, encoding=0):
+        """bsw_reads_upload_start / bsw_reads_upload_start_enc: returns the block's handle at once; it may be handed to the
+        *_reads_* submits at once.  `reads` as for reads_upload; the arrays are kept alive here until the block is freed (their
+        bases belong to the upload until it is ready)."""
+        arrs, ptrs, lens = self._reads_table(reads, encoding)
         h = C.c_void_p()
-        self._chk(lib().bsw_reads_upload_start(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(reads), C.byref(h)), "bsw_reads_upload_start")
+        if encoding == READS_CODES:
+            self._chk(lib().bsw_reads_upload_start(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(arrs), C.byref(h)), "bsw_reads_upload_start")
+        else:
+            self._chk(lib().bsw_reads_upload_start_enc(self.handle, ptrs.ctypes.data, lens.ctypes.data, len(arrs), int(encoding), C.byref(h)), "bsw_reads_upload_start_enc")
         if not hasattr(self, "_reads_alive"):
             self._reads_alive = {}
-        self._reads_alive[h.value] = reads
+        self._reads_alive[h.value] = arrs
         return h
 
     def reads_test(self, rd):

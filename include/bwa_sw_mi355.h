@@ -274,8 +274,8 @@ int      bsw_host_unregister(void *p);
  * bsw_wait waits for ALL of them and returns the first failure in submit order.
  *
  * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, the three
- * *_reads_* submits, bsw_reads_upload, bsw_reads_upload_start, bsw_reads_test, bsw_reads_wait, bsw_reads_free, bsw_wait_ticket,
- * bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
+ * *_reads_* submits, bsw_reads_upload, bsw_reads_upload_enc, bsw_reads_upload_start, bsw_reads_upload_start_enc, bsw_reads_test,
+ * bsw_reads_wait, bsw_reads_free, bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
  * every other call that takes the context (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free,
  * bsw_host_stats, bsw_reads_image) needs it to itself.  bsw_set_align_long, bsw_align_long and bsw_align_long_stats take no
  * context and may be called from any thread at any time; a change applies to the calls that enter the library afterwards.
@@ -659,6 +659,28 @@ int      bsw_reads_upload(bsw_ctx *ctx, const uint8_t *const *reads, const int32
  *     launches anything that reads the block; other tickets are left alone.  bsw_reads_free then frees what there is.
  *   - bsw_reads_free answers BSW_E_BUSY while the upload is in flight; bsw_destroy waits for it, as it does for tickets. */
 int      bsw_reads_upload_start(bsw_ctx *ctx, const uint8_t *const *reads, const int32_t *lens, size_t n_reads, bsw_reads **out);
+/* UPLOAD ENCODINGS.  A host holds its reads as codes only after a conversion pass; the _enc forms of the two uploads take them
+ * as they lie at two other moments.  lens[] stays in BASES whatever the encoding, and the block is THE SAME IMAGE: reads that
+ * spell the same bases give, word for word, the device copy bsw_reads_upload makes of their codes, slack words included, so
+ * nothing behind the upload changes.  The two calls above are the _enc calls with BSW_READS_CODES; everything said there — the
+ * threading rules, at most 2 uploads in flight, tickets ordered behind the upload on the device, bsw_reads_test / _wait / _image /
+ * _free / _info, the failure rules, 65 535 bases per read and 2^28 - 2^13 words per block — holds for them word for word.
+ *   BSW_READS_ASCII   FASTQ letters, as a reader thread hands a block over: A a -> 0, C c -> 1, G g -> 2, T t -> 3, EVERY other
+ *                     byte value -> 4 (N n, IUPAC letters, '-', U, and the bytes 0..4 themselves).  No byte is an error.
+ *   BSW_READS_PACKED  the device's own format, as bsw_pack_bases writes it: reads[i] addresses ceil(lens[i] / 16) uint64 words,
+ *                     all of them readable.  Nibbles 0..3 are stored as they are, 4..15 as 4; the nibbles behind a read's last
+ *                     base may hold anything and come out zero.  A read of non-zero length whose pointer is not 8-byte aligned
+ *                     is refused: BSW_E_INVAL, the text names the read, no block is made.
+ *   any other value   BSW_E_INVAL; nothing is allocated or queued.
+ * A read's RAW bytes are lens[i] for the byte encodings and 8 * ceil(lens[i] / 16) for the packed one: that is what crosses
+ * PCIe per read and device (plus a 16-byte record on the asynchronous path), what bsw_host_stats.h2d_bytes grows by, and what
+ * the asynchronous upload cuts its pieces by.  Letters are translated, and words clamped and masked, by the GPU kernel that
+ * packs the codes form (bsw_reads_upload_start_enc) or on the caller's thread (bsw_reads_upload_enc). */
+#define BSW_READS_CODES   0   /* one byte per base, codes 0..4, larger stored as 4: the form of the two calls above */
+#define BSW_READS_ASCII   1   /* one byte per base, FASTQ letters */
+#define BSW_READS_PACKED  2   /* reads[i] addresses uint64 words, 16 bases each, base k in bits [4k, 4k+3] */
+int      bsw_reads_upload_enc(bsw_ctx *ctx, const void *const *reads, const int32_t *lens, size_t n_reads, int encoding, bsw_reads **out);
+int      bsw_reads_upload_start_enc(bsw_ctx *ctx, const void *const *reads, const int32_t *lens, size_t n_reads, int encoding, bsw_reads **out);
 /* 1: the block is ready, 0: its upload is in flight, < 0: the upload's failure.  Never blocks. */
 int      bsw_reads_test(bsw_ctx *ctx, const bsw_reads *rd);
 /* blocks until the upload is over (the watchdog of every wait applies) and returns its error code; may be called again */

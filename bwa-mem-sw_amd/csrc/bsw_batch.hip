@@ -1555,7 +1555,7 @@ struct ticket_t {
     bsw_result *out = nullptr;
     bool packed = false;
     size_t n = 0;
-    int kind = 0;                               /* 0 seed extension; 1 CIGAR, 2 mate rescue (f4: bsw_cigar_ref_submit_t / bsw_matesw_ref_submit_t) */
+    int kind = 0;                               /* 0 seed extension; 1 CIGAR, 2 mate rescue, 3 region patch (f4: bsw_cigar_ref_submit_t / bsw_matesw_ref_submit_t / bsw_patch_ref_submit_t) */
     f4_submit f4;
     std::atomic<size_t> remaining{0};           /* chunks whose results have not been handed over yet */
     size_t nchunks = 0;                         /* chunks the submit was cut into */
@@ -1777,7 +1777,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
                          d, s, (unsigned long long)tid, base, n, t1 - t0, t2 - t1, t3 - t2, tnow() - t3, t0, rc ? " FAILED" : "");
     };
 
-    /* A CIGAR or mate-rescue chunk: the whole of cigar_chunk / matesw_chunk on the slot's lane — its stage_t, its stream, its
+    /* A CIGAR, mate-rescue or region-patch chunk: the whole of cigar_chunk / matesw_chunk / patch_chunk on the slot's lane — its stage_t, its stream, its
      * watchdog event, its own scratch, the reference copy of its device.  The chunk function waits for its own work (read-backs
      * into pinned memory in front of sync_stream) and drains the stream itself when it fails, so nothing of the chunk is queued
      * when it reports; it takes no turn at the input-DMA gate. */
@@ -1806,12 +1806,14 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
         else if (f.kind == 1)
             rc = cigar_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ctasks ? f.ctasks + base : nullptr, n, f.max_cigar, f.cigars ? f.cigars + base * (size_t)f.max_cigar : nullptr,
                              f.max_md, f.md ? f.md + base * (size_t)f.max_md : nullptr, f.cres + base, f.rd, f.rd ? f.rd_ctasks + base : nullptr);
+        else if (f.kind == 3)
+            rc = patch_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ptasks ? f.ptasks + base : nullptr, n, f.pres + base, f.rd, f.rd ? f.rd_ptasks + base : nullptr);
         else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks ? f.mtasks + base : nullptr, n, f.mres + base, f.rd, f.rd ? f.rd_mtasks + base : nullptr, f.al_mode);
         if (rc) ticket_fail(t, rc, e);
         else { pp.h2d_bytes += lane.h2d; pp.d2h_bytes += lane.d2h; pp.chunks += 1; }
         chunk_done(t);                              /* (the ticket may be collected and freed from here on) */
         if (dbg) fprintf(stderr, "[bsw] slot %zu.%zu ticket %llu %s chunk @%zu n=%zu: %.3f ms (t0=%.3f)%s\n", d, s, (unsigned long long)tid,
-                         f.kind == 1 ? "cigar" : "matesw", base, n, tnow() - t0, t0, rc ? " FAILED" : "");
+                         f.kind == 1 ? "cigar" : f.kind == 3 ? "patch" : "matesw", base, n, tnow() - t0, t0, rc ? " FAILED" : "");
     };
 
     /* A job that is no ticket's (pipeline_submit_job): like a CIGAR chunk it takes the slot's lane once the extension chunk in

@@ -9,7 +9,9 @@
  *      formula) equals the previous one's would return the previous score and end the loop on "score == last": it is counted, not run;
  *   3. bsw_cigar_md_kernel derives NM and MD once per task from its final CIGAR, and settles bwa's no-gap shortcut.
  * A chunk runs on a LANE (f4_lane, bsw_internal.h): the context's own for bsw_cigar_ref_batch, a pipeline slot's for the chunks of
- * bsw_cigar_ref_submit_t (bsw_batch.hip), which reads back into pinned memory in front of the watchdog's wait. */
+ * bsw_cigar_ref_submit_t (bsw_batch.hip), which reads back into pinned memory in front of the watchdog's wait.
+ * Behind it, in the second half of the file: mem_patch_reg (bsw_patch_ref_batch and its ticket forms), which is one try of the
+ * above for its score alone, between two pieces of host arithmetic. */
 #include "bsw_f4_host.h"
 
 #include <climits>
@@ -342,6 +344,310 @@ extern "C" int bsw_cigar_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const
     if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_reads_submit: bad argument"));
     if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_reads_submit: the read block was uploaded through another context, or is being freed"));
     const int rc = cigar_submit(ctx, p, ref, nullptr, rd, tasks, n, max_cigar, cigars, max_md, md, res, ticket, "bsw_cigar_reads_submit");
+    if (rc) reads_release(rd);                       /* no ticket was made */
+    return rc;
+}
+
+/* ======== mem_patch_reg (bwamem.c, bwa >= 0.7.10; restated as recalled): bsw_patch_ref_batch and its ticket forms ========
+ * The two halves around the alignment run on the host: the pre-tests before a task is staged, the 0.90 test once its score is
+ * back.  Between them a chunk is a cigar_chunk of one try without its outputs: the same records for bsw_pack_kernel (the slice
+ * starts at base a.qb of the read), ONE round of the global kernels with z == NULL and cigars == NULL, and 8 bytes per task back.
+ * The few tasks of bwa's no-gap shortcut are gathered into records of their own for bsw_cigar_md_kernel, which sums their matrix
+ * entries (its one CIGAR word per such task is the only CIGAR room a chunk reserves; no MD slot, no backtrack matrix). */
+
+/* everything before bwa_gen_cigar2; 64-bit where bwa's int would overflow on values no aligner produces */
+static int patch_pretest(const bsw_params &p, int64_t l_pac, const bsw_preg &a, const bsw_preg &b, int *w_out)
+{
+    if (a.rb < l_pac && b.rb >= l_pac) return 0;                                    /* different strands */
+    if (a.qb >= b.qb || a.qe >= b.qe || a.re >= b.re) return 0;                     /* not colinear */
+    int64_t w = (a.re - b.rb) - ((int64_t)a.qe - b.qb);
+    w = w > 0 ? w : -w;
+    double r = (double)(a.re - b.rb) / (double)(b.re - a.rb) - (double)(a.qe - b.qb) / (double)(b.qe - a.qb);
+    r = r > 0. ? r : -r;
+    const int64_t ow = p.w;
+    if (a.re < b.rb || a.qe < b.qb) {                                               /* a gap between them: the tighter limits */
+        if (w > ow << 1 || r >= 0.05f) return 0;
+    } else if (w > ow << 2 || r >= 0.05f * 2) return 0;
+    w += (int64_t)a.w + b.w;
+    w = w < ow << 2 ? w : ow << 2;
+    if (w_out) *w_out = (int)std::min<int64_t>(w, INT_MAX);
+    return 1;
+}
+
+/* everything behind it: the return value */
+static int patch_decide(const bsw_preg &a, const bsw_preg &b, int score)
+{
+    const double sum = (double)((int64_t)b.score + a.score);
+    const double qd = (double)(b.qe - a.qb) / (double)(((int64_t)b.qe - b.qb) + ((int64_t)a.qe - a.qb)) * sum + .499;
+    const double rd = (double)(b.re - a.rb) / (double)((b.re - b.rb) + (a.re - a.rb)) * sum + .499;
+    auto to_int = [](double v) { return v >= 2147483647. ? INT_MAX : v > -2147483648. ? (int)v : INT_MIN; };   /* (out of int's range, NaN: as x86's conversion answers) */
+    const int q_s = to_int(qd), r_s = to_int(rd);
+    if ((double)score / (double)(q_s > r_s ? q_s : r_s) < 0.90f) return 0;
+    return score;
+}
+
+extern "C" int bsw_patch_pretest(const bsw_params *p, int64_t l_pac, const bsw_preg *a, const bsw_preg *b, int *w)
+{
+    if (w) *w = 0;
+    if (!p || !a || !b) return 0;
+    return patch_pretest(*p, l_pac, *a, *b, w);
+}
+extern "C" int bsw_patch_decide(const bsw_preg *a, const bsw_preg *b, int gscore)
+{
+    if (!a || !b) return 0;
+    return patch_decide(*a, *b, gscore);
+}
+
+/* task i in the pointer form's terms (resident reads: query stays NULL, l_query is the read's length) */
+static inline bsw_ptask ptask_of(const bsw_ptask *tasks, const bsw_reads *rd, const bsw_rd_ptask *rtasks, size_t i)
+{
+    if (!rtasks) return tasks[i];
+    const bsw_rd_ptask &r = rtasks[i];
+    bsw_ptask t;
+    t.query = nullptr; t.l_query = r.read < rd->rd.size() ? rd->rd[r.read].len : -1; t._pad = 0; t.a = r.a; t.b = r.b;
+    return t;
+}
+
+/* does task t reach the GPU?  Its band w_, and whether bwa_gen_cigar2 has an alignment for [a.rb, b.re) at all */
+static inline bool patch_runs(const bsw_params &pp, int64_t l_pac, const bsw_ptask &t, int *w_)
+{
+    if (!patch_pretest(pp, l_pac, t.a, t.b, w_)) return false;
+    const int64_t rb = t.a.rb, re = t.b.re;
+    return !((rb < l_pac && re > l_pac) || rb < 0 || re > 2 * l_pac);
+}
+
+BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ptask *tasks,
+                          size_t n, bsw_presult *res, const bsw_reads *rd, const bsw_rd_ptask *rtasks)
+{
+    stage_t &st = *L.st;
+    hipStream_t s = L.s;
+    hipError_t he;
+    const int64_t l_pac = ref->l_pac;
+    int rc = stage_records(e, st, n, true);
+    if (rc) return rc;
+    std::vector<bsw_gdtask> gt(n);
+    std::vector<bsw_cdtask> cd;                       /* the no-gap shortcut's tasks, gathered */
+    std::vector<uint32_t> live, cd_of, cls;
+    std::vector<uint8_t> rev(n, 0);
+    const global_route route;
+    uint64_t acc = 0;
+    raw_span sp;
+    for (size_t i = 0; i < n; ++i) {
+        const bsw_ptask t = ptask_of(tasks, rd, rtasks, i);
+        bsw_dtask &d = st.h_tasks.p[i];
+        bsw_rawoff &r = st.h_roff.p[i];
+        bsw_refx &x = st.h_desc.p[i];
+        memset(&d, 0, sizeof(d));
+        memset(&r, 0, sizeof(r));
+        x = bsw_refx{0, 0};
+        memset(&gt[i], 0, sizeof(bsw_gdtask));
+        res[i] = bsw_presult{0, 0, 0, 1};
+        int w_ = 0;
+        if (!patch_runs(pp, l_pac, t, &w_)) continue;
+        const int lq = t.b.qe - t.a.qb, rlen = (int)(t.b.re - t.a.rb);
+        const uint32_t qw = (uint32_t)acc, tw = (uint32_t)(acc + nwords(lq));
+        acc += nwords(lq) + nwords(rlen);
+        /* where the slice starts: a byte offset into the raw bytes, or (resident reads) the position of base a.qb of its read */
+        const uint32_t at = rd ? rd->pos(rtasks[i].read) + (uint32_t)t.a.qb : (uint32_t)sp.bytes;
+        if (t.a.rb >= l_pac) {            /* left side only: read backwards from its last base, target downwards from re - 1 */
+            d.lq_off = qw; d.lt_off = tw; d.lqlen = (uint16_t)lq; d.ltlen = (uint16_t)rlen;
+            r.lq = at + (uint32_t)lq - 1u;
+            x.xl = t.b.re - 1;
+            rev[i] = 1;
+        } else {                          /* right side only: read forwards, target upwards from rb */
+            d.rq_off = qw; d.rt_off = tw; d.rqlen = (uint16_t)lq; d.rtlen = (uint16_t)rlen;
+            r.rq = at;
+            x.xr = t.a.rb;
+        }
+        if (!rd) sp.add(t.query + t.a.qb, (size_t)lq);
+        res[i].w = w_;
+        res[i].status = 0;                /* (runs: settled below) */
+        if (lq == rlen && w_ == 0) {      /* the no-gap shortcut: the NM / MD kernel sums the matrix entries */
+            bsw_cdtask c;
+            memset(&c, 0, sizeof(c));
+            c.q_off = qw; c.t_off = tw; c.qlen = lq; c.tlen = rlen;
+            c.flags = BSW_CD_NOGAP | (rev[i] ? BSW_CD_REV : 0u);
+            cd.push_back(c);
+            cd_of.push_back((uint32_t)i);
+            continue;
+        }
+        bsw_gdtask &g = gt[i];
+        g.q_off = qw; g.t_off = tw; g.qlen = lq; g.tlen = rlen; g.w = gen_cigar_band(pp, lq, rlen, w_);
+        const int n_col = g.qlen < 2 * g.w + 1 ? g.qlen : 2 * g.w + 1;
+        live.push_back((uint32_t)i);
+        cls.push_back((uint32_t)route(g.qlen, n_col));
+    }
+    if (live.empty() && cd.empty()) return BSW_OK;    /* nothing passed the pre-tests: no HIP call */
+    staged_raw raw;
+    rc = stage_raw(e, st, n, sp, acc, true, false, 1, [&](size_t i, int) {
+        if (res[i].status) return raw_piece{nullptr, 0, &bsw_rawoff::rq, false};
+        return raw_piece{tasks[i].query + tasks[i].a.qb, (size_t)(tasks[i].b.qe - tasks[i].a.qb), rev[i] ? &bsw_rawoff::lq : &bsw_rawoff::rq, rev[i] != 0};
+    }, &raw);
+    if (rc) return rc;
+    const size_t nc = cd.size();
+    if ((he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess || (he = L.g_res->reserve(n + 1)) != hipSuccess ||
+        (nc && ((he = L.c_tasks->reserve(nc + 1)) != hipSuccess || (he = L.c_res->reserve(nc + 1)) != hipSuccess || (he = L.g_cig->reserve(nc + 1)) != hipSuccess)))
+        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    /* a slot reads back into pinned memory: the scores | the shortcut's records */
+    const size_t in_gt = (nc + 1) * sizeof(bsw_cdtask), in_order = in_gt + (n + 1) * sizeof(bsw_gdtask);
+    if (L.h_back && ((he = L.h_back->reserve(n * sizeof(bsw_gresult) + nc * sizeof(bsw_cresult) + 16)) != hipSuccess ||
+                     (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
+        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    std::vector<bsw_gresult> gr(live.empty() ? 0 : n);
+    std::vector<bsw_cresult> cr(nc);
+    class_lists cl;
+    cl.build(route.classes(), cls.data(), live.data(), live.size());
+    drain_on_failure drain(ctx, s, L.ev);
+    if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
+    if ((rc = stage_pack(e, L, n, BSW_PACK_REV_LEFT, ref, rd)) != BSW_OK) return rc;
+    if (!live.empty()) {
+        HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, L.dma_src(gt.data(), n * sizeof(bsw_gdtask), in_gt), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(cl.order.data(), live.size() * sizeof(uint32_t), in_order), live.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        L.h2d += n * sizeof(bsw_gdtask) + live.size() * sizeof(uint32_t);
+        if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p, nullptr, nullptr, 0, L.g_res->p, s)) != BSW_OK) return rc;
+    }
+    if (nc) {
+        HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), nc * sizeof(bsw_cdtask), 0), nc * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
+        L.h2d += nc * sizeof(bsw_cdtask);
+        HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.c_tasks->p, (uint32_t)nc, L.g_cig->p, 1, L.g_res->p, nullptr, 0, L.c_res->p, s));
+    }
+    rc = lane_read_back(ctx, e, L, {{gr.data(), L.g_res->p, gr.size() * sizeof(bsw_gresult)}, {cr.data(), L.c_res->p, nc * sizeof(bsw_cresult)}});
+    if (rc) return rc;
+    for (uint32_t i : live) res[i].gscore = gr[i].score;
+    for (size_t k = 0; k < nc; ++k) res[cd_of[k]].gscore = cr[k].score;
+    for (size_t i = 0; i < n; ++i) {
+        if (res[i].status) continue;
+        const bsw_ptask t = ptask_of(tasks, rd, rtasks, i);
+        res[i].score = patch_decide(t.a, t.b, res[i].gscore);
+        res[i].status = res[i].score > 0 ? 0 : 2;
+    }
+    drain.done();
+    return BSW_OK;
+}
+
+/* what all three entry points check before anything runs or is queued; *pp keeps p->w (opt->w).  cells[i] (may be NULL):
+ * the banded cells of task i, 0 for one that does not reach the GPU; seqb[i]: its sequence bytes */
+static int patch_validate(errs &e, const bsw_params *p, const bsw_ref *ref, const bsw_ptask *tasks, const bsw_reads *rd, const bsw_rd_ptask *rtasks,
+                          size_t n, bsw_params *pp, bsw_dparams *dp, std::vector<uint64_t> &cells, std::vector<uint64_t> &seqb)
+{
+    bsw_params p0 = *p;
+    p0.w = 0;                                         /* (the kernels' band is per task) */
+    int rc = check_params(e, &p0, dp);
+    if (rc) return rc;
+    if (p->w < 0) return fail(e, BSW_E_INVAL, "patch: negative band w = %d", p->w);
+    *pp = *p;
+    cells.assign(n, 0);
+    seqb.assign(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (rd && rtasks[i].read >= rd->rd.size())
+            return fail(e, BSW_E_INVAL, "patch task %zu: read %u is not in the block of %zu reads", i, rtasks[i].read, rd->rd.size());
+        const bsw_ptask t = ptask_of(tasks, rd, rtasks, i);
+        if (t.l_query < 0) return fail(e, BSW_E_INVAL, "patch task %zu: negative length", i);
+        if (t.l_query && !t.query && !rd) return fail(e, BSW_E_INVAL, "patch task %zu: NULL read", i);
+        for (const bsw_preg *g : {&t.a, &t.b}) {
+            if (g->rb >= g->re) return fail(e, BSW_E_INVAL, "patch task %zu: region with rb >= re", i);
+            if (g->qb < 0 || g->qb >= g->qe || g->qe > t.l_query)
+                return fail(e, BSW_E_INVAL, "patch task %zu: [qb, qe) = [%d, %d) is not a slice of the read of %d bases", i, g->qb, g->qe, t.l_query);
+            if (g->w < 0) return fail(e, BSW_E_INVAL, "patch task %zu: negative band", i);
+        }
+        if (t.a.rb > t.b.rb) return fail(e, BSW_E_INVAL, "patch task %zu: a.rb > b.rb (bwa asserts a.rb <= b.rb)", i);
+        if ((int64_t)t.a.score + t.b.score <= 0) return fail(e, BSW_E_INVAL, "patch task %zu: a.score + b.score <= 0", i);
+        int w_ = 0;
+        if (!patch_runs(*pp, ref->l_pac, t, &w_)) continue;
+        const int64_t lq = (int64_t)t.b.qe - t.a.qb, rlen = t.b.re - t.a.rb;
+        if (lq > BSW_GLOBAL_MAX_QLEN || rlen > BSW_MAX_TLEN)
+            return fail(e, BSW_E_LIMIT, "patch task %zu: beyond BSW_GLOBAL_MAX_QLEN / BSW_MAX_TLEN", i);
+        const int band = gen_cigar_band(*pp, (int)lq, (int)rlen, w_);
+        cells[i] = (uint64_t)std::min<int64_t>(lq, 2 * (int64_t)band + 1) * (uint64_t)rlen;
+        seqb[i] = (uint64_t)(lq + rlen);
+    }
+    return BSW_OK;
+}
+
+/* The work target of a patch chunk, in banded cells (min(l_query, 2 w + 1) x (re - rb) under the task's band, summed), from the
+ * sweep of tools/patch_rate.py ("sweep" of profiles/patch_rate.json), submit + wait of one ticket at 2^24 .. 2^30:
+ * 65 536 pairs of 150 bases 3.9 / 3.4 / 3.2 / 3.3 / 3.5 / 3.4 / 3.5 ms (from 2^28 on the same four chunks: a submit is spread over
+ * the slots first); 4 096 pairs of 2 000 bases 218 / 116 / 61 / 36 / 19 / 12 / 12 ms — a chunk of 2^28 cells holds only 512
+ * such alignments, too few to fill the device, and the chunks of a ticket add up.  2^30 is where the long shape levels off and the
+ * short one is unchanged; F4_CIGAR_CHUNK_WORK (2^28, where this started) loses 1.6 x at the long shape, beyond the runs' ranges.
+ * BSW_F4_PATCH_WORK overrides it (tests, measurements). */
+#define F4_PATCH_CHUNK_WORK (1ull << 30)
+#define PATCH_BATCH_WORK (4ull << 30)                  /* a sub-batch of the synchronous call: as many cells as bsw_cigar_ref_batch's hold backtrack bytes */
+static uint64_t patch_work_switch()                   /* BSW_F4_PATCH_WORK, 0: not set */
+{
+    static const uint64_t v = getenv("BSW_F4_PATCH_WORK") && atof(getenv("BSW_F4_PATCH_WORK")) >= 1.0 ? (uint64_t)atof(getenv("BSW_F4_PATCH_WORK")) : 0;
+    return v;
+}
+static uint64_t patch_chunk_work() { return patch_work_switch() ? patch_work_switch() : F4_PATCH_CHUNK_WORK; }
+
+extern "C" int bsw_patch_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ptask *tasks, size_t n, bsw_presult *res)
+{
+    if (!ctx) return BSW_E_INVAL;
+    errs &e = ctx->err;
+    if (!p || !ref || (!tasks && n) || (!res && n)) return fail(e, BSW_E_INVAL, "bsw_patch_ref_batch: bad argument");
+    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
+        return fail(e, BSW_E_INVAL, "bsw_patch_ref_batch: the reference was uploaded through another context");
+    int rc = busy_check(ctx, "bsw_patch_ref_batch");
+    if (rc) return rc;
+    bsw_params pp;
+    bsw_dparams dp;
+    std::vector<uint64_t> cells, seqb;
+    rc = patch_validate(e, p, ref, tasks, nullptr, nullptr, n, &pp, &dp, cells, seqb);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(ctx->device0()));
+    f4_lane L = ctx_lane(ctx);
+    /* sub-batches run one after the other, so they are large: the sequence arena's bound and PATCH_BATCH_WORK banded cells (no
+     * backtrack term), or what BSW_F4_PATCH_WORK says */
+    span_caps caps;
+    caps.work = patch_work_switch() ? patch_work_switch() : PATCH_BATCH_WORK;
+    const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) { return span_cost{0, seqb[i], 0, cells[i], 0, 0}; }, caps);
+    for (const chunk_span &c : spans) {
+        rc = patch_chunk(ctx, e, L, pp, dp, ref, tasks + c.base, c.cnt, res + c.base);
+        if (rc) return rc;
+    }
+    return BSW_OK;
+}
+
+/* both ticket forms: tasks (pointer form) or rd + rtasks (resident reads) */
+static int patch_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ptask *tasks, const bsw_reads *rd, const bsw_rd_ptask *rtasks,
+                        size_t n, bsw_presult *res, bsw_ticket *ticket, const char *what)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
+    if (!p || !ref || (!tasks && !rtasks && n) || (!res && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: bad argument", what));
+    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
+        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what));
+    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
+    f4_submit f;
+    f.kind = 3;
+    std::vector<uint64_t> cells, seqb;
+    int rc = patch_validate(e, p, ref, tasks, rd, rtasks, n, &f.pp, &f.dp, cells, seqb);
+    if (rc) return ctx_fail(ctx, e, rc);
+    f.ref = ref; f.ptasks = tasks; f.rd = rd; f.rd_ptasks = rtasks; f.n = n; f.pres = res;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) total += cells[i];
+    span_caps caps;
+    caps.work = std::max<uint64_t>(f4_chunk_work(ctx, total, patch_chunk_work()), 1);
+    f.spans = cut_spans(n, [&](size_t i) { return span_cost{0, seqb[i], 0, cells[i], 0, 0}; }, caps);
+    return pipeline_submit_f4(ctx, std::move(f), ticket, what);
+}
+
+extern "C" int bsw_patch_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ptask *tasks, size_t n, bsw_presult *res,
+                                      bsw_ticket *ticket)
+{
+    return patch_submit(ctx, p, ref, tasks, nullptr, nullptr, n, res, ticket, "bsw_patch_ref_submit");
+}
+
+extern "C" int bsw_patch_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_ptask *tasks,
+                                        size_t n, bsw_presult *res, bsw_ticket *ticket)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;
+    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_patch_reads_submit: bad argument"));
+    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_patch_reads_submit: the read block was uploaded through another context, or is being freed"));
+    const int rc = patch_submit(ctx, p, ref, nullptr, rd, tasks, n, res, ticket, "bsw_patch_reads_submit");
     if (rc) reads_release(rd);                       /* no ticket was made */
     return rc;
 }

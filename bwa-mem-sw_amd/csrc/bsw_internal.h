@@ -464,7 +464,7 @@ struct chunk_span {
     size_t base, cnt;
 };
 
-/* A ticketed CIGAR (kind 1) or mate-rescue (kind 2) submit as its entry point hands it to the pipeline: validated, the band
+/* A ticketed CIGAR (kind 1), mate-rescue (kind 2) or region-patch (kind 3) submit as its entry point hands it to the pipeline: validated, the band
  * taken out of the parameters, cut into chunks.  The caller's arrays stay the caller's until the ticket is collected. */
 struct f4_submit {
     int kind = 0;
@@ -473,15 +473,18 @@ struct f4_submit {
     const bsw_ref *ref = nullptr;
     const bsw_ctask *ctasks = nullptr;
     const bsw_mtask *mtasks = nullptr;
-    const bsw_reads *rd = nullptr;    /* non-NULL: the tasks name reads of this resident block (rd_ctasks / rd_mtasks instead of the two above) */
+    const bsw_ptask *ptasks = nullptr;
+    const bsw_reads *rd = nullptr;    /* non-NULL: the tasks name reads of this resident block (rd_ctasks / rd_mtasks / rd_ptasks instead of the three above) */
     const bsw_rd_ctask *rd_ctasks = nullptr;
     const bsw_rd_mtask *rd_mtasks = nullptr;
+    const bsw_rd_ptask *rd_ptasks = nullptr;
     size_t n = 0;
     int max_cigar = 0, max_md = 0;
     uint32_t *cigars = nullptr;
     char *md = nullptr;
     bsw_cresult *cres = nullptr;
     bsw_mresult *mres = nullptr;
+    bsw_presult *pres = nullptr;
     std::vector<chunk_span> spans;    /* chunk k -> device k mod n_devices */
     int al_mode = 0;                  /* mate rescue: bsw_align_long() as the submit found it; the chunks route by this, never by the switch */
 };
@@ -508,6 +511,9 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
                           const bsw_reads *rd = nullptr, const bsw_rd_ctask *rtasks = nullptr);
 BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
                            bsw_mresult *res, const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr, int al_mode = 0);
+/* mem_patch_reg (kind 3): pp.w is opt->w here, not taken out as for the other two */
+BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ptask *tasks,
+                          size_t n, bsw_presult *res, const bsw_reads *rd = nullptr, const bsw_rd_ptask *rtasks = nullptr);
 
 /* ---- bsw_f4.hip: the long-query route of ksw_align2 (bsw_set_align_long).  bsw_align_long.hip, the unit that owns the switch and
  * names the launcher of bsw_align_long_kernel.hip, registers this table when the library is loaded; a program linked without that

@@ -55,6 +55,12 @@ RD_MTASK = np.dtype([("read", "<u4"), ("is_rev", "<i4"), ("rb", "<i8"), ("re", "
 RD_CTASK = np.dtype([("read", "<u4"), ("qb", "<i4"), ("qe", "<i4"), ("w", "<i4"), ("rb", "<i8"), ("re", "<i8"),
                      ("w_cap", "<i4"), ("min_score", "<i4"), ("max_tries", "<i4"), ("_pad", "<i4")])
 assert RD_TASK.itemsize == 48 and RD_MTASK.itemsize == 32 and RD_CTASK.itemsize == 48
+# mem_patch_reg (bsw_patch_ref_batch): the fields it reads of two regions of one read
+PREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("w", "<i4")])
+PTASK = np.dtype([("query", "<u8"), ("l_query", "<i4"), ("_pad", "<i4"), ("a", PREG), ("b", PREG)])
+RD_PTASK = np.dtype([("read", "<u4"), ("_pad", "<i4"), ("a", PREG), ("b", PREG)])
+PRESULT = np.dtype([("score", "<i4"), ("w", "<i4"), ("gscore", "<i4"), ("status", "<i4")])
+assert PREG.itemsize == 32 and PTASK.itemsize == 80 and RD_PTASK.itemsize == 72 and PRESULT.itemsize == 16
 # how the reads of a block are encoded at its upload (BSW_READS_*): codes 0..4, FASTQ letters, 4-bit words
 READS_CODES, READS_ASCII, READS_PACKED = 0, 1, 2
 MAX_DEVICES = 16
@@ -174,6 +180,11 @@ def lib():
             "bsw_submit_reads_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
             "bsw_matesw_reads_submit_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
             "bsw_cigar_reads_submit_t": (C.c_int, [vp, vp, vp, vp, vp, sz, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_uint64)]),
+            "bsw_patch_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
+            "bsw_patch_ref_submit_t": (C.c_int, [vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
+            "bsw_patch_reads_submit_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
+            "bsw_patch_pretest": (C.c_int, [vp, C.c_int64, vp, vp, C.POINTER(C.c_int)]),
+            "bsw_patch_decide": (C.c_int, [vp, vp, C.c_int]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -210,6 +221,7 @@ def lib():
 
 EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
+           "bsw_patch_ref_batch", "bsw_patch_ref_submit_t", "bsw_patch_reads_submit_t", "bsw_patch_pretest", "bsw_patch_decide",
            "bsw_reads_upload", "bsw_reads_upload_start", "bsw_reads_upload_enc", "bsw_reads_upload_start_enc", "bsw_reads_test", "bsw_reads_wait", "bsw_reads_image", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
            "bsw_infer_dir", "bsw_matesw_windows", "bsw_align_batch", "ksw_align2", "ksw_align", "ksw_extend2", "ksw_extend", "bsw_set_default_variant", "bsw_scalar_stats", "bsw_set_rtl_packed", "bsw_rtl_packed", "bsw_rtl_packed_stats", "bsw_set_align_long", "bsw_align_long", "bsw_align_long_stats", "bsw_host_alloc", "bsw_host_free",
            "bsw_host_register", "bsw_host_unregister", "bsw_batch_order", "bsw_refbatch_submit", "bsw_refbatch_wait", "bsw_default_params", "bsw_default_config",
@@ -550,6 +562,33 @@ class BswContext:
                   "bsw_matesw_ref_batch")
         return res
 
+    def patch_ref_batch(self, params, ref, ptasks):
+        """mem_patch_reg against a reference from ref_upload (PTASK records: the whole read and two of its regions; params["w"]
+        is opt->w).  Returns a PRESULT array."""
+        res = np.zeros(len(ptasks), dtype=PRESULT)
+        self._chk(lib().bsw_patch_ref_batch(self.handle, params.ctypes.data, ref, ptasks.ctypes.data, len(ptasks), res.ctypes.data),
+                  "bsw_patch_ref_batch")
+        return res
+
+    def submit_patch_ref(self, params, ref, ptasks):
+        """patch_ref_batch as a ticket of the streaming pipeline (bsw_patch_ref_submit_t).  Returns (ticket, PRESULT array); the
+        array is filled once the ticket is complete.  The reads that `ptasks` points to must stay alive until then."""
+        res = np.zeros(len(ptasks), dtype=PRESULT)
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_patch_ref_submit_t(self.handle, params.ctypes.data, ref, ptasks.ctypes.data, len(ptasks), res.ctypes.data,
+                                               C.byref(t)), "bsw_patch_ref_submit")
+        self._keep_alive(t.value, params, ptasks, res)
+        return t.value, res
+
+    def submit_patch_reads(self, params, ref, rd, rdptasks):
+        """submit_patch_ref against a resident read block (RD_PTASK records).  Returns (ticket, PRESULT array)."""
+        res = np.zeros(len(rdptasks), dtype=PRESULT)
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_patch_reads_submit_t(self.handle, params.ctypes.data, ref, rd, rdptasks.ctypes.data, len(rdptasks),
+                                                 res.ctypes.data, C.byref(t)), "bsw_patch_reads_submit")
+        self._keep_alive(t.value, params, rdptasks, res)
+        return t.value, res
+
     def _keep_alive(self, ticket, *arrays):
         if self._keep is None:
             self._keep = {}
@@ -887,6 +926,20 @@ def pac_get_seq(pac, l_pac, beg, end):
 def infer_bw(l1, l2, score, a, q, r):
     """mem_reg2aln's infer_bw (bsw_infer_bw)."""
     return int(lib().bsw_infer_bw(l1, l2, score, a, q, r))
+
+
+def patch_pretest(params, l_pac, a, b):
+    """mem_patch_reg up to bwa_gen_cigar2 (bsw_patch_pretest; a, b: PREG records): (1, w_) when the alignment runs, else (0, 0)."""
+    a, b = np.ascontiguousarray(a, dtype=PREG), np.ascontiguousarray(b, dtype=PREG)
+    w = C.c_int(0)
+    r = lib().bsw_patch_pretest(params.ctypes.data, l_pac, a.ctypes.data, b.ctypes.data, C.byref(w))
+    return int(r), int(w.value)
+
+
+def patch_decide(a, b, gscore):
+    """mem_patch_reg behind bwa_gen_cigar2 (bsw_patch_decide): its return value for the alignment's score."""
+    a, b = np.ascontiguousarray(a, dtype=PREG), np.ascontiguousarray(b, dtype=PREG)
+    return int(lib().bsw_patch_decide(a.ctypes.data, b.ctypes.data, int(gscore)))
 
 
 def infer_dir(l_pac, b1, b2):

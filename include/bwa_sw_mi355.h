@@ -31,8 +31,12 @@
  *                              (bwa host software, not the RTL)
  *   bsw_matesw_ref_batch       mem_matesw's ksw_align2 against the device-resident
  *                              reference (bwa host software, not the RTL)
- *   bsw_cigar_ref_submit_t /   the two calls above as tickets of the streaming pipeline:
- *   bsw_matesw_ref_submit_t    every device of the context, beside extension submits
+ *   bsw_patch_ref_batch        mem_patch_reg (mem_sort_dedup_patch, bwa >= 0.7.10) against the
+ *                              device-resident reference: the score of bwa_gen_cigar2 without a
+ *                              CIGAR, and the tests around it (bwa host software, not the RTL)
+ *   bsw_cigar_ref_submit_t /   the three calls above as tickets of the streaming pipeline:
+ *   bsw_matesw_ref_submit_t /  every device of the context, beside extension submits
+ *   bsw_patch_ref_submit_t
  *   bsw_reads_upload,          a read block resident on every device; the three stages as tickets that name a
  *   bsw_*_reads_submit_t       read by its index (only coordinates cross PCIe)
  *
@@ -273,8 +277,8 @@ int      bsw_host_unregister(void *p);
  * submit order, so the tail of one overlaps the head of the next.  One more than that answers BSW_E_BUSY.
  * bsw_wait waits for ALL of them and returns the first failure in submit order.
  *
- * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, the three
- * *_reads_* submits, bsw_reads_upload, bsw_reads_upload_enc, bsw_reads_upload_start, bsw_reads_upload_start_enc, bsw_reads_test,
+ * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, bsw_patch_ref_submit_t, the four
+ * *_reads_* submits (bsw_patch_reads_submit_t among them), bsw_reads_upload, bsw_reads_upload_enc, bsw_reads_upload_start, bsw_reads_upload_start_enc, bsw_reads_test,
  * bsw_reads_wait, bsw_reads_free, bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
  * every other call that takes the context (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free,
  * bsw_host_stats, bsw_reads_image) needs it to itself.  bsw_set_align_long, bsw_align_long and bsw_align_long_stats take no
@@ -727,6 +731,55 @@ int      bsw_matesw_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_
 int      bsw_cigar_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd,
                                   const bsw_rd_ctask *tasks, size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md,
                                   bsw_cresult *res, bsw_ticket *ticket);
+
+/* ---- mem_patch_reg (bwamem.c of bwa >= 0.7.10, restated AS RECALLED: bwa's source is not in this tree) against the resident
+ * reference: may two regions a, b of one read be joined into one?  Pre-tests on the host (strand, colinearity, the band and
+ * ratio limits), bwa_gen_cigar2 with n_cigar = 0, cigar = 0 — the SCORE of the banded global alignment of read[a.qb, b.qe)
+ * against the reference [a.rb, b.re), band w_ through bwa_gen_cigar2's formula, both reversed on the reverse strand, the no-gap
+ * shortcut when the spans agree and w_ == 0 — and the 0.90 test of that score against the two regions' scores.  No backtrack
+ * matrix, no CIGAR, no NM / MD: 8 bytes per alignment come back.  mem_sort_dedup_patch's bookkeeping (a merged region changes
+ * later pairs) stays with the caller: INTEGRATION.md "Region patching". ---- */
+typedef struct bsw_preg {            /* the fields of mem_alnreg_t that mem_patch_reg reads */
+    int64_t  rb, re;
+    int32_t  qb, qe, score, w;
+} bsw_preg;                          /* 32 bytes */
+typedef struct bsw_ptask {
+    const uint8_t *query;            /* the WHOLE read, codes 0..4 */
+    int32_t  l_query, _pad;
+    bsw_preg a, b;                   /* a.rb <= b.rb, as bwa asserts */
+} bsw_ptask;                         /* 80 bytes */
+typedef struct bsw_rd_ptask {        /* bsw_ptask with query = reads[read], l_query = lens[read] */
+    uint32_t read;
+    int32_t  _pad;
+    bsw_preg a, b;
+} bsw_rd_ptask;                      /* 72 bytes */
+typedef struct bsw_presult {
+    int32_t score;                   /* mem_patch_reg's return value: > 0 exactly when bwa merges, else 0 */
+    int32_t w;                       /* *_w (the band handed to bwa_gen_cigar2) whenever the alignment ran, else 0 */
+    int32_t gscore;                  /* bwa_gen_cigar2's score whenever the alignment ran (status 0 or 2), else 0 */
+    int32_t status;                  /* 0 merged; 1 not run (a pre-test returned 0, or bwa_gen_cigar2 has no alignment: the interval
+                                        bridges l_pac or leaves [0, 2*l_pac)); 2 run, and the return value is 0 (ratio below 0.90f) */
+} bsw_presult;                       /* 16 bytes */
+/* Batched mem_patch_reg on the context's first device; opt->w is p->w.  The first malformed task rejects the call: NULL read of
+ * non-zero length, a region with rb >= re or without 0 <= qb < qe <= l_query, a.rb > b.rb, a.w / b.w / p->w < 0,
+ * a.score + b.score <= 0 -> BSW_E_INVAL; a task that PASSES the pre-tests with b.qe - a.qb > BSW_GLOBAL_MAX_QLEN or
+ * b.re - a.rb > BSW_MAX_TLEN -> BSW_E_LIMIT (one that fails a pre-test is never limit-checked and never reaches the GPU). */
+int      bsw_patch_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ptask *tasks, size_t n, bsw_presult *res);
+/* The same as a TICKET of the context's pipeline: the contract of bsw_cigar_ref_submit_t, word for word (one ticket space,
+ * BSW_MAX_INFLIGHT, the checks above in the caller's thread and no ticket when one fails, chunk k on device k mod n_devices,
+ * BSW_E_BUSY changes nothing, n == 0 completes at once), with the results of bsw_patch_ref_batch byte for byte.  tasks[], the
+ * reads and res stay valid until the ticket is collected; the reads form (read >= n_reads, a block of another context ->
+ * BSW_E_INVAL; the regions are checked against lens[read]) holds its block until then: bsw_reads_free answers BSW_E_BUSY.
+ * BSW_F4_PATCH_WORK replaces the work of a chunk (banded cells) for tests and measurements only. */
+int      bsw_patch_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_ptask *tasks, size_t n, bsw_presult *res,
+                                bsw_ticket *ticket);
+int      bsw_patch_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_ptask *tasks,
+                                  size_t n, bsw_presult *res, bsw_ticket *ticket);
+/* Host only, no GPU: the two halves around the alignment, for a caller's replay of mem_sort_dedup_patch and for tests.
+ * bsw_patch_pretest: 1 when bwa reaches bwa_gen_cigar2, with *w (may be NULL) the band it hands over; 0 when bwa returns 0 before.
+ * bsw_patch_decide: mem_patch_reg's return value for bwa_gen_cigar2's score gscore (gscore, or 0 below the 0.90f ratio). */
+int      bsw_patch_pretest(const bsw_params *p, int64_t l_pac, const bsw_preg *a, const bsw_preg *b, int *w);
+int      bsw_patch_decide(const bsw_preg *a, const bsw_preg *b, int gscore);
 
 /* ---- device sequence format: 4 bits per base, 16 bases per uint64, base k of a word in bits [4k,4k+3];
  * codes > 4 are stored as 4 (N).  words must hold (len+15)/16 entries.  Returns 1 if an N was seen. ---- */

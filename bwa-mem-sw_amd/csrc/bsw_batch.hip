@@ -1538,9 +1538,9 @@ static std::vector<std::vector<chunk_span>> plan_chunks(size_t n, size_t chunk, 
  * wait for the slot's previous chunk -> input DMAs in the device's chunk order -> pack, bin, DP kernels -> result DMA.  The
  * host pass of the slot's next chunk runs while its previous one is still on the GPU: it only needs the pinned host staging,
  * which is free again as soon as that chunk's input DMAs are done.
- * A ticket has a KIND: seed extension (above), or one of the two stages behind it against the resident reference — CIGAR
- * (bsw_cigar_ref_submit_t) and mate rescue (bsw_matesw_ref_submit_t) — whose chunks run cigar_chunk / matesw_chunk on the slot's
- * lane (process_f4 in slot_main).  All kinds share the ticket space, BSW_MAX_INFLIGHT and the devices' queues. */
+ * A ticket is a seed extension (above), or one of the stages behind it against the resident reference — CIGAR, mate rescue,
+ * region patch (bsw_cigar.hip, bsw_matesw.hip) — which brings its own chunk function: f4.run, called on the slot's lane
+ * (process_f4 in slot_main).  Both share the ticket space, BSW_MAX_INFLIGHT and the devices' queues. */
 struct ticket_t {
     uint64_t id = 0;
     bsw_params p{};
@@ -1554,9 +1554,7 @@ struct ticket_t {
     ~ticket_t() { reads_release(rd_held); }
     bsw_result *out = nullptr;
     bool packed = false;
-    size_t n = 0;
-    int kind = 0;                               /* 0 seed extension; 1 CIGAR, 2 mate rescue, 3 region patch (f4: bsw_cigar_ref_submit_t / bsw_matesw_ref_submit_t / bsw_patch_ref_submit_t) */
-    f4_submit f4;
+    f4_submit f4;                               /* with a `run`: no seed extension but a CIGAR, mate-rescue or region-patch submit; the members above stay unset */
     std::atomic<size_t> remaining{0};           /* chunks whose results have not been handed over yet */
     size_t nchunks = 0;                         /* chunks the submit was cut into */
     std::atomic<int> abort{0};                  /* a chunk failed: the others do nothing any more */
@@ -1777,21 +1775,18 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
                          d, s, (unsigned long long)tid, base, n, t1 - t0, t2 - t1, t3 - t2, tnow() - t3, t0, rc ? " FAILED" : "");
     };
 
-    /* A CIGAR, mate-rescue or region-patch chunk: the whole of cigar_chunk / matesw_chunk / patch_chunk on the slot's lane — its stage_t, its stream, its
-     * watchdog event, its own scratch, the reference copy of its device.  The chunk function waits for its own work (read-backs
+    /* A CIGAR, mate-rescue or region-patch chunk: the whole of the submit's chunk function (f4_submit::run) on the slot's lane — its stage_t, its stream,
+     * its watchdog event, its own scratch, the reference copy of its device.  The chunk function waits for its own work (read-backs
      * into pinned memory in front of sync_stream) and drains the stream itself when it fails, so nothing of the chunk is queued
      * when it reports; it takes no turn at the input-DMA gate. */
     f4_lane lane;
     lane.dev = d; lane.st = &st; lane.s = stream; lane.ev = dev.events[s];
-    lane.bind(dev.f4[s]);
-    lane.h_back = &dev.f4[s].h_back;
-    lane.h_in = &dev.f4[s].h_in;
+    lane.b = &dev.f4[s]; lane.h_back = &lane.b->h_back; lane.h_in = &lane.b->h_in;
     lane.h2d_total = &pp.h2d_bytes;
     auto process_f4 = [&](const chunk_job &job) {
         ticket_t *t = job.t;
-        const f4_submit &f = t->f4;
-        const size_t n = job.span.cnt, base = job.span.base;
         const uint64_t tid = t->id;
+        const char *name = t->f4.name;              /* (a literal: it outlives the ticket) */
         const double t0 = dbg ? tnow() : 0;
         finish();                                   /* the slot's extension chunk in flight owns the stage_t until it is handed over */
         errs e;
@@ -1803,17 +1798,12 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
             dev_err = hipSetDevice(dev.device);
         } else if (ctx->dead) rc = fail(e, BSW_E_HIP, "context is dead (an earlier wait for the GPU timed out)");      /* nothing more is queued on a hung device */
         else if (t->abort) rc = fail(e, BSW_E_HIP, "aborted: another chunk failed");
-        else if (f.kind == 1)
-            rc = cigar_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ctasks ? f.ctasks + base : nullptr, n, f.max_cigar, f.cigars ? f.cigars + base * (size_t)f.max_cigar : nullptr,
-                             f.max_md, f.md ? f.md + base * (size_t)f.max_md : nullptr, f.cres + base, f.rd, f.rd ? f.rd_ctasks + base : nullptr);
-        else if (f.kind == 3)
-            rc = patch_chunk(ctx, e, lane, f.pp, f.dp, f.ref, f.ptasks ? f.ptasks + base : nullptr, n, f.pres + base, f.rd, f.rd ? f.rd_ptasks + base : nullptr);
-        else rc = matesw_chunk(ctx, e, lane, f.dp, f.ref, f.mtasks ? f.mtasks + base : nullptr, n, f.mres + base, f.rd, f.rd ? f.rd_mtasks + base : nullptr, f.al_mode);
+        else rc = t->f4.run(ctx, e, lane, job.span);
         if (rc) ticket_fail(t, rc, e);
         else { pp.h2d_bytes += lane.h2d; pp.d2h_bytes += lane.d2h; pp.chunks += 1; }
         chunk_done(t);                              /* (the ticket may be collected and freed from here on) */
         if (dbg) fprintf(stderr, "[bsw] slot %zu.%zu ticket %llu %s chunk @%zu n=%zu: %.3f ms (t0=%.3f)%s\n", d, s, (unsigned long long)tid,
-                         f.kind == 1 ? "cigar" : f.kind == 3 ? "patch" : "matesw", base, n, tnow() - t0, t0, rc ? " FAILED" : "");
+                         name, job.span.base, job.span.cnt, tnow() - t0, t0, rc ? " FAILED" : "");
     };
 
     /* A job that is no ticket's (pipeline_submit_job): like a CIGAR chunk it takes the slot's lane once the extension chunk in
@@ -1833,7 +1823,7 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
             dq.q.pop_front();
             lk.unlock();
             if (job.fn) process_job(job);
-            else if (job.t->kind) process_f4(job);
+            else if (job.t->f4.run) process_f4(job);
             else process(job);
             account();
             lk.lock();
@@ -1889,6 +1879,33 @@ BSW_LOCAL void pipeline_shutdown(bsw_ctx *ctx)
     delete pp;
 }
 
+/* How every submit ends: the ticket, cut into `total` chunks, joins the live ones, and enqueue(ticket), called under pp.mu, puts
+ * its chunks on the devices' queues.  With BSW_MAX_INFLIGHT tickets live already it answers BSW_E_BUSY instead: nothing is queued,
+ * no id is taken, and rd (the read block the entry point acquired, or NULL) stays the entry point's to give back.  Once the
+ * ticket exists IT owns the block. */
+template <class F>
+static int register_ticket(bsw_ctx *ctx, pipeline &pp, std::shared_ptr<ticket_t> t, size_t total, const bsw_reads *rd, bsw_ticket *ticket, const char *what, F enqueue)
+{
+    t->remaining = total;
+    t->nchunks = total;
+    t->done = total == 0;
+    {
+        std::lock_guard<std::mutex> lk(pp.mu);
+        if (pp.live.size() >= BSW_MAX_INFLIGHT) {
+            errs e;
+            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "%s: %d submits in flight already (BSW_MAX_INFLIGHT); wait for one first", what, BSW_MAX_INFLIGHT));
+        }
+        t->id = pp.next_id++;
+        if (ticket) *ticket = t->id;
+        enqueue(t.get());
+        t->rd_held = rd;
+        pp.live.push_back(std::move(t));
+        pp.submits += 1;
+    }
+    pp.cv_work.notify_all();
+    return BSW_OK;
+}
+
 static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *tasks, const bsw_ref *ref, const bsw_ref_task *rtasks,
                          size_t n, bsw_result *out, bool packed, bsw_ticket *ticket, const char *what,
                          const bsw_reads *rd = nullptr /* acquired by the caller; the ticket gives it back */, const bsw_rd_task *rdtasks = nullptr)
@@ -1903,7 +1920,7 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
     pipeline &pp = *ctx->pipe.load();
     const size_t G = ctx->devs.size();
     std::shared_ptr<ticket_t> t(new ticket_t());
-    t->p = *p; t->dp = dp; t->tasks = tasks; t->ref = ref; t->rtasks = rtasks; t->out = out; t->packed = packed; t->n = n;
+    t->p = *p; t->dp = dp; t->tasks = tasks; t->ref = ref; t->rtasks = rtasks; t->out = out; t->packed = packed;
     t->rd = rd; t->rdtasks = rdtasks;
     /* chunk_tasks = 0 (the default): sized by WORK, not by seeds.  A chunk's launches must fill the machine — 128 Ki seeds of
      * the 150 bp single bin (131-base sides) do; PE seeds with their two shorter sides hold half the cells per seed and want
@@ -1937,58 +1954,30 @@ static int submit_common(bsw_ctx *ctx, const bsw_params *p, const bsw_task *task
     const std::vector<std::vector<chunk_span>> chunks = plan_chunks(n, chunk, G);
     size_t total = 0;
     for (const auto &v : chunks) total += v.size();
-    t->remaining = total;
-    t->nchunks = total;
-    t->done = total == 0;
-    {
-        std::lock_guard<std::mutex> lk(pp.mu);
-        if (pp.live.size() >= BSW_MAX_INFLIGHT)
-            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "%s: %d submits in flight already (BSW_MAX_INFLIGHT); wait for one first", what, BSW_MAX_INFLIGHT));
-        t->id = pp.next_id++;
-        if (ticket) *ticket = t->id;
+    return register_ticket(ctx, pp, t, total, rd, ticket, what, [&](ticket_t *tk) {
         /* chunk c of the submit -> device c mod G; the devices' queues are filled in the submit's own chunk order */
         size_t left = total;
         for (size_t k = 0; left; ++k)
             for (size_t d = 0; d < G; ++d)
-                if (k < chunks[d].size()) { pp.devs[d]->q.push_back(chunk_job{t.get(), chunks[d][k], pp.devs[d]->next_seq++}); --left; }
-        t->rd_held = rd;                             /* the ticket exists: from here on IT gives the block back */
-        pp.live.push_back(std::move(t));
-        pp.submits += 1;
-    }
-    pp.cv_work.notify_all();
-    return BSW_OK;
+                if (k < chunks[d].size()) { pp.devs[d]->q.push_back(chunk_job{tk, chunks[d][k], pp.devs[d]->next_seq++}); --left; }
+    });
 }
 
-/* a validated CIGAR / mate-rescue submit (bsw_cigar.hip, bsw_matesw.hip) becomes a ticket: one ticket space with the extension
+/* a validated CIGAR / mate-rescue / patch submit (bsw_cigar.hip, bsw_matesw.hip) becomes a ticket: one ticket space with the extension
  * submits, the same BSW_MAX_INFLIGHT, chunk k on device k mod G behind whatever the devices' queues hold already */
 BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket, const char *what)
 {
     if (ticket) *ticket = 0;
-    errs e;
     int rc = pipeline_start(ctx);
     if (rc) return rc;
     pipeline &pp = *ctx->pipe.load();
     const size_t G = ctx->devs.size();
     std::shared_ptr<ticket_t> t(new ticket_t());
-    t->kind = f.kind; t->n = f.n; t->ref = f.ref; t->p = f.pp; t->dp = f.dp;
     t->f4 = std::move(f);
-    const size_t total = t->f4.spans.size();
-    t->remaining = total;
-    t->nchunks = total;
-    t->done = total == 0;
-    {
-        std::lock_guard<std::mutex> lk(pp.mu);
-        if (pp.live.size() >= BSW_MAX_INFLIGHT)
-            return ctx_fail(ctx, e, fail(e, BSW_E_BUSY, "%s: %d submits in flight already (BSW_MAX_INFLIGHT); wait for one first", what, BSW_MAX_INFLIGHT));
-        t->id = pp.next_id++;
-        if (ticket) *ticket = t->id;
-        for (size_t k = 0; k < total; ++k) pp.devs[k % G]->q.push_back(chunk_job{t.get(), t->f4.spans[k], 0});
-        t->rd_held = t->f4.rd;                       /* (a *_reads_* submit: acquired by its entry point, given back when the ticket goes) */
-        pp.live.push_back(std::move(t));
-        pp.submits += 1;
-    }
-    pp.cv_work.notify_all();
-    return BSW_OK;
+    const std::vector<chunk_span> &spans = t->f4.spans;
+    return register_ticket(ctx, pp, t, spans.size(), t->f4.rd, ticket, what, [&](ticket_t *tk) {
+        for (size_t k = 0; k < spans.size(); ++k) pp.devs[k % G]->q.push_back(chunk_job{tk, spans[k], 0});
+    });
 }
 
 /* a job per piece on EVERY device's queue, behind what is queued and ahead of whatever is submitted later; it is no submit: no

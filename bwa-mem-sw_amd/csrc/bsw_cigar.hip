@@ -50,13 +50,14 @@ static inline bsw_ctask ctask_of(const bsw_ctask *tasks, const bsw_rd_ctask *rta
     return t;
 }
 
-BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
-                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res,
-                          const bsw_reads *rd, const bsw_rd_ctask *rtasks)
+/* rd != NULL: the chunk's tasks are rtasks[0..n) and name reads of the resident block (tasks is NULL then): the per-task work is
+ * the device records plus a base position — no span, no registration test, no gather, no raw bytes */
+static int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
+                       size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res,
+                       const bsw_reads *rd, const bsw_rd_ctask *rtasks)
 {
     stage_t &st = *L.st;
     hipStream_t s = L.s;
-    hipError_t he;
     const int64_t l_pac = ref->l_pac;
     int rc = stage_records(e, st, n, true);
     if (rc) return rc;
@@ -67,12 +68,6 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_ctask t = ctask_of(tasks, rtasks, i);
-        bsw_dtask &d = st.h_tasks.p[i];
-        bsw_rawoff &r = st.h_roff.p[i];
-        bsw_refx &x = st.h_desc.p[i];
-        memset(&d, 0, sizeof(d));
-        memset(&r, 0, sizeof(r));
-        x = bsw_refx{0, 0};
         bsw_cdtask &c = cd[i];
         memset(&c, 0, sizeof(c));
         cstate &q = cs[i];
@@ -82,23 +77,15 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         /* bwa: no alignment for an empty read, an empty or bridging interval, or one bns_get_seq cannot return whole */
         if (t.l_query == 0 || t.rb >= t.re || (t.rb < l_pac && t.re > l_pac) || t.rb < 0 || t.re > 2 * l_pac) {
             c.flags = BSW_CD_STATUS;
+            clear_records(st, i);
             continue;
         }
         const int rlen = (int)(t.re - t.rb);
-        const bool rev = t.rb >= l_pac;
-        const uint32_t qw = (uint32_t)acc, tw = (uint32_t)(acc + nwords(t.l_query));
-        acc += nwords(t.l_query) + nwords(rlen);
+        const bool rev = t.rb >= l_pac;           /* the reverse strand: a left-side-only seed */
         /* where the slice starts: a byte offset into the raw bytes, or (resident reads) the position of base qb of its read */
         const uint32_t at = rd ? rd->pos(rtasks[i].read) + (uint32_t)rtasks[i].qb : (uint32_t)sp.bytes;
-        if (rev) {                        /* left side only: read backwards from its last base, target downwards from re - 1 */
-            d.lq_off = qw; d.lt_off = tw; d.lqlen = (uint16_t)t.l_query; d.ltlen = (uint16_t)rlen;
-            r.lq = at + (uint32_t)t.l_query - 1u;
-            x.xl = t.re - 1;
-        } else {                          /* right side only: read forwards, target upwards from rb */
-            d.rq_off = qw; d.rt_off = tw; d.rqlen = (uint16_t)t.l_query; d.rtlen = (uint16_t)rlen;
-            r.rq = at;
-            x.xr = t.rb;
-        }
+        const interval_words iw = lay_interval(st, i, t.l_query, rlen, rev, at, t.rb, t.re, acc);
+        const uint32_t qw = iw.qw, tw = iw.tw;
         if (!rd) sp.add(t.query, (size_t)t.l_query);
         c.q_off = qw; c.t_off = tw; c.qlen = t.l_query; c.tlen = rlen;
         c.flags = rev ? BSW_CD_REV : 0u;
@@ -129,18 +116,13 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         const int wmax = gen_cigar_band(pp, cd[i].qlen, cd[i].tlen, INT_MAX);
         zmax += (uint64_t)std::min(cd[i].qlen, 2 * wmax + 1) * (uint64_t)cd[i].tlen;
     }
-    if ((he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
-        (he = L.g_res->reserve(n + 1)) != hipSuccess || (he = L.g_z->reserve((size_t)zmax + 64)) != hipSuccess ||
-        (he = L.g_cig->reserve(n * (size_t)max_cigar + 1)) != hipSuccess ||
-        (he = L.c_tasks->reserve(n + 1)) != hipSuccess || (he = L.c_res->reserve(n + 1)) != hipSuccess ||
-        (md && (he = L.c_md->reserve(n * (size_t)max_md + 1)) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    if ((rc = reserve_all(e, "device staging", {{L.b->g_tasks, n + 1}, {L.b->g_order, n + 1}, {L.b->g_res, n + 1}, {L.b->g_z, (size_t)zmax + 64}, {L.b->g_cig, n * (size_t)max_cigar + 1},
+                                                {L.b->c_tasks, n + 1}, {L.b->c_res, n + 1}, {L.b->c_md, n * (size_t)max_md + 1, md != nullptr}})) != BSW_OK) return rc;
     /* a slot reads back into pinned memory: the scores of a try, then results | CIGARs | MD slots */
     const size_t cigb = cigars ? n * (size_t)max_cigar * sizeof(uint32_t) : 0, mdb = md ? n * (size_t)max_md : 0;
     const size_t in_gt = (n + 1) * sizeof(bsw_cdtask), in_order = in_gt + (n + 1) * sizeof(bsw_gdtask);
-    if (L.h_back && ((he = L.h_back->reserve(std::max(n * sizeof(bsw_cresult) + cigb + mdb, n * sizeof(bsw_gresult)) + 16)) != hipSuccess ||
-                     (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    if (L.h_back && (rc = reserve_all(e, "pinned staging", {{*L.h_back, std::max(n * sizeof(bsw_cresult) + cigb + mdb, n * sizeof(bsw_gresult)) + 16},
+                                                            {*L.h_in, in_order + (n + 1) * sizeof(uint32_t)}})) != BSW_OK) return rc;
     /* what the tries need (declared here: the guard behind them is destroyed first) */
     std::vector<bsw_gresult> gr(L.h_back ? 0 : n);
     const bsw_gresult *grp = L.h_back ? (const bsw_gresult *)L.h_back->p : gr.data();
@@ -149,7 +131,7 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     std::vector<uint32_t> cls, live;
     drain_on_failure drain(ctx, s, L.ev);
     if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
-    HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), n * sizeof(bsw_cdtask), 0), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(L.b->c_tasks.p, L.dma_src(cd.data(), n * sizeof(bsw_cdtask), 0), n * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
     L.h2d += n * sizeof(bsw_cdtask);
     if ((rc = stage_pack(e, L, n, BSW_PACK_REV_LEFT, ref, rd)) != BSW_OK) return rc;
 
@@ -168,11 +150,8 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
             cls[k] = (uint32_t)route(g.qlen, n_col);     /* bsw_global_batch's routing */
         }
         cl.build(route.classes(), cls.data(), live.data(), live.size());
-        HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, L.dma_src(gt.data(), n * sizeof(bsw_gdtask), in_gt), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(cl.order.data(), live.size() * sizeof(uint32_t), in_order), live.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        L.h2d += n * sizeof(bsw_gdtask) + live.size() * sizeof(uint32_t);
-        if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p, L.g_z->p, L.g_cig->p, max_cigar, L.g_res->p, s)) != BSW_OK) return rc;
-        if ((rc = lane_read_back(ctx, e, L, {{L.h_back ? nullptr : gr.data(), L.g_res->p, n * sizeof(bsw_gresult)}})) != BSW_OK) return rc;
+        if ((rc = upload_launch_global(e, L, cl, dp, gt.data(), n, in_gt, in_order, L.b->g_z.p, L.b->g_cig.p, max_cigar)) != BSW_OK) return rc;
+        if ((rc = lane_read_back(ctx, e, L, {{L.h_back ? nullptr : gr.data(), L.b->g_res.p, n * sizeof(bsw_gresult)}})) != BSW_OK) return rc;
         /* mem_reg2aln: if (score == last || w2 == w_cap) break; last = score; w2 <<= 1; } while (++i < max_tries && score < min_score) */
         std::vector<uint32_t> next;
         for (uint32_t i : live) {
@@ -197,9 +176,9 @@ BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
         }
         live.swap(next);
     }
-    HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.c_tasks->p, (uint32_t)n, L.g_cig->p, max_cigar, L.g_res->p,
-                                   md ? L.c_md->p : nullptr, max_md, L.c_res->p, s));
-    rc = lane_read_back(ctx, e, L, {{res, L.c_res->p, n * sizeof(bsw_cresult)}, {cigars, L.g_cig->p, cigb}, {md, L.c_md->p, mdb}});
+    HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.b->c_tasks.p, (uint32_t)n, L.b->g_cig.p, max_cigar, L.b->g_res.p,
+                                   md ? L.b->c_md.p : nullptr, max_md, L.b->c_res.p, s));
+    rc = lane_read_back(ctx, e, L, {{res, L.b->c_res.p, n * sizeof(bsw_cresult)}, {cigars, L.b->g_cig.p, cigb}, {md, L.b->c_md.p, mdb}});
     if (rc) return rc;
     for (size_t i = 0; i < n; ++i) {
         bsw_cresult &r = res[i];
@@ -258,11 +237,7 @@ extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
 {
     if (!ctx) return BSW_E_INVAL;
     errs &e = ctx->err;
-    if (!p || !ref || (!tasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1))
-        return fail(e, BSW_E_INVAL, "bsw_cigar_ref_batch: bad argument");
-    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return fail(e, BSW_E_INVAL, "bsw_cigar_ref_batch: the reference was uploaded through another context");
-    int rc = busy_check(ctx, "bsw_cigar_ref_batch");
+    int rc = ref_entry_check(ctx, "bsw_cigar_ref_batch", !p || !ref || (!tasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1), ref, false);
     if (rc) return rc;
     bsw_params pp;
     bsw_dparams dp;
@@ -278,7 +253,7 @@ extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
     }, span_caps());
     for (const chunk_span &c : spans) {
         rc = cigar_chunk(ctx, e, L, pp, dp, ref, tasks + c.base, c.cnt, max_cigar, cigars ? cigars + c.base * (size_t)max_cigar : nullptr, max_md,
-                         md ? md + c.base * (size_t)max_md : nullptr, res + c.base);
+                         md ? md + c.base * (size_t)max_md : nullptr, res + c.base, nullptr, nullptr);
         if (rc) return rc;
     }
     return BSW_OK;
@@ -293,7 +268,7 @@ extern "C" int bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
 #define F4_CIGAR_OUT_MAX (1ull << 30)                  /* CIGAR words and MD slots of a chunk: 1 GiB each at the most */
 static uint64_t cigar_chunk_work()
 {
-    static const uint64_t v = getenv("BSW_F4_CIGAR_WORK") && atof(getenv("BSW_F4_CIGAR_WORK")) >= 1.0 ? (uint64_t)atof(getenv("BSW_F4_CIGAR_WORK")) : F4_CIGAR_CHUNK_WORK;
+    static const uint64_t v = chunk_work_env("BSW_F4_CIGAR_WORK", F4_CIGAR_CHUNK_WORK);
     return v;
 }
 
@@ -306,20 +281,22 @@ static int cigar_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, c
 {
     if (!ctx) return BSW_E_INVAL;
     if (ticket) *ticket = 0;
+    int rc = ref_entry_check(ctx, what, !p || !ref || (!tasks && !rtasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1), ref, true);
+    if (rc) return rc;
     errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
-    if (!p || !ref || (!tasks && !rtasks && n) || (!res && n) || max_cigar < 1 || (md && max_md < 1))
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: bad argument", what));
-    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what));
-    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
-    f4_submit f;
-    f.kind = 1;
-    int rc = cigar_validate(e, p, tasks, n, &f.pp, &f.dp, rd, rtasks);
+    bsw_params pp;
+    bsw_dparams dp;
+    rc = cigar_validate(e, p, tasks, n, &pp, &dp, rd, rtasks);
     if (rc) return ctx_fail(ctx, e, rc);
-    f.ref = ref; f.ctasks = tasks; f.rd = rd; f.rd_ctasks = rtasks; f.n = n; f.max_cigar = max_cigar; f.cigars = cigars; f.max_md = max_md; f.md = md; f.cres = res;
+    f4_submit f;
+    f.name = "cigar"; f.rd = rd;
+    f.run = [=](bsw_ctx *cx, errs &ce, f4_lane &L, chunk_span c) {
+        return cigar_chunk(cx, ce, L, pp, dp, ref, tasks ? tasks + c.base : nullptr, c.cnt, max_cigar, cigars ? cigars + c.base * (size_t)max_cigar : nullptr, max_md,
+                           md ? md + c.base * (size_t)max_md : nullptr, res + c.base, rd, rd ? rtasks + c.base : nullptr);
+    };
     std::vector<uint64_t> nz(n), ns(n);               /* one walk over the tasks: the band formula is the cost of this pass */
     uint64_t total = 0;
-    for (size_t i = 0; i < n; ++i) { cigar_task_cost(f.pp, ctask_of(tasks, rtasks, i), nz[i], ns[i]); total += nz[i]; }
+    for (size_t i = 0; i < n; ++i) { cigar_task_cost(pp, ctask_of(tasks, rtasks, i), nz[i], ns[i]); total += nz[i]; }
     span_caps caps;                                   /* the batch call's bounds, the room of the outputs, and the work of a chunk */
     caps.work = std::min<uint64_t>(f4_chunk_work(ctx, total, cigar_chunk_work()), 4ull << 30);
     caps.out_per_task = std::max<uint64_t>((uint64_t)max_cigar * sizeof(uint32_t), md ? (uint64_t)max_md : 0);
@@ -338,14 +315,8 @@ extern "C" int bsw_cigar_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const b
 extern "C" int bsw_cigar_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_ctask *tasks,
                                         size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res, bsw_ticket *ticket)
 {
-    if (!ctx) return BSW_E_INVAL;
-    if (ticket) *ticket = 0;
-    errs e;
-    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_reads_submit: bad argument"));
-    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_cigar_reads_submit: the read block was uploaded through another context, or is being freed"));
-    const int rc = cigar_submit(ctx, p, ref, nullptr, rd, tasks, n, max_cigar, cigars, max_md, md, res, ticket, "bsw_cigar_reads_submit");
-    if (rc) reads_release(rd);                       /* no ticket was made */
-    return rc;
+    return reads_submit(ctx, rd, ticket, "bsw_cigar_reads_submit",
+                        [&] { return cigar_submit(ctx, p, ref, nullptr, rd, tasks, n, max_cigar, cigars, max_md, md, res, ticket, "bsw_cigar_reads_submit"); });
 }
 
 /* ======== mem_patch_reg (bwamem.c, bwa >= 0.7.10; restated as recalled): bsw_patch_ref_batch and its ticket forms ========
@@ -416,12 +387,12 @@ static inline bool patch_runs(const bsw_params &pp, int64_t l_pac, const bsw_pta
     return !((rb < l_pac && re > l_pac) || rb < 0 || re > 2 * l_pac);
 }
 
-BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ptask *tasks,
-                          size_t n, bsw_presult *res, const bsw_reads *rd, const bsw_rd_ptask *rtasks)
+/* pp.w is opt->w here, not taken out as for the other two stages; rd / rtasks as for cigar_chunk */
+static int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ptask *tasks,
+                       size_t n, bsw_presult *res, const bsw_reads *rd, const bsw_rd_ptask *rtasks)
 {
     stage_t &st = *L.st;
     hipStream_t s = L.s;
-    hipError_t he;
     const int64_t l_pac = ref->l_pac;
     int rc = stage_records(e, st, n, true);
     if (rc) return rc;
@@ -434,31 +405,19 @@ BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_ptask t = ptask_of(tasks, rd, rtasks, i);
-        bsw_dtask &d = st.h_tasks.p[i];
-        bsw_rawoff &r = st.h_roff.p[i];
-        bsw_refx &x = st.h_desc.p[i];
-        memset(&d, 0, sizeof(d));
-        memset(&r, 0, sizeof(r));
-        x = bsw_refx{0, 0};
         memset(&gt[i], 0, sizeof(bsw_gdtask));
         res[i] = bsw_presult{0, 0, 0, 1};
         int w_ = 0;
-        if (!patch_runs(pp, l_pac, t, &w_)) continue;
+        if (!patch_runs(pp, l_pac, t, &w_)) {
+            clear_records(st, i);
+            continue;
+        }
         const int lq = t.b.qe - t.a.qb, rlen = (int)(t.b.re - t.a.rb);
-        const uint32_t qw = (uint32_t)acc, tw = (uint32_t)(acc + nwords(lq));
-        acc += nwords(lq) + nwords(rlen);
+        rev[i] = t.a.rb >= l_pac;         /* the reverse strand: a left-side-only seed */
         /* where the slice starts: a byte offset into the raw bytes, or (resident reads) the position of base a.qb of its read */
         const uint32_t at = rd ? rd->pos(rtasks[i].read) + (uint32_t)t.a.qb : (uint32_t)sp.bytes;
-        if (t.a.rb >= l_pac) {            /* left side only: read backwards from its last base, target downwards from re - 1 */
-            d.lq_off = qw; d.lt_off = tw; d.lqlen = (uint16_t)lq; d.ltlen = (uint16_t)rlen;
-            r.lq = at + (uint32_t)lq - 1u;
-            x.xl = t.b.re - 1;
-            rev[i] = 1;
-        } else {                          /* right side only: read forwards, target upwards from rb */
-            d.rq_off = qw; d.rt_off = tw; d.rqlen = (uint16_t)lq; d.rtlen = (uint16_t)rlen;
-            r.rq = at;
-            x.xr = t.a.rb;
-        }
+        const interval_words iw = lay_interval(st, i, lq, rlen, rev[i] != 0, at, t.a.rb, t.b.re, acc);
+        const uint32_t qw = iw.qw, tw = iw.tw;
         if (!rd) sp.add(t.query + t.a.qb, (size_t)lq);
         res[i].w = w_;
         res[i].status = 0;                /* (runs: settled below) */
@@ -485,14 +444,12 @@ BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     }, &raw);
     if (rc) return rc;
     const size_t nc = cd.size();
-    if ((he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess || (he = L.g_res->reserve(n + 1)) != hipSuccess ||
-        (nc && ((he = L.c_tasks->reserve(nc + 1)) != hipSuccess || (he = L.c_res->reserve(nc + 1)) != hipSuccess || (he = L.g_cig->reserve(nc + 1)) != hipSuccess)))
-        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    if ((rc = reserve_all(e, "device staging", {{L.b->g_tasks, n + 1}, {L.b->g_order, n + 1}, {L.b->g_res, n + 1},
+                                                {L.b->c_tasks, nc + 1, nc != 0}, {L.b->c_res, nc + 1, nc != 0}, {L.b->g_cig, nc + 1, nc != 0}})) != BSW_OK) return rc;
     /* a slot reads back into pinned memory: the scores | the shortcut's records */
     const size_t in_gt = (nc + 1) * sizeof(bsw_cdtask), in_order = in_gt + (n + 1) * sizeof(bsw_gdtask);
-    if (L.h_back && ((he = L.h_back->reserve(n * sizeof(bsw_gresult) + nc * sizeof(bsw_cresult) + 16)) != hipSuccess ||
-                     (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    if (L.h_back && (rc = reserve_all(e, "pinned staging", {{*L.h_back, n * sizeof(bsw_gresult) + nc * sizeof(bsw_cresult) + 16}, {*L.h_in, in_order + (n + 1) * sizeof(uint32_t)}})) != BSW_OK)
+        return rc;
     std::vector<bsw_gresult> gr(live.empty() ? 0 : n);
     std::vector<bsw_cresult> cr(nc);
     class_lists cl;
@@ -500,18 +457,13 @@ BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &p
     drain_on_failure drain(ctx, s, L.ev);
     if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
     if ((rc = stage_pack(e, L, n, BSW_PACK_REV_LEFT, ref, rd)) != BSW_OK) return rc;
-    if (!live.empty()) {
-        HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, L.dma_src(gt.data(), n * sizeof(bsw_gdtask), in_gt), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(cl.order.data(), live.size() * sizeof(uint32_t), in_order), live.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        L.h2d += n * sizeof(bsw_gdtask) + live.size() * sizeof(uint32_t);
-        if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p, nullptr, nullptr, 0, L.g_res->p, s)) != BSW_OK) return rc;
-    }
+    if (!live.empty() && (rc = upload_launch_global(e, L, cl, dp, gt.data(), n, in_gt, in_order, nullptr, nullptr, 0)) != BSW_OK) return rc;
     if (nc) {
-        HIPCHK(e, hipMemcpyAsync(L.c_tasks->p, L.dma_src(cd.data(), nc * sizeof(bsw_cdtask), 0), nc * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.b->c_tasks.p, L.dma_src(cd.data(), nc * sizeof(bsw_cdtask), 0), nc * sizeof(bsw_cdtask), hipMemcpyHostToDevice, s));
         L.h2d += nc * sizeof(bsw_cdtask);
-        HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.c_tasks->p, (uint32_t)nc, L.g_cig->p, 1, L.g_res->p, nullptr, 0, L.c_res->p, s));
+        HIPCHK(e, bsw::launch_cigar_md(dp, st.d_seq.p, L.b->c_tasks.p, (uint32_t)nc, L.b->g_cig.p, 1, L.b->g_res.p, nullptr, 0, L.b->c_res.p, s));
     }
-    rc = lane_read_back(ctx, e, L, {{gr.data(), L.g_res->p, gr.size() * sizeof(bsw_gresult)}, {cr.data(), L.c_res->p, nc * sizeof(bsw_cresult)}});
+    rc = lane_read_back(ctx, e, L, {{gr.data(), L.b->g_res.p, gr.size() * sizeof(bsw_gresult)}, {cr.data(), L.b->c_res.p, nc * sizeof(bsw_cresult)}});
     if (rc) return rc;
     for (uint32_t i : live) res[i].gscore = gr[i].score;
     for (size_t k = 0; k < nc; ++k) res[cd_of[k]].gscore = cr[k].score;
@@ -575,7 +527,7 @@ static int patch_validate(errs &e, const bsw_params *p, const bsw_ref *ref, cons
 #define PATCH_BATCH_WORK (4ull << 30)                  /* a sub-batch of the synchronous call: as many cells as bsw_cigar_ref_batch's hold backtrack bytes */
 static uint64_t patch_work_switch()                   /* BSW_F4_PATCH_WORK, 0: not set */
 {
-    static const uint64_t v = getenv("BSW_F4_PATCH_WORK") && atof(getenv("BSW_F4_PATCH_WORK")) >= 1.0 ? (uint64_t)atof(getenv("BSW_F4_PATCH_WORK")) : 0;
+    static const uint64_t v = chunk_work_env("BSW_F4_PATCH_WORK", 0);
     return v;
 }
 static uint64_t patch_chunk_work() { return patch_work_switch() ? patch_work_switch() : F4_PATCH_CHUNK_WORK; }
@@ -584,10 +536,7 @@ extern "C" int bsw_patch_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
 {
     if (!ctx) return BSW_E_INVAL;
     errs &e = ctx->err;
-    if (!p || !ref || (!tasks && n) || (!res && n)) return fail(e, BSW_E_INVAL, "bsw_patch_ref_batch: bad argument");
-    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return fail(e, BSW_E_INVAL, "bsw_patch_ref_batch: the reference was uploaded through another context");
-    int rc = busy_check(ctx, "bsw_patch_ref_batch");
+    int rc = ref_entry_check(ctx, "bsw_patch_ref_batch", !p || !ref || (!tasks && n) || (!res && n), ref, false);
     if (rc) return rc;
     bsw_params pp;
     bsw_dparams dp;
@@ -602,7 +551,7 @@ extern "C" int bsw_patch_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_
     caps.work = patch_work_switch() ? patch_work_switch() : PATCH_BATCH_WORK;
     const std::vector<chunk_span> spans = cut_spans(n, [&](size_t i) { return span_cost{0, seqb[i], 0, cells[i], 0, 0}; }, caps);
     for (const chunk_span &c : spans) {
-        rc = patch_chunk(ctx, e, L, pp, dp, ref, tasks + c.base, c.cnt, res + c.base);
+        rc = patch_chunk(ctx, e, L, pp, dp, ref, tasks + c.base, c.cnt, res + c.base, nullptr, nullptr);
         if (rc) return rc;
     }
     return BSW_OK;
@@ -614,17 +563,19 @@ static int patch_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, c
 {
     if (!ctx) return BSW_E_INVAL;
     if (ticket) *ticket = 0;
+    int rc = ref_entry_check(ctx, what, !p || !ref || (!tasks && !rtasks && n) || (!res && n), ref, true);
+    if (rc) return rc;
     errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
-    if (!p || !ref || (!tasks && !rtasks && n) || (!res && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: bad argument", what));
-    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what));
-    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
-    f4_submit f;
-    f.kind = 3;
+    bsw_params pp;
+    bsw_dparams dp;
     std::vector<uint64_t> cells, seqb;
-    int rc = patch_validate(e, p, ref, tasks, rd, rtasks, n, &f.pp, &f.dp, cells, seqb);
+    rc = patch_validate(e, p, ref, tasks, rd, rtasks, n, &pp, &dp, cells, seqb);
     if (rc) return ctx_fail(ctx, e, rc);
-    f.ref = ref; f.ptasks = tasks; f.rd = rd; f.rd_ptasks = rtasks; f.n = n; f.pres = res;
+    f4_submit f;
+    f.name = "patch"; f.rd = rd;
+    f.run = [=](bsw_ctx *cx, errs &ce, f4_lane &L, chunk_span c) {
+        return patch_chunk(cx, ce, L, pp, dp, ref, tasks ? tasks + c.base : nullptr, c.cnt, res + c.base, rd, rd ? rtasks + c.base : nullptr);
+    };
     uint64_t total = 0;
     for (size_t i = 0; i < n; ++i) total += cells[i];
     span_caps caps;
@@ -642,12 +593,5 @@ extern "C" int bsw_patch_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const b
 extern "C" int bsw_patch_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_ptask *tasks,
                                         size_t n, bsw_presult *res, bsw_ticket *ticket)
 {
-    if (!ctx) return BSW_E_INVAL;
-    if (ticket) *ticket = 0;
-    errs e;
-    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_patch_reads_submit: bad argument"));
-    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_patch_reads_submit: the read block was uploaded through another context, or is being freed"));
-    const int rc = patch_submit(ctx, p, ref, nullptr, rd, tasks, n, res, ticket, "bsw_patch_reads_submit");
-    if (rc) reads_release(rd);                       /* no ticket was made */
-    return rc;
+    return reads_submit(ctx, rd, ticket, "bsw_patch_reads_submit", [&] { return patch_submit(ctx, p, ref, nullptr, rd, tasks, n, res, ticket, "bsw_patch_reads_submit"); });
 }

@@ -191,9 +191,7 @@ static void ctx_release(bsw_ctx *ctx)
         if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
         for (auto &pr : ctx->hist) { (void)hipEventDestroy(pr.e0); (void)hipEventDestroy(pr.mid); (void)hipEventDestroy(pr.e1); }
         ctx->small.release();
-        ctx->g_tasks.release(); ctx->g_z.release(); ctx->g_cig.release(); ctx->g_order.release(); ctx->g_res.release();
-        ctx->a_tasks.release(); ctx->a_bl.release(); ctx->a_res.release();
-        ctx->c_tasks.release(); ctx->c_res.release(); ctx->c_md.release();
+        ctx->f4.release();
     }
     delete ctx;
 }

@@ -12,6 +12,24 @@ BSW_LOCAL bool global_force_long()
     return on;
 }
 
+BSW_LOCAL int ref_entry_check(bsw_ctx *ctx, const char *what, bool bad_args, const bsw_ref *ref, bool ticket_form)
+{
+    errs local;
+    errs &e = ticket_form ? local : ctx->err;
+    int rc = BSW_OK;
+    if (bad_args) rc = fail(e, BSW_E_INVAL, "%s: bad argument", what);
+    else if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0]) rc = fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what);
+    else if (!ticket_form) return busy_check(ctx, what);
+    else if (ctx->dead) rc = fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what);
+    return rc && ticket_form ? ctx_fail(ctx, e, rc) : rc;
+}
+
+BSW_LOCAL uint64_t chunk_work_env(const char *name, uint64_t dflt)
+{
+    const char *v = getenv(name);
+    return v && atof(v) >= 1.0 ? (uint64_t)atof(v) : dflt;
+}
+
 BSW_LOCAL int launch_global_lists(errs &e, const class_lists &cl, const bsw_dparams &dp, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *d_order,
                                   uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s)
 {
@@ -32,13 +50,19 @@ BSW_LOCAL int launch_align_lists(errs &e, const class_lists &cl, const align_lon
     return BSW_OK;
 }
 
+BSW_LOCAL int upload_launch_global(errs &e, f4_lane &L, const class_lists &cl, const bsw_dparams &dp, const bsw_gdtask *gt, size_t n, size_t in_gt, size_t in_order,
+                                   uint8_t *z, uint32_t *cigars, int max_cigar)
+{
+    const size_t gtb = n * sizeof(bsw_gdtask), orderb = cl.order.size() * sizeof(uint32_t);
+    HIPCHK(e, hipMemcpyAsync(L.b->g_tasks.p, L.dma_src(gt, gtb, in_gt), gtb, hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.b->g_order.p, L.dma_src(cl.order.data(), orderb, in_order), orderb, hipMemcpyHostToDevice, L.s));
+    L.h2d += gtb + orderb;
+    return launch_global_lists(e, cl, dp, L.st->d_seq.p, L.b->g_tasks.p, L.b->g_order.p, z, cigars, max_cigar, L.b->g_res.p, L.s);
+}
+
 BSW_LOCAL int stage_records(errs &e, stage_t &st, size_t n, bool desc)
 {
-    hipError_t he;
-    if ((he = st.h_tasks.reserve(n + 1)) != hipSuccess || (he = st.h_roff.reserve(n + 1)) != hipSuccess ||
-        (desc && (he = st.h_desc.reserve(n + 1)) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
-    return BSW_OK;
+    return reserve_all(e, "pinned staging", {{st.h_tasks, n + 1}, {st.h_roff, n + 1}, {st.h_desc, n + 1, desc}});
 }
 
 BSW_LOCAL int stage_upload(errs &e, f4_lane &L, const staged_raw &r, size_t n)
@@ -110,7 +134,6 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
 {
     f4_lane L = ctx_lane(ctx);
     stage_t &st = *L.st;
-    hipError_t he;
     int rc = stage_records(e, st, n, false);
     if (rc) return rc;
     std::vector<bsw_gdtask> gt(n);
@@ -131,19 +154,17 @@ static int global_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_
     cl.build(route.classes(), cls.data(), nullptr, n);
     staged_raw raw;
     if ((rc = stage_raw(e, st, n, sp, acc, false, true, 2, [&](size_t i, int k) { return pair_piece(tasks[i], k); }, &raw)) != BSW_OK) return rc;
-    if ((he = L.g_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
-        (he = L.g_res->reserve(n + 1)) != hipSuccess || (cigars && (he = L.g_z->reserve((size_t)zacc + 64)) != hipSuccess) ||
-        (cigars && (he = L.g_cig->reserve(n * (size_t)max_cigar + 1)) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    if ((rc = reserve_all(e, "device staging", {{L.b->g_tasks, n + 1}, {L.b->g_order, n + 1}, {L.b->g_res, n + 1}, {L.b->g_z, (size_t)zacc + 64, cigars != nullptr},
+                                                {L.b->g_cig, n * (size_t)max_cigar + 1, cigars != nullptr}})) != BSW_OK) return rc;
     drain_on_failure drain(ctx, L.s, L.ev);
     if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
-    HIPCHK(e, hipMemcpyAsync(L.g_tasks->p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, L.s));
-    HIPCHK(e, hipMemcpyAsync(L.g_order->p, cl.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.b->g_tasks.p, gt.data(), n * sizeof(bsw_gdtask), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.b->g_order.p, cl.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
     if ((rc = stage_pack(e, L, n, 0, nullptr, nullptr)) != BSW_OK) return rc;
-    if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.g_tasks->p, L.g_order->p, cigars ? L.g_z->p : nullptr, cigars ? L.g_cig->p : nullptr, max_cigar,
-                                  L.g_res->p, L.s)) != BSW_OK) return rc;
+    if ((rc = launch_global_lists(e, cl, dp, st.d_seq.p, L.b->g_tasks.p, L.b->g_order.p, cigars ? L.b->g_z.p : nullptr, cigars ? L.b->g_cig.p : nullptr, max_cigar,
+                                  L.b->g_res.p, L.s)) != BSW_OK) return rc;
     const size_t cigb = cigars ? n * (size_t)max_cigar * sizeof(uint32_t) : 0;
-    if ((rc = lane_read_back(ctx, e, L, {{res, L.g_res->p, n * sizeof(bsw_gresult)}, {cigars, L.g_cig->p, cigb}})) != BSW_OK) return rc;
+    if ((rc = lane_read_back(ctx, e, L, {{res, L.b->g_res.p, n * sizeof(bsw_gresult)}, {cigars, L.b->g_cig.p, cigb}})) != BSW_OK) return rc;
     drain.done();
     return BSW_OK;
 }
@@ -235,7 +256,6 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
 {
     f4_lane L = ctx_lane(ctx);
     stage_t &st = *L.st;
-    hipError_t he;
     int rc = stage_records(e, st, n, false);
     if (rc) return rc;
     std::vector<bsw_adtask> at(n);
@@ -259,16 +279,14 @@ static int align_chunk(bsw_ctx *ctx, errs &e, const bsw_dparams &dp, const bsw_a
     cl.build(nall, cls.data(), nullptr, n);
     staged_raw raw;
     if ((rc = stage_raw(e, st, n, sp, acc, false, true, 2, [&](size_t i, int k) { return pair_piece(tasks[i], k); }, &raw)) != BSW_OK) return rc;
-    if ((he = L.a_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
-        (he = L.a_res->reserve(n + 1)) != hipSuccess || (he = L.a_bl->reserve((size_t)bacc + 64)) != hipSuccess)
-        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    if ((rc = reserve_all(e, "device staging", {{L.b->a_tasks, n + 1}, {L.b->g_order, n + 1}, {L.b->a_res, n + 1}, {L.b->a_bl, (size_t)bacc + 64}})) != BSW_OK) return rc;
     drain_on_failure drain(ctx, L.s, L.ev);
     if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
-    HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, at.data(), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, L.s));
-    HIPCHK(e, hipMemcpyAsync(L.g_order->p, cl.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.b->a_tasks.p, at.data(), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, L.s));
+    HIPCHK(e, hipMemcpyAsync(L.b->g_order.p, cl.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, L.s));
     if ((rc = stage_pack(e, L, n, 0, nullptr, nullptr)) != BSW_OK) return rc;
-    if ((rc = launch_align_lists(e, cl, alo, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p, L.a_bl->p, L.a_res->p, L.s)) != BSW_OK) return rc;
-    if ((rc = lane_read_back(ctx, e, L, {{out, L.a_res->p, n * sizeof(bsw_kswr)}})) != BSW_OK) return rc;
+    if ((rc = launch_align_lists(e, cl, alo, dp, st.d_seq.p, L.b->a_tasks.p, L.b->g_order.p, L.b->a_bl.p, L.b->a_res.p, L.s)) != BSW_OK) return rc;
+    if ((rc = lane_read_back(ctx, e, L, {{out, L.b->a_res.p, n * sizeof(bsw_kswr)}})) != BSW_OK) return rc;
     drain.done();
     return BSW_OK;
 }

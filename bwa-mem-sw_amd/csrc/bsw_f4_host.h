@@ -1,6 +1,8 @@
-/* bsw_f4_host.h — internal: what global_chunk / align_chunk (bsw_f4.hip), cigar_chunk (bsw_cigar.hip) and matesw_chunk
+/* bsw_f4_host.h — internal: what global_chunk / align_chunk (bsw_f4.hip), cigar_chunk / patch_chunk (bsw_cigar.hip) and matesw_chunk
  * (bsw_matesw.hip) share, each written once: the span of the caller's bytes with the direct-DMA test, per-class task lists, kernel
- * routing and launch loops, staging the sequences on a lane, reading a lane back, cutting a call into sub-batches.  Nothing here
+ * routing and launch loops, reservations in a row, a task's layout as a one-sided seed, staging the sequences on a lane, reading a
+ * lane back, cutting a call into sub-batches, and the entry prologue, the read-block wrapper and the work switch of the three
+ * stages against the resident reference.  Nothing here
  * keeps state (but the one getenv of global_force_long): chunks run concurrently on slot threads.  Non-inline bodies: bsw_f4.hip. */
 #ifndef BSW_F4_HOST_H
 #define BSW_F4_HOST_H
@@ -8,6 +10,28 @@
 #include "bsw_internal.h"
 
 #include <initializer_list>
+
+/* ---- what every entry point of the stages against the resident reference (bsw_cigar_ref_*, bsw_matesw_ref_*, bsw_patch_ref_*) does
+ * first, in this order: its own argument test (bad_args, evaluated by the caller: "<what>: bad argument"), the reference belongs to
+ * this context, then busy_check for a synchronous call, or "the context is dead" for a ticket form.  A synchronous call writes the
+ * context's error text directly; a ticket form may run beside others and sets it under the context's lock (ctx_fail). ---- */
+BSW_LOCAL int ref_entry_check(bsw_ctx *ctx, const char *what, bool bad_args, const bsw_ref *ref, bool ticket_form);
+/* a *_reads_submit_t: takes the block, runs the stage's submit() and gives the block back when no ticket was made (the ticket owns
+ * the block only once it exists: BSW_E_BUSY included) */
+template <class F>
+inline int reads_submit(bsw_ctx *ctx, const bsw_reads *rd, bsw_ticket *ticket, const char *what, F submit)
+{
+    if (!ctx) return BSW_E_INVAL;
+    if (ticket) *ticket = 0;
+    errs e;
+    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: bad argument", what));
+    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the read block was uploaded through another context, or is being freed", what));
+    const int rc = submit();
+    if (rc) reads_release(rd);
+    return rc;
+}
+/* a chunk's work target from the environment (BSW_F4_*_WORK: tests, measurements): set and >= 1, else dflt.  The callers cache it. */
+BSW_LOCAL uint64_t chunk_work_env(const char *name, uint64_t dflt);
 
 /* ---- the caller's bytes a chunk references: their span and sum ---- */
 struct raw_span {
@@ -84,16 +108,68 @@ inline int align_byte_mode_check(errs &e, const bsw_params *p, int xtra, const c
     return BSW_OK;
 }
 
+/* ---- growing several buffers in the order given, up to the first that fails: "<what>: <HIP's text>" with BSW_E_NOMEM (what: "device staging"
+ * or "pinned staging").  An entry whose `on` is false is skipped. ---- */
+struct reserve_req {
+    void *buf;
+    size_t need;
+    hipError_t (*grow)(void *, size_t);
+    template <class B>
+    reserve_req(B &b, size_t n, bool on = true) : buf(on ? &b : nullptr), need(n), grow([](void *p, size_t k) { return ((B *)p)->reserve(k); }) {}
+};
+inline int reserve_all(errs &e, const char *what, std::initializer_list<reserve_req> list)
+{
+    for (const reserve_req &r : list) {
+        const hipError_t he = r.buf ? r.grow(r.buf, r.need) : hipSuccess;
+        if (he != hipSuccess) return fail(e, BSW_E_NOMEM, "%s: %s", what, hipGetErrorString(he));
+    }
+    return BSW_OK;
+}
+
 /* ---- one launch per class that holds a task, ascending; d_order: the device copy of cl.order; alo: the LDS-row kernel's classes
  * behind the ncls of bsw_align_kernel ---- */
 BSW_LOCAL int launch_global_lists(errs &e, const class_lists &cl, const bsw_dparams &dp, const uint64_t *seq, const bsw_gdtask *tasks, const uint32_t *d_order,
                                   uint8_t *z, uint32_t *cigars, int max_cigar, bsw_gresult *out, hipStream_t s);
 BSW_LOCAL int launch_align_lists(errs &e, const class_lists &cl, const align_long_ops *alo, const bsw_dparams &dp, const uint64_t *seq, const bsw_adtask *tasks,
                                  const uint32_t *d_order, unsigned long long *blist, bsw_kswr *out, hipStream_t s);
+/* the global kernels on a lane's packed sequences: the host-built records gt[0..n) and cl.order go to the lane's g_tasks / g_order (a slot: through its
+ * pinned h_in, at in_gt / in_order), counted in L.h2d, then launch_global_lists into the lane's g_res.  (global_chunk queues the same copies in front of
+ * its pack launch and keeps that order.) */
+BSW_LOCAL int upload_launch_global(errs &e, f4_lane &L, const class_lists &cl, const bsw_dparams &dp, const bsw_gdtask *gt, size_t n, size_t in_gt, size_t in_order,
+                                   uint8_t *z, uint32_t *cigars, int max_cigar);
 
 /* ---- staging the sequences of a chunk on a lane.  The caller: stage_records, fills h_tasks / h_roff (/ h_desc) with offsets of a gather
  * (raw_span::bytes as it goes), stage_raw, its own reservations, its drain_on_failure, stage_upload, its own records, stage_pack. ---- */
 BSW_LOCAL int stage_records(errs &e, stage_t &st, size_t n, bool desc);
+/* Task i against the resident reference as a one-sided seed of bsw_pack_kernel.  clear_records: a task that does not run.  lay_interval: lq query
+ * bases from `at` (a byte offset into the raw bytes, or the base's position in the resident read store) against the reference interval [rb, re)
+ * of rlen bases.  rev: left side only, the query read backwards from its last base and the target downwards from re - 1 — bwa's reversal of
+ * both, for free; else right side only, the query read forwards and the target upwards from rb.  The sequences' words start at acc, which moves
+ * on; returns where the query's and the target's begin. */
+inline void clear_records(stage_t &st, size_t i)
+{
+    memset(&st.h_tasks.p[i], 0, sizeof(bsw_dtask));
+    memset(&st.h_roff.p[i], 0, sizeof(bsw_rawoff));
+    st.h_desc.p[i] = bsw_refx{0, 0};
+}
+struct interval_words { uint32_t qw, tw; };
+inline interval_words lay_interval(stage_t &st, size_t i, int lq, int rlen, bool rev, uint32_t at, int64_t rb, int64_t re, uint64_t &acc)
+{
+    clear_records(st, i);
+    bsw_dtask &d = st.h_tasks.p[i];
+    const interval_words w{(uint32_t)acc, (uint32_t)(acc + nwords(lq))};
+    acc += nwords(lq) + nwords(rlen);
+    if (rev) {
+        d.lq_off = w.qw; d.lt_off = w.tw; d.lqlen = (uint16_t)lq; d.ltlen = (uint16_t)rlen;
+        st.h_roff.p[i].lq = at + (uint32_t)lq - 1u;
+        st.h_desc.p[i].xl = re - 1;
+    } else {
+        d.rq_off = w.qw; d.rt_off = w.tw; d.rqlen = (uint16_t)lq; d.rtlen = (uint16_t)rlen;
+        st.h_roff.p[i].rq = at;
+        st.h_desc.p[i].xr = rb;
+    }
+    return w;
+}
 /* a task's sequence as the caller holds it: p[0..len), the field of its bsw_rawoff that names it (last: names its LAST byte, read backwards); len == 0: none */
 struct raw_piece { const uint8_t *p; size_t len; uint32_t bsw_rawoff::*at; bool last; };
 struct staged_raw {                   /* what crosses PCIe: the caller's arena from raw_span::lo, or h_raw (resident reads: nothing) */
@@ -106,7 +182,7 @@ struct staged_raw {                   /* what crosses PCIe: the caller's arena f
 template <class F>
 inline int stage_raw(errs &e, stage_t &st, size_t n, const raw_span &sp, uint64_t words, bool desc, bool gather_empty, int pieces, F piece, staged_raw *out)
 {
-    hipError_t he;
+    int rc;
     const bool direct = sp.direct(RAW_SLACK);
     if (direct) {
         for (size_t i = 0; i < n; ++i)
@@ -115,7 +191,7 @@ inline int stage_raw(errs &e, stage_t &st, size_t n, const raw_span &sp, uint64_
                 st.h_roff.p[i].*pc.at = pc.len ? (uint32_t)(pc.p - sp.lo) + (pc.last ? (uint32_t)pc.len - 1u : 0u) : 0u;
             }
     } else if (gather_empty || sp.bytes) {
-        if ((he = st.h_raw.reserve((size_t)sp.bytes + RAW_SLACK)) != hipSuccess) return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+        if ((rc = reserve_all(e, "pinned staging", {{st.h_raw, (size_t)sp.bytes + RAW_SLACK}})) != BSW_OK) return rc;
         for (size_t i = 0; i < n; ++i)
             for (int k = 0; k < pieces; ++k) {
                 const raw_piece pc = piece(i, k);
@@ -125,11 +201,8 @@ inline int stage_raw(errs &e, stage_t &st, size_t n, const raw_span &sp, uint64_
     out->bytes = direct ? sp.span() : (size_t)sp.bytes;
     out->src = direct ? sp.lo : st.h_raw.p;
     out->desc = desc;
-    if ((he = st.d_raw.reserve(out->bytes + RAW_FRONT + RAW_SLACK)) != hipSuccess || (he = st.d_seq.reserve((size_t)words + 4)) != hipSuccess ||
-        (he = st.d_tasks.reserve(n + 1)) != hipSuccess || (he = st.d_roff.reserve(n + 1)) != hipSuccess ||
-        (desc && (he = st.d_desc.reserve(n + 1)) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
-    return BSW_OK;
+    return reserve_all(e, "device staging", {{st.d_raw, out->bytes + RAW_FRONT + RAW_SLACK}, {st.d_seq, (size_t)words + 4}, {st.d_tasks, n + 1}, {st.d_roff, n + 1},
+                                             {st.d_desc, n + 1, desc}});
 }
 /* queues the raw bytes (behind RAW_FRONT), the task records, the offsets and the reference positions; counts them in L.h2d */
 BSW_LOCAL int stage_upload(errs &e, f4_lane &L, const staged_raw &r, size_t n);

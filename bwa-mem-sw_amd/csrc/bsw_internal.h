@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -252,18 +253,18 @@ struct fork_t {
     bool ok = false;
 };
 
-/* Device scratch of the CIGAR and mate-rescue hosts beside a stage_t.  The context owns one set (its members g_* / a_* / c_*,
- * shared with bsw_global_batch / bsw_align_batch); every pipeline slot owns one of these, reserved on the slot's device by the
- * first CIGAR or rescue chunk it runs, released by bsw_destroy. */
+/* Device scratch of the global, alignment, CIGAR, mate-rescue and patch hosts beside a stage_t.  The context owns one (bsw_ctx::f4,
+ * for its synchronous calls; its h_back and h_in are never reserved); every pipeline slot owns one, reserved on the slot's device
+ * by the first CIGAR, rescue or patch chunk it runs.  bsw_destroy releases them. */
 struct f4_bufs {
-    dbuf<bsw_gdtask> g_tasks;
+    dbuf<bsw_gdtask> g_tasks;         /* banded global alignment */
     dbuf<uint8_t> g_z;
     dbuf<uint32_t> g_cig, g_order;
     dbuf<bsw_gresult> g_res;
-    dbuf<bsw_adtask> a_tasks;
+    dbuf<bsw_adtask> a_tasks;         /* local alignment */
     dbuf<unsigned long long> a_bl;
     dbuf<bsw_kswr> a_res;
-    dbuf<bsw_cdtask> c_tasks;
+    dbuf<bsw_cdtask> c_tasks;         /* bwa_gen_cigar2's NM / MD pass */
     dbuf<bsw_cresult> c_res;
     dbuf<char> c_md;
     hbuf<uint8_t> h_back;             /* pinned: what a slot's chunk reads back (scores per try, then results, CIGARs, MD) */
@@ -332,17 +333,7 @@ struct bsw_ctx {
     std::atomic<int> uploads{0};      /* bsw_reads_upload_start: uploads in flight (at most BSW_READS_MAX_UPLOADS) */
     /* small synchronous batches (bsw_extend_batch, scalar ABI, wire format) */
     stage_t small;
-    /* banded global alignment (F4) */
-    dbuf<bsw_gdtask> g_tasks;
-    dbuf<uint8_t> g_z;
-    dbuf<uint32_t> g_cig, g_order;
-    dbuf<bsw_gresult> g_res;
-    dbuf<bsw_adtask> a_tasks;         /* local alignment (bsw_align_batch) */
-    dbuf<unsigned long long> a_bl;
-    dbuf<bsw_kswr> a_res;
-    dbuf<bsw_cdtask> c_tasks;         /* bwa_gen_cigar2 on the resident reference (bsw_cigar_ref_batch) */
-    dbuf<bsw_cresult> c_res;
-    dbuf<char> c_md;
+    f4_bufs f4;                       /* scratch of the synchronous F4 and resident-reference calls (ctx_lane) */
     std::vector<refbatch_req> ref_queue;
     int device0() const { return devs[0].device; }
     hipStream_t stream0() const { return devs[0].streams[0]; }
@@ -411,23 +402,15 @@ inline int reads_order(errs &e, const bsw_reads *rd, size_t d, hipStream_t s)
 }
 
 /* Where one chunk of bsw_cigar_ref_* / bsw_matesw_ref_* runs: the device (index into bsw_config.devices[], and so into
- * bsw_ref::d_pac), the staging, the stream, the watchdog event and the scratch buffers.  The synchronous calls pass the context's
- * own lane (ctx_lane); every pipeline slot has one over its own stage_t, stream and f4_bufs. */
+ * bsw_ref::d_pac), the staging, the stream, the watchdog event and the scratch buffers `b`.  The synchronous calls pass the context's
+ * own lane (ctx_lane: h_back and h_in are NULL); every pipeline slot has one over its own stage_t, stream and f4_bufs, with h_back and
+ * h_in pointing into that f4_bufs. */
 struct f4_lane {
     size_t dev = 0;
     stage_t *st = nullptr;
     hipStream_t s = nullptr;
     hipEvent_t ev = nullptr;
-    dbuf<bsw_gdtask> *g_tasks = nullptr;
-    dbuf<uint8_t> *g_z = nullptr;
-    dbuf<uint32_t> *g_cig = nullptr, *g_order = nullptr;
-    dbuf<bsw_gresult> *g_res = nullptr;
-    dbuf<bsw_adtask> *a_tasks = nullptr;
-    dbuf<unsigned long long> *a_bl = nullptr;
-    dbuf<bsw_kswr> *a_res = nullptr;
-    dbuf<bsw_cdtask> *c_tasks = nullptr;
-    dbuf<bsw_cresult> *c_res = nullptr;
-    dbuf<char> *c_md = nullptr;
+    f4_bufs *b = nullptr;
     hbuf<uint8_t> *h_back = nullptr;  /* non-NULL (a slot): read-backs are asynchronous copies on `s` into this pinned buffer, in front
                                          of the sync_stream that carries the watchdog; NULL: the blocking copies of the synchronous calls */
     hbuf<uint8_t> *h_in = nullptr;    /* with h_back: the host-built records are DMA'd from this pinned buffer */
@@ -442,20 +425,11 @@ struct f4_lane {
     uint64_t h2d = 0, d2h = 0;        /* bytes the chunk moved (bsw_host_stats) */
     std::atomic<uint64_t> *h2d_total = nullptr;   /* a slot: the pipeline's H2D counter, for a job that must have its bytes counted BEFORE it reports
                                                      (a piece of an upload: the block is ready once the last piece has reported) */
-    void bind(f4_bufs &b)
-    {
-        g_tasks = &b.g_tasks; g_z = &b.g_z; g_cig = &b.g_cig; g_order = &b.g_order; g_res = &b.g_res;
-        a_tasks = &b.a_tasks; a_bl = &b.a_bl; a_res = &b.a_res;
-        c_tasks = &b.c_tasks; c_res = &b.c_res; c_md = &b.c_md;
-    }
 };
 inline f4_lane ctx_lane(bsw_ctx *ctx)
 {
     f4_lane L;
-    L.dev = 0; L.st = &ctx->small; L.s = ctx->stream0(); L.ev = ctx->devs[0].events[0];
-    L.g_tasks = &ctx->g_tasks; L.g_z = &ctx->g_z; L.g_cig = &ctx->g_cig; L.g_order = &ctx->g_order; L.g_res = &ctx->g_res;
-    L.a_tasks = &ctx->a_tasks; L.a_bl = &ctx->a_bl; L.a_res = &ctx->a_res;
-    L.c_tasks = &ctx->c_tasks; L.c_res = &ctx->c_res; L.c_md = &ctx->c_md;
+    L.dev = 0; L.st = &ctx->small; L.s = ctx->stream0(); L.ev = ctx->devs[0].events[0]; L.b = &ctx->f4;
     return L;
 }
 
@@ -464,29 +438,16 @@ struct chunk_span {
     size_t base, cnt;
 };
 
-/* A ticketed CIGAR (kind 1), mate-rescue (kind 2) or region-patch (kind 3) submit as its entry point hands it to the pipeline: validated, the band
- * taken out of the parameters, cut into chunks.  The caller's arrays stay the caller's until the ticket is collected. */
+/* A ticketed CIGAR, mate-rescue or region-patch submit as its entry point hands it to the pipeline: validated and cut into chunks.
+ * What a chunk does is the entry point's own business: `run` is a closure over the validated parameters (the band taken out where
+ * the stage does that), the caller's arrays and the submit's snapshot of bsw_align_long(), all by value; it applies the span's base
+ * to those arrays itself and runs the stage's chunk function on the slot's lane.  The caller's arrays stay the caller's until the
+ * ticket is collected.  (One indirect call per chunk, and a chunk holds thousands of alignments: it is nowhere near a hot path.) */
 struct f4_submit {
-    int kind = 0;
-    bsw_params pp{};
-    bsw_dparams dp{};
-    const bsw_ref *ref = nullptr;
-    const bsw_ctask *ctasks = nullptr;
-    const bsw_mtask *mtasks = nullptr;
-    const bsw_ptask *ptasks = nullptr;
-    const bsw_reads *rd = nullptr;    /* non-NULL: the tasks name reads of this resident block (rd_ctasks / rd_mtasks / rd_ptasks instead of the three above) */
-    const bsw_rd_ctask *rd_ctasks = nullptr;
-    const bsw_rd_mtask *rd_mtasks = nullptr;
-    const bsw_rd_ptask *rd_ptasks = nullptr;
-    size_t n = 0;
-    int max_cigar = 0, max_md = 0;
-    uint32_t *cigars = nullptr;
-    char *md = nullptr;
-    bsw_cresult *cres = nullptr;
-    bsw_mresult *mres = nullptr;
-    bsw_presult *pres = nullptr;
+    const char *name = "";            /* "cigar", "matesw" or "patch": the BSW_DEBUG_TIMING line */
+    const bsw_reads *rd = nullptr;    /* non-NULL: the resident block the tasks name, acquired by the entry point; the ticket gives it back */
     std::vector<chunk_span> spans;    /* chunk k -> device k mod n_devices */
-    int al_mode = 0;                  /* mate rescue: bsw_align_long() as the submit found it; the chunks route by this, never by the switch */
+    std::function<int(bsw_ctx *, errs &, f4_lane &, chunk_span)> run;
 };
 /* the work one chunk of a submit should hold: the kind's target (a launch of that much fills the machine), less for a submit
  * that would otherwise leave slots of the context without a chunk, never below an eighth of the target */
@@ -503,21 +464,9 @@ BSW_LOCAL int pipeline_submit_f4(bsw_ctx *ctx, f4_submit &&f, bsw_ticket *ticket
  * fn waits for nothing but its own work, reports through arg and adds its bytes to *lane.h2d_total (bsw_host_stats). ---- */
 typedef void (*slot_job_fn)(bsw_ctx *ctx, f4_lane &lane, void *arg, size_t piece);
 BSW_LOCAL int pipeline_submit_job(bsw_ctx *ctx, slot_job_fn fn, void *arg, size_t pieces);
-/* ---- bsw_cigar.hip / bsw_matesw.hip: one chunk on a lane ---- */
-/* rd != NULL: the chunk's tasks are rtasks[0..n) and name reads of the resident block (tasks is NULL then): the per-task work is
- * the device records plus a base position — no span, no registration test, no gather, no raw bytes */
-BSW_LOCAL int cigar_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ctask *tasks,
-                          size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md, bsw_cresult *res,
-                          const bsw_reads *rd = nullptr, const bsw_rd_ctask *rtasks = nullptr);
-BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                           bsw_mresult *res, const bsw_reads *rd = nullptr, const bsw_rd_mtask *rtasks = nullptr, int al_mode = 0);
-/* mem_patch_reg (kind 3): pp.w is opt->w here, not taken out as for the other two */
-BSW_LOCAL int patch_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_params &pp, const bsw_dparams &dp, const bsw_ref *ref, const bsw_ptask *tasks,
-                          size_t n, bsw_presult *res, const bsw_reads *rd = nullptr, const bsw_rd_ptask *rtasks = nullptr);
-
 /* ---- bsw_f4.hip: the long-query route of ksw_align2 (bsw_set_align_long).  bsw_align_long.hip, the unit that owns the switch and
  * names the launcher of bsw_align_long_kernel.hip, registers this table when the library is loaded; a program linked without that
- * unit keeps the NULL pointer, which means "mode 0 only".  The hosts (align_chunk, matesw_chunk) read the mode ONCE per call or
+ * unit keeps the NULL pointer, which means "mode 0 only".  The hosts (align_chunk, bsw_matesw.hip's chunks) read the mode ONCE per call or
  * submit, in the caller's thread, and route by that snapshot: a task of more than BSW_ALIGN_MAX_QLEN bases that passed the check goes
  * to `launch` whatever the switch says by the time its chunk runs. ---- */
 struct align_long_ops {

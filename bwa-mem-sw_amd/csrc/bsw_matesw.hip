@@ -33,12 +33,12 @@ static inline bsw_mtask mtask_of(const bsw_mtask *tasks, const bsw_reads *rd, co
     return t;
 }
 
-BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
-                           bsw_mresult *res, const bsw_reads *rd, const bsw_rd_mtask *rtasks, int al_mode)
+/* rd != NULL: the chunk's tasks are rtasks[0..n) and name mates of the resident block (tasks is NULL then) */
+static int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams &dp, const bsw_ref *ref, const bsw_mtask *tasks, size_t n,
+                        bsw_mresult *res, const bsw_reads *rd, const bsw_rd_mtask *rtasks, int al_mode)
 {
     stage_t &st = *L.st;
     hipStream_t s = L.s;
-    hipError_t he;
     const int64_t l_pac = ref->l_pac;
     int rc = stage_records(e, st, n, true);
     if (rc) return rc;
@@ -53,23 +53,17 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
     raw_span sp;
     for (size_t i = 0; i < n; ++i) {
         const bsw_mtask t = mtask_of(tasks, rd, rtasks, i);
-        bsw_dtask &d = st.h_tasks.p[i];
-        bsw_rawoff &r = st.h_roff.p[i];
-        bsw_refx &x = st.h_desc.p[i];
-        memset(&d, 0, sizeof(d));
-        memset(&r, 0, sizeof(r));
-        x = bsw_refx{0, 0};
         runs[i] = mtask_runs(t, l_pac) ? 1 : 0;
-        if (!runs[i]) continue;
+        if (!runs[i]) {
+            clear_records(st, i);
+            continue;
+        }
         const int tlen = (int)(t.re - t.rb);
-        d.rq_off = (uint32_t)acc; acc += nwords(t.l_ms);
-        d.rt_off = (uint32_t)acc; acc += nwords(tlen);
-        d.rqlen = (uint16_t)t.l_ms; d.rtlen = (uint16_t)tlen;
-        x.xr = t.rb;
-        if (rd) r.rq = rd->pos(rtasks[i].read);      /* the mate's first base in the store: read forwards */
-        else { r.rq = (uint32_t)sp.bytes; sp.add(t.mate, (size_t)t.l_ms); }
+        /* the forward layout on both strands; the mate starts at its first base in the store, or at the next byte of the raw bytes */
+        const interval_words iw = lay_interval(st, i, t.l_ms, tlen, false, rd ? rd->pos(rtasks[i].read) : (uint32_t)sp.bytes, t.rb, t.re, acc);
+        if (!rd) sp.add(t.mate, (size_t)t.l_ms);
         bsw_adtask &a = at[i];
-        a.q_off = d.rq_off; a.t_off = d.rt_off; a.qlen = t.l_ms; a.tlen = tlen; a.xtra = t.xtra;
+        a.q_off = iw.qw; a.t_off = iw.tw; a.qlen = t.l_ms; a.tlen = tlen; a.xtra = t.xtra;
         a.pad = t.is_rev ? BSW_AD_QRC : 0u;
         a.b_off = bacc;
         if (t.xtra & KSW_XSUBO) bacc += (uint64_t)tlen;
@@ -84,23 +78,20 @@ BSW_LOCAL int matesw_chunk(bsw_ctx *ctx, errs &e, f4_lane &L, const bsw_dparams 
         return raw_piece{runs[i] ? tasks[i].mate : nullptr, runs[i] ? (size_t)tasks[i].l_ms : 0, &bsw_rawoff::rq, false};
     }, &raw);
     if (rc) return rc;
-    if ((he = L.a_tasks->reserve(n + 1)) != hipSuccess || (he = L.g_order->reserve(n + 1)) != hipSuccess ||
-        (he = L.a_res->reserve(n + 1)) != hipSuccess || (he = L.a_bl->reserve((size_t)bacc + 64)) != hipSuccess)
-        return fail(e, BSW_E_NOMEM, "device staging: %s", hipGetErrorString(he));
+    if ((rc = reserve_all(e, "device staging", {{L.b->a_tasks, n + 1}, {L.b->g_order, n + 1}, {L.b->a_res, n + 1}, {L.b->a_bl, (size_t)bacc + 64}})) != BSW_OK) return rc;
     const size_t in_order = (n + 1) * sizeof(bsw_adtask);
-    if (L.h_back && ((he = L.h_back->reserve(n * sizeof(bsw_kswr) + 16)) != hipSuccess || (he = L.h_in->reserve(in_order + (n + 1) * sizeof(uint32_t))) != hipSuccess))
-        return fail(e, BSW_E_NOMEM, "pinned staging: %s", hipGetErrorString(he));
+    if (L.h_back && (rc = reserve_all(e, "pinned staging", {{*L.h_back, n * sizeof(bsw_kswr) + 16}, {*L.h_in, in_order + (n + 1) * sizeof(uint32_t)}})) != BSW_OK) return rc;
     std::vector<bsw_kswr> aln(L.h_back ? 0 : n);
     const bsw_kswr *alnp = L.h_back ? (const bsw_kswr *)L.h_back->p : aln.data();      /* a slot reads back into pinned memory */
     drain_on_failure drain(ctx, s, L.ev);
     if (!cl.order.empty()) {
         if ((rc = stage_upload(e, L, raw, n)) != BSW_OK) return rc;
-        HIPCHK(e, hipMemcpyAsync(L.a_tasks->p, L.dma_src(at.data(), n * sizeof(bsw_adtask), 0), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(L.g_order->p, L.dma_src(cl.order.data(), cl.order.size() * sizeof(uint32_t), in_order), cl.order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.b->a_tasks.p, L.dma_src(at.data(), n * sizeof(bsw_adtask), 0), n * sizeof(bsw_adtask), hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(L.b->g_order.p, L.dma_src(cl.order.data(), cl.order.size() * sizeof(uint32_t), in_order), cl.order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         L.h2d += n * sizeof(bsw_adtask) + cl.order.size() * sizeof(uint32_t);
         if ((rc = stage_pack(e, L, n, 0, ref, rd)) != BSW_OK) return rc;
-        if ((rc = launch_align_lists(e, cl, alo, dp, st.d_seq.p, L.a_tasks->p, L.g_order->p, L.a_bl->p, L.a_res->p, s)) != BSW_OK) return rc;
-        if ((rc = lane_read_back(ctx, e, L, {{L.h_back ? nullptr : aln.data(), L.a_res->p, n * sizeof(bsw_kswr)}})) != BSW_OK) return rc;
+        if ((rc = launch_align_lists(e, cl, alo, dp, st.d_seq.p, L.b->a_tasks.p, L.b->g_order.p, L.b->a_bl.p, L.b->a_res.p, s)) != BSW_OK) return rc;
+        if ((rc = lane_read_back(ctx, e, L, {{L.h_back ? nullptr : aln.data(), L.b->a_res.p, n * sizeof(bsw_kswr)}})) != BSW_OK) return rc;
     }
     /* mem_matesw: if (aln.score >= opt->min_seed_len && aln.qb >= 0) { b.qb = is_rev? l_ms - (aln.qe + 1) : aln.qb; ... } */
     for (size_t i = 0; i < n; ++i) {
@@ -172,10 +163,7 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
 {
     if (!ctx) return BSW_E_INVAL;
     errs &e = ctx->err;
-    if (!p || !ref || (!tasks && n) || (!res && n)) return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: NULL argument");
-    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return fail(e, BSW_E_INVAL, "bsw_matesw_ref_batch: the reference was uploaded through another context");
-    int rc = busy_check(ctx, "bsw_matesw_ref_batch");
+    int rc = ref_entry_check(ctx, "bsw_matesw_ref_batch", !p || !ref || (!tasks && n) || (!res && n), ref, false);
     if (rc) return rc;
     bsw_dparams dp;
     const int al_mode = align_long_snapshot();        /* the switch as this call finds it */
@@ -199,7 +187,7 @@ extern "C" int bsw_matesw_ref_batch(bsw_ctx *ctx, const bsw_params *p, const bsw
 #define F4_MATESW_CHUNK_WORK (1ull << 31)
 static uint64_t matesw_chunk_work()
 {
-    static const uint64_t v = getenv("BSW_F4_MATESW_WORK") && atof(getenv("BSW_F4_MATESW_WORK")) >= 1.0 ? (uint64_t)atof(getenv("BSW_F4_MATESW_WORK")) : F4_MATESW_CHUNK_WORK;
+    static const uint64_t v = chunk_work_env("BSW_F4_MATESW_WORK", F4_MATESW_CHUNK_WORK);
     return v;
 }
 
@@ -212,17 +200,18 @@ static int matesw_submit(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, 
 {
     if (!ctx) return BSW_E_INVAL;
     if (ticket) *ticket = 0;
+    int rc = ref_entry_check(ctx, what, !p || !ref || (!tasks && !rtasks && n) || (!res && n), ref, true);
+    if (rc) return rc;
     errs e;                                          /* (several threads may submit at once: the context's text is set under its lock) */
-    if (!p || !ref || (!tasks && !rtasks && n) || (!res && n)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: NULL argument", what));
-    if (ref->d_pac.size() != ctx->devs.size() || !ref->d_pac[0])
-        return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "%s: the reference was uploaded through another context", what));
-    if (ctx->dead) return ctx_fail(ctx, e, fail(e, BSW_E_HIP, "%s: context is dead (an earlier wait for the GPU timed out)", what));
-    f4_submit f;
-    f.kind = 2; f.pp = *p; f.pp.w = 0; f.pp.variant = BSW_VARIANT_H;
-    f.al_mode = align_long_snapshot();               /* in the submitting thread; the chunks run later on slot threads */
-    int rc = matesw_validate(e, p, tasks, n, what, &f.dp, f.al_mode, rd, rtasks);
+    bsw_dparams dp;
+    const int al_mode = align_long_snapshot();        /* in the submitting thread; the chunks run later on slot threads and route by this, never by the switch */
+    rc = matesw_validate(e, p, tasks, n, what, &dp, al_mode, rd, rtasks);
     if (rc) return ctx_fail(ctx, e, rc);
-    f.ref = ref; f.mtasks = tasks; f.rd = rd; f.rd_mtasks = rtasks; f.n = n; f.mres = res;
+    f4_submit f;
+    f.name = "matesw"; f.rd = rd;
+    f.run = [=](bsw_ctx *cx, errs &ce, f4_lane &L, chunk_span c) {
+        return matesw_chunk(cx, ce, L, dp, ref, tasks ? tasks + c.base : nullptr, c.cnt, res + c.base, rd, rd ? rtasks + c.base : nullptr, al_mode);
+    };
     uint64_t total = 0;
     for (size_t i = 0; i < n; ++i) total += mtask_cost(mtask_of(tasks, rd, rtasks, i)).work;
     span_caps caps;                                   /* the batch call's bounds, and the work of a chunk */
@@ -242,12 +231,5 @@ extern "C" int bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const 
 extern "C" int bsw_matesw_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd, const bsw_rd_mtask *tasks,
                                          size_t n, bsw_mresult *res, bsw_ticket *ticket)
 {
-    if (!ctx) return BSW_E_INVAL;
-    if (ticket) *ticket = 0;
-    errs e;
-    if (!rd) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_reads_submit: NULL argument"));
-    if (!reads_acquire(ctx, rd)) return ctx_fail(ctx, e, fail(e, BSW_E_INVAL, "bsw_matesw_reads_submit: the read block was uploaded through another context, or is being freed"));
-    const int rc = matesw_submit(ctx, p, ref, nullptr, rd, tasks, n, res, ticket, "bsw_matesw_reads_submit");
-    if (rc) reads_release(rd);                       /* no ticket was made */
-    return rc;
+    return reads_submit(ctx, rd, ticket, "bsw_matesw_reads_submit", [&] { return matesw_submit(ctx, p, ref, nullptr, rd, tasks, n, res, ticket, "bsw_matesw_reads_submit"); });
 }

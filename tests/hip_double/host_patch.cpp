@@ -1,11 +1,12 @@
-/* host_patch.cpp — bsw_patch_ref_batch, bsw_patch_ref_submit_t and bsw_patch_reads_submit_t (mem_patch_reg: bsw_cigar.hip and
- * kind 3 of bsw_batch.hip's pipeline) on the host-memory HIP stand-in, plain and under ASan / UBSan or TSan (TEST INFRASTRUCTURE;
+/* host_patch.cpp — bsw_patch_ref_batch, bsw_patch_ref_submit_t and bsw_patch_reads_submit_t (mem_patch_reg: bsw_cigar.hip, its
+ * tickets through bsw_batch.hip's pipeline) on the host-memory HIP stand-in, plain and under ASan / UBSan or TSan (TEST INFRASTRUCTURE;
  * tests/test_patch_double_cpu.py builds it with tests/_patch_double_build.py and runs it).  A stand-alone program: nothing is
  * preloaded, no GPU is opened.
  *
  *   host_patch parity   the batch call and both ticket forms on 1, 2 and 3 devices, registered and pageable reads, against the C
  *                       oracle's ksw_global2 for the score and a C restatement of mem_patch_reg's arithmetic around it
- *   host_patch checks   every validation code; nothing is queued by a rejected call
+ *   host_patch checks   every validation code; nothing is queued by a rejected call; the argument, reference and BSW_E_BUSY
+ *                       answers of all nine entry points of the CIGAR, mate-rescue and patch stages
  *   host_patch cuts     (under BSW_F4_PATCH_WORK) the batch call's sub-batches and the tickets' chunks
  *   host_patch mixed    a patch ticket in flight beside an extension and a CIGAR ticket; the fifth submit is BUSY; bsw_reads_free
  *                       is BUSY until the reads ticket is collected
@@ -291,6 +292,82 @@ static int parity_mode()
     return 0;
 }
 
+/* ---- what the nine entry points of the three stages against the resident reference (CIGAR, mate rescue, region patch; each as a
+ * batch call, a ticket and a ticket by read index) share in front of their own checks: a NULL p, a NULL result array with n > 0
+ * and a reference of another context answer BSW_E_INVAL, write no ticket and queue nothing; with BSW_MAX_INFLIGHT tickets
+ * uncollected every ticket form answers BSW_E_BUSY, and one by read index gives its block back.  Task `good` of w runs. ---- */
+static void nine_entry_points(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, bsw_ref *oref, bsw_reads *rd, const pwork &w, size_t good)
+{
+    const bsw_ptask &pt = w.t[good];
+    bsw_ctask ct;
+    memset(&ct, 0, sizeof(ct));
+    ct.query = pt.query + pt.a.qb; ct.l_query = pt.b.qe - pt.a.qb; ct.w = w.want[good].w; ct.rb = pt.a.rb; ct.re = pt.b.re; ct.min_score = INT_MIN; ct.max_tries = 1;
+    bsw_rd_ctask rct;
+    memset(&rct, 0, sizeof(rct));
+    rct.read = (uint32_t)good; rct.qb = pt.a.qb; rct.qe = pt.b.qe; rct.w = ct.w; rct.rb = ct.rb; rct.re = ct.re; rct.min_score = INT_MIN; rct.max_tries = 1;
+    bsw_mtask mt;
+    memset(&mt, 0, sizeof(mt));
+    mt.mate = pt.query; mt.l_ms = pt.l_query; mt.rb = pt.a.rb; mt.re = pt.b.re; mt.xtra = KSW_XSTART | 10; mt.min_score = 19;
+    bsw_rd_mtask rmt;
+    memset(&rmt, 0, sizeof(rmt));
+    rmt.read = (uint32_t)good; rmt.rb = mt.rb; rmt.re = mt.re; rmt.xtra = mt.xtra; rmt.min_score = mt.min_score;
+    const bsw_rd_ptask &rpt = w.rt[good];
+    bsw_cresult cres[1];
+    bsw_mresult mres[1];
+    bsw_presult pres[1];
+    uint32_t cig[64];
+    /* one task through an entry point: pp and rf as given, no result array when !res; tk == NULL for the batch calls */
+    struct entry {
+        const char *name;
+        bool ticket, reads;
+        std::function<int(const bsw_params *, const bsw_ref *, bool, bsw_ticket *)> call;
+    };
+    const entry entries[9] = {
+        {"bsw_cigar_ref_batch", false, false, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *) { return bsw_cigar_ref_batch(ctx, pp, rf, &ct, 1, 64, cig, 0, nullptr, res ? cres : nullptr); }},
+        {"bsw_cigar_ref_submit_t", true, false, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *tk) { return bsw_cigar_ref_submit_t(ctx, pp, rf, &ct, 1, 64, cig, 0, nullptr, res ? cres : nullptr, tk); }},
+        {"bsw_cigar_reads_submit_t", true, true, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *tk) { return bsw_cigar_reads_submit_t(ctx, pp, rf, rd, &rct, 1, 64, cig, 0, nullptr, res ? cres : nullptr, tk); }},
+        {"bsw_matesw_ref_batch", false, false, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *) { return bsw_matesw_ref_batch(ctx, pp, rf, &mt, 1, res ? mres : nullptr); }},
+        {"bsw_matesw_ref_submit_t", true, false, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *tk) { return bsw_matesw_ref_submit_t(ctx, pp, rf, &mt, 1, res ? mres : nullptr, tk); }},
+        {"bsw_matesw_reads_submit_t", true, true, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *tk) { return bsw_matesw_reads_submit_t(ctx, pp, rf, rd, &rmt, 1, res ? mres : nullptr, tk); }},
+        {"bsw_patch_ref_batch", false, false, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *) { return bsw_patch_ref_batch(ctx, pp, rf, &pt, 1, res ? pres : nullptr); }},
+        {"bsw_patch_ref_submit_t", true, false, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *tk) { return bsw_patch_ref_submit_t(ctx, pp, rf, &pt, 1, res ? pres : nullptr, tk); }},
+        {"bsw_patch_reads_submit_t", true, true, [&](const bsw_params *pp, const bsw_ref *rf, bool res, bsw_ticket *tk) { return bsw_patch_reads_submit_t(ctx, pp, rf, rd, &rpt, 1, res ? pres : nullptr, tk); }},
+    };
+    const uint64_t submits0 = stats_of(ctx).submits;
+    for (const entry &en : entries) {
+        const struct { const char *what; const bsw_params *pp; const bsw_ref *rf; bool res; } bad[3] = {
+            {"a NULL p", nullptr, ref, true}, {"a NULL result array", &p, ref, false}, {"the reference of another context", &p, oref, true}};
+        for (const auto &b : bad) {
+            const uint64_t calls = hipdbl::overall_calls();
+            bsw_ticket tk = 77;
+            const int rc = en.call(b.pp, b.rf, b.res, &tk);
+            CHECK(rc == BSW_E_INVAL, "%s with %s -> %d (%s)", en.name, b.what, rc, bsw_last_error(ctx));
+            CHECK(*bsw_last_error(ctx), "%s with %s: no text", en.name, b.what);
+            CHECK(!en.ticket || tk == 0, "%s with %s wrote ticket %llu", en.name, b.what, (unsigned long long)tk);
+            CHECK(bsw_inflight(ctx) == 0 && hipdbl::overall_calls() == calls, "%s with %s queued something", en.name, b.what);
+        }
+    }
+    /* BSW_MAX_INFLIGHT tickets live (complete or not: uncollected), none of them by read index */
+    std::vector<bsw_presult> lo = fresh_out(BSW_MAX_INFLIGHT);
+    bsw_ticket lt[BSW_MAX_INFLIGHT];
+    for (int k = 0; k < BSW_MAX_INFLIGHT; ++k)
+        CHECK(bsw_patch_ref_submit_t(ctx, &p, ref, &pt, 1, &lo[(size_t)k], &lt[k]) == BSW_OK && lt[k], "live ticket %d: %s", k, bsw_last_error(ctx));
+    CHECK(bsw_inflight(ctx) == BSW_MAX_INFLIGHT, "%d tickets live", bsw_inflight(ctx));
+    for (const entry &en : entries) {
+        bsw_ticket tk = 77;
+        const int rc = en.call(&p, ref, true, &tk);
+        CHECK(rc == BSW_E_BUSY, "%s beside %d live tickets -> %d (%s)", en.name, BSW_MAX_INFLIGHT, rc, bsw_last_error(ctx));
+        CHECK(!en.ticket || tk == 0, "%s answered BSW_E_BUSY and wrote ticket %llu", en.name, (unsigned long long)tk);
+        CHECK(bsw_inflight(ctx) == BSW_MAX_INFLIGHT && stats_of(ctx).submits == submits0 + BSW_MAX_INFLIGHT, "%s: BSW_E_BUSY changed something", en.name);
+    }
+    for (int k = 0; k < BSW_MAX_INFLIGHT; ++k) {
+        CHECK(bsw_wait_ticket(ctx, lt[k]) == BSW_OK, "live ticket %d: %s", k, bsw_last_error(ctx));
+        CHECK(memcmp(&lo[(size_t)k], &w.want[good], sizeof(bsw_presult)) == 0, "live ticket %d: its result", k);
+    }
+    CHECK(bsw_inflight(ctx) == 0, "tickets left");
+    /* (the caller frees rd next: a refused submit by read index that kept the block would make that BSW_E_BUSY) */
+}
+
 /* ---- every validation code ---- */
 static int checks_mode()
 {
@@ -392,6 +469,7 @@ static int checks_mode()
         CHECK(bsw_patch_ref_batch(ctx, nullptr, ref, w.t.data(), 2, o.data()) == BSW_E_INVAL && bsw_patch_ref_batch(ctx, &p, ref, w.t.data(), 2, nullptr) == BSW_E_INVAL, "NULL arguments");
         CHECK(bsw_patch_ref_batch(nullptr, &p, ref, w.t.data(), 2, o.data()) == BSW_E_INVAL, "no context");
         CHECK(bsw_inflight(ctx) == 0, "nothing was queued");
+        nine_entry_points(ctx, p, ref, oref, rd, w, good);
         CHECK(bsw_reads_free(ctx, rd) == BSW_OK && bsw_reads_free(other, ord) == BSW_OK, "a rejected reads submit gives its block back");
         bsw_ref_free(ctx, ref);
         bsw_ref_free(other, oref);

@@ -1640,8 +1640,13 @@ static void slot_main(bsw_ctx *ctx, size_t d, size_t s)
                 if (ce != hipSuccess) rc = fail(fe, BSW_E_HIP, "result DMA: %s", hipGetErrorString(ce));
             }
         }
-        if (!rc) rc = sync_stream(ctx, fe, stream, dev.events[s]);
-        else { errs quiet; (void)sync_stream(ctx, quiet, stream, dev.events[s]); }     /* leave nothing of the chunk in flight */
+        if (!rc) {
+            rc = sync_stream(ctx, fe, stream, dev.events[s]);
+            /* the wait itself failed: that proves nothing about the result copy, which writes the caller's array.  Wait once more
+             * before the failure is reported (the caller may free the array as soon as its wait returns); a second failure leaves
+             * nothing to promise about the buffers, as in drain_after_error */
+            if (rc) { errs quiet; if (sync_stream(ctx, quiet, stream, dev.events[s]) != BSW_OK) ctx->dead = true; }
+        } else { errs quiet; (void)sync_stream(ctx, quiet, stream, dev.events[s]); }     /* leave nothing of the chunk in flight */
         if (!rc && !pend.direct) memcpy(pend.out, st.h_out.p, pend.n * rec);
         if (rc) ticket_fail(pend.t, rc, fe);
         else { pp.d2h_bytes += pend.n * rec; pp.seeds += pend.n; }

@@ -11,6 +11,7 @@
  *   bsw_matesw.hip  mem_matesw's ksw_align2 against the resident reference, batch and ticketed submit
  *   bsw_reads.hip   the resident read store: upload, free, info (its submits live with their pointer forms in the three files above)
  *   bsw_reads_async.hip  the asynchronous upload: the reads cross as they lie and bsw_reads_pack_kernel packs them on the GPU
+ *   bsw_chain2aln_job.hip  mem_chain2aln as one job of the pipeline: plan (bsw_chain2aln.c) + extension submit, then wait + replay
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
 #ifndef BSW_INTERNAL_H
@@ -536,6 +537,11 @@ struct drain_on_failure {
         if (armed) (void)sync_stream(ctx, quiet, s, ev);
     }
 };
+/* bsw_chain2aln.c: bsw_chain2aln_replay without its pass over the chains and seeds, for arrays bsw_chain2aln_plan has accepted,
+ * the reads split over up to `threads` threads */
+extern "C" BSW_LOCAL int bsw_c2a_replay_planned(const bsw_params *p, const bsw_c2a_opt *opt, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds,
+                                                size_t n_seeds, const int32_t *lens, size_t n_reads, const void *results, int result_format, bsw_creg *regs,
+                                                size_t *n_regs, uint8_t *extended, uint64_t *reg_start, int threads);
 BSW_LOCAL int check_params(errs &e, const bsw_params *p, bsw_dparams *dp);
 BSW_LOCAL int mat_max(const int8_t *mat);
 BSW_LOCAL int gap_limit(const bsw_params *p, int mx, int qlen, int end_bonus);

@@ -8,6 +8,7 @@ numpy structured dtypes below are byte-for-byte the C structs of include/bwa_sw_
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -61,6 +62,16 @@ PTASK = np.dtype([("query", "<u8"), ("l_query", "<i4"), ("_pad", "<i4"), ("a", P
 RD_PTASK = np.dtype([("read", "<u4"), ("_pad", "<i4"), ("a", PREG), ("b", PREG)])
 PRESULT = np.dtype([("score", "<i4"), ("w", "<i4"), ("gscore", "<i4"), ("status", "<i4")])
 assert PREG.itemsize == 32 and PTASK.itemsize == 80 and RD_PTASK.itemsize == 72 and PRESULT.itemsize == 16
+# mem_chain2aln (bsw_chain2aln_*): a chain's seeds with their scores, the chains of a read block, the regions bwa pushes
+CSEED = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4"), ("score", "<i4"), ("_pad", "<i4")])
+CHAIN = np.dtype([("read", "<u4"), ("n_seeds", "<i4"), ("first_seed", "<u8"), ("rlo", "<i8"), ("rhi", "<i8"), ("rid", "<i4"),
+                  ("frac_rep", "<f4")])
+CREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("truesc", "<i4"), ("w", "<i4"),
+                 ("seedcov", "<i4"), ("seedlen0", "<i4"), ("rid", "<i4"), ("frac_rep", "<f4"), ("read", "<u4"), ("chain", "<u4"),
+                 ("seed", "<u4")])
+C2A_OPT = np.dtype([("seedlen0_frac", "<f8"), ("ovl_len_frac", "<f8")])
+C2A_STATS = np.dtype([("seeds_gpu", "<u8"), ("seeds_bwa", "<u8"), ("regs", "<u8"), ("chains", "<u8"), ("reads", "<u8")])
+assert CSEED.itemsize == 24 and CHAIN.itemsize == 40 and CREG.itemsize == 64 and C2A_OPT.itemsize == 16 and C2A_STATS.itemsize == 40
 # how the reads of a block are encoded at its upload (BSW_READS_*): codes 0..4, FASTQ letters, 4-bit words
 READS_CODES, READS_ASCII, READS_PACKED = 0, 1, 2
 MAX_DEVICES = 16
@@ -185,6 +196,14 @@ def lib():
             "bsw_patch_reads_submit_t": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]),
             "bsw_patch_pretest": (C.c_int, [vp, C.c_int64, vp, vp, C.POINTER(C.c_int)]),
             "bsw_patch_decide": (C.c_int, [vp, vp, C.c_int]),
+            "bsw_c2a_default_opt": (None, [vp]),
+            "bsw_chain2aln_plan": (C.c_int, [vp, C.c_int64, vp, sz, vp, sz, vp, sz, vp, vp, vp, C.c_char_p, sz]),
+            "bsw_chain2aln_replay": (C.c_int, [vp, vp, vp, sz, vp, sz, vp, sz, vp, C.c_int, vp, C.POINTER(sz), vp, vp]),
+            "bsw_chain2aln_ref_start": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp)]),
+            "bsw_chain2aln_reads_start": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, sz, C.POINTER(vp)]),
+            "bsw_chain2aln_test": (C.c_int, [vp]),
+            "bsw_chain2aln_finish": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp, vp]),
+            "bsw_chain2aln_stats": (C.c_int, [vp, vp]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -219,7 +238,9 @@ def lib():
     return _lib
 
 
-EXPORTS = ["ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
+EXPORTS = ["bsw_c2a_default_opt", "bsw_chain2aln_plan", "bsw_chain2aln_replay", "bsw_chain2aln_ref_start", "bsw_chain2aln_reads_start",
+           "bsw_chain2aln_test", "bsw_chain2aln_finish", "bsw_chain2aln_stats",
+           "ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
            "bsw_patch_ref_batch", "bsw_patch_ref_submit_t", "bsw_patch_reads_submit_t", "bsw_patch_pretest", "bsw_patch_decide",
            "bsw_reads_upload", "bsw_reads_upload_start", "bsw_reads_upload_enc", "bsw_reads_upload_start_enc", "bsw_reads_test", "bsw_reads_wait", "bsw_reads_image", "bsw_reads_free", "bsw_reads_info", "bsw_submit_reads_t", "bsw_matesw_reads_submit_t", "bsw_cigar_reads_submit_t",
@@ -404,6 +425,8 @@ class BswContext:
 
     def close(self):
         if self.handle:
+            for job in list(getattr(self, "_jobs", ())):       # jobs never finished: their ticket and pinned arrays go first
+                job.release()
             lib().bsw_destroy(self.handle)
             self.handle = None
 
@@ -725,6 +748,33 @@ class BswContext:
         self._keep_alive(t.value, params, rdctasks, res, cig, md)
         return t.value, res, cig, md
 
+    # mem_chain2aln as one job of the pipeline: every seed is extended, bwa's loop is replayed over the results
+    def chain2aln_start(self, params, ref, chains, seeds, rd=None, reads=None, opt=None):
+        """bsw_chain2aln_reads_start (rd: a resident block) or bsw_chain2aln_ref_start (reads: a list of uint8 code arrays).
+        chains: CHAIN array, seeds: CSEED array.  Returns a Chain2alnJob; it takes the place of the extension ticket."""
+        chains, seeds = np.ascontiguousarray(chains, dtype=CHAIN), np.ascontiguousarray(seeds, dtype=CSEED)
+        o = c2a_opt(**(opt or {}))
+        h = C.c_void_p()
+        keep = [params, chains, seeds, o]
+        if rd is not None:
+            rc = lib().bsw_chain2aln_reads_start(self.handle, params.ctypes.data, o.ctypes.data, ref, rd, chains.ctypes.data, len(chains),
+                                                 seeds.ctypes.data, len(seeds), C.byref(h))
+            n_reads = self.reads_info(rd)["n_reads"]
+        else:
+            arrs = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+            ptrs = np.array([r.ctypes.data if len(r) else 0 for r in arrs], dtype=np.uint64)
+            lens = np.array([len(r) for r in arrs], dtype=np.int32)
+            keep += [arrs, ptrs, lens]
+            rc = lib().bsw_chain2aln_ref_start(self.handle, params.ctypes.data, o.ctypes.data, ref, ptrs.ctypes.data, lens.ctypes.data, len(arrs),
+                                               chains.ctypes.data, len(chains), seeds.ctypes.data, len(seeds), C.byref(h))
+            n_reads = len(arrs)
+        self._chk(rc, "bsw_chain2aln_start")
+        job = Chain2alnJob(self, h, len(seeds), n_reads, keep)
+        if not hasattr(self, "_jobs"):
+            self._jobs = weakref.WeakSet()
+        self._jobs.add(job)
+        return job
+
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""
         res = np.zeros(len(atasks), dtype=KSWR)
@@ -777,6 +827,108 @@ class BswContext:
         if rc < 0:
             self._chk(rc, "bsw_refbatch_run")
         return out, rc
+
+
+class Chain2alnJob:
+    """One bsw_c2a_job: test() polls, finish() collects the ticket, replays mem_chain2aln and frees the job.  A job that is dropped
+    without finish() — an exception between start and finish, a `with` block left early — is released (waited for, its results
+    thrown away): by release(), at the end of a `with job:` block, by the context's close(), or when the object is collected."""
+
+    def __init__(self, ctx, handle, n_seeds, n_reads, keep):
+        self.ctx, self.handle, self.n_seeds, self.n_reads, self._keep = ctx, handle, n_seeds, n_reads, keep
+
+    def release(self):
+        """give up a job that was not finished: its place among the submits in flight and its pinned arrays are freed"""
+        h, self.handle = self.handle, None
+        if h and self.ctx.handle:                           # (a context that is closed has released its jobs itself)
+            n = C.c_size_t(0)
+            lib().bsw_chain2aln_finish(h, None, C.byref(n), None, None, None)      # waits; frees the job whatever it returns
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def test(self):
+        rc = lib().bsw_chain2aln_test(self.handle)
+        if rc < 0:
+            self.ctx._chk(rc, "bsw_chain2aln_test")
+        return bool(rc)
+
+    def stats(self):
+        s = np.zeros(1, dtype=C2A_STATS)
+        rc = lib().bsw_chain2aln_stats(self.handle, s.ctypes.data)
+        if rc:
+            raise BswError(rc, "bsw_chain2aln_stats")
+        return {k: int(s[k][0]) for k in C2A_STATS.names}
+
+    def finish(self):
+        """-> (CREG array in bwa's push order, extended uint8[n_seeds], reg_start uint64[n_reads + 1], stats dict)"""
+        regs = np.zeros(max(self.n_seeds, 1), dtype=CREG)
+        ext = np.zeros(max(self.n_seeds, 1), dtype=np.uint8)
+        start = np.zeros(self.n_reads + 1, dtype=np.uint64)
+        st = np.zeros(1, dtype=C2A_STATS)
+        n = C.c_size_t(0)
+        h, self.handle = self.handle, None                  # finish frees the job whatever it returns
+        try:
+            self.ctx._chk(lib().bsw_chain2aln_finish(h, regs.ctypes.data, C.byref(n), ext.ctypes.data, start.ctypes.data, st.ctypes.data),
+                          "bsw_chain2aln_finish")
+        finally:
+            self._keep = None
+        return regs[:n.value], ext[:self.n_seeds], start, {k: int(st[k][0]) for k in C2A_STATS.names}
+
+
+def c2a_opt(**over):
+    """bsw_c2a_default_opt, with fields replaced (seedlen0_frac < 0: the bwa-0.7.8 behaviour)"""
+    o = np.zeros(1, dtype=C2A_OPT)
+    lib().bsw_c2a_default_opt(o.ctypes.data)
+    for k, v in over.items():
+        o[k] = v
+    return o
+
+
+def chain2aln_plan(params, l_pac, chains, seeds, lens, reads=None):
+    """bsw_chain2aln_plan: -> (RD_TASK array, REF_TASK array or None when reads is None).  reads: list of uint8 arrays whose
+    addresses the REF_TASK records store (keep them alive).  Raises BswError with the plan's text."""
+    chains, seeds = np.ascontiguousarray(chains, dtype=CHAIN), np.ascontiguousarray(seeds, dtype=CSEED)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    rdt = np.zeros(len(seeds), dtype=RD_TASK)
+    rft = np.zeros(len(seeds), dtype=REF_TASK) if reads is not None else None
+    ptrs = np.array([r.ctypes.data if len(r) else 0 for r in reads], dtype=np.uint64) if reads is not None else None
+    err = C.create_string_buffer(400)
+    rc = lib().bsw_chain2aln_plan(params.ctypes.data, l_pac, chains.ctypes.data, len(chains), seeds.ctypes.data, len(seeds), lens.ctypes.data,
+                                  len(lens), ptrs.ctypes.data if reads is not None else None, rdt.ctypes.data,
+                                  rft.ctypes.data if reads is not None else None, err, 400)
+    if rc:
+        raise BswError(rc, err.value.decode())
+    return rdt, rft
+
+
+def chain2aln_replay(params, chains, seeds, lens, results, opt=None):
+    """bsw_chain2aln_replay over a RESULT or a PAIR array (one record per seed, in seed order) -> (CREG array, extended, reg_start)"""
+    chains, seeds = np.ascontiguousarray(chains, dtype=CHAIN), np.ascontiguousarray(seeds, dtype=CSEED)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    results = np.ascontiguousarray(results)
+    assert results.dtype in (RESULT, PAIR) and len(results) == len(seeds)
+    o = c2a_opt(**(opt or {}))
+    regs = np.zeros(max(len(seeds), 1), dtype=CREG)
+    ext = np.zeros(max(len(seeds), 1), dtype=np.uint8)
+    start = np.zeros(len(lens) + 1, dtype=np.uint64)
+    n = C.c_size_t(0)
+    rc = lib().bsw_chain2aln_replay(params.ctypes.data, o.ctypes.data, chains.ctypes.data, len(chains), seeds.ctypes.data, len(seeds),
+                                    lens.ctypes.data, len(lens), results.ctypes.data, RESULT_PAIR if results.dtype == PAIR else RESULT_FULL,
+                                    regs.ctypes.data, C.byref(n), ext.ctypes.data, start.ctypes.data)
+    if rc:
+        raise BswError(rc, "bsw_chain2aln_replay")
+    return regs[:n.value], ext[:len(seeds)], start
 
 
 class HostArena:

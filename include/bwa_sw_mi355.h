@@ -34,6 +34,9 @@
  *   bsw_patch_ref_batch        mem_patch_reg (mem_sort_dedup_patch, bwa >= 0.7.10) against the
  *                              device-resident reference: the score of bwa_gen_cigar2 without a
  *                              CIGAR, and the tests around it (bwa host software, not the RTL)
+ *   bsw_chain2aln_*_start,     mem_chain2aln's driver around ksw_extend2 (bwa 0.7.12 - 0.7.17, as recalled): which seeds of a chain
+ *   bsw_chain2aln_finish       are extended, in which order, and the regions with seedcov / seedlen0 / rid / frac_rep; every seed
+ *                              is extended as one job of the pipeline, bwa's loop is replayed on the host (bwa host software)
  *   bsw_cigar_ref_submit_t /   the three calls above as tickets of the streaming pipeline:
  *   bsw_matesw_ref_submit_t /  every device of the context, beside extension submits
  *   bsw_patch_ref_submit_t
@@ -403,8 +406,9 @@ int      bsw_cigar_ref_batch(bsw_ctx *ctx, const bsw_params *p, const struct bsw
  * and streams the extension submits use, in submit order with them: it is accepted while extension submits are in flight and
  * the other way round.  res, cigars and md receive, byte for byte, what bsw_cigar_ref_batch writes for the same tasks, in task
  * order.  tasks[], the reads they point to, res, cigars and md stay valid until the ticket is collected.  A chunk that fails
- * makes the others of its ticket give up; the wait returns the failure, nothing of the ticket is still queued then, and other
- * tickets are left alone.  May be called on one context from several threads (THREADS above).
+ * makes the others of its ticket give up; the wait returns the failure, nothing of the ticket is still queued then (this holds for
+ * every submit: a slot whose own wait for a chunk fails waits once more before it reports, so res and the other arrays may be freed as
+ * soon as bsw_wait_ticket has returned the failure — unless the context is dead, below), and other tickets are left alone.  May be called on one context from several threads (THREADS above).
  * A watchdog expiry is different: the wait answers BSW_E_HIP, the context is dead, and what the hung device still holds in its
  * queues may read the reads and `ref` whenever it wakes.  Call bsw_destroy (it leaves the runtime alone on a dead context), do
  * NOT call bsw_ref_free on that reference and do not free or unregister the reads of the failed tickets: that memory is
@@ -731,6 +735,92 @@ int      bsw_matesw_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_
 int      bsw_cigar_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_ref *ref, const bsw_reads *rd,
                                   const bsw_rd_ctask *tasks, size_t n, int max_cigar, uint32_t *cigars, int max_md, char *md,
                                   bsw_cresult *res, bsw_ticket *ticket);
+
+/* ---- mem_chain2aln itself (bwamem.c of bwa 0.7.12 - 0.7.17, restated AS RECALLED: bwa's source is not in this tree):
+ * the loop that DRIVES the seed extension.  Per read bwa keeps one growing list av of regions, shared by the read's chains.  It
+ * visits a chain's seeds by score (srt[i] = (uint64)score << 32 | i sorted ascending, walked from the top: highest score first,
+ * the larger index first among equal scores), SKIPS a seed that an earlier region of the read explains — the seed lies inside
+ * the region on both axes, is not more than 0.1 * l_query longer than the seed the region grew from, and sits within
+ * min(cal_max_gap, region.w) of the region's diagonal ahead of or behind it — UN-SKIPS it when a seed of the same chain that was
+ * visited earlier and not skipped, at least 0.95 times as long, overlaps it on the query by len >> 2 or more on another
+ * diagonal, and stamps every region with seedcov, seedlen0, rid and frac_rep.  A region per seed is NOT bwa's output.
+ * The extension of a seed does not depend on av, only the decision to run it does: bsw_chain2aln_plan makes a task of EVERY
+ * seed, the existing extension path runs them, and bsw_chain2aln_replay walks bwa's loop with the results at hand.  The
+ * result of a skipped seed is never read; regs[] is bwa's av, in bwa's push order.  What the speculation costs: README.
+ * The skip mark is the VALUE 0 in srt[], as in bwa, so (score 0, index 0) reads as skipped; with scores >= 0 that entry is
+ * visited last and nothing reads it afterwards, so the quirk is kept and has no effect.  Negative scores are refused.
+ * A host of the bwa-0.7.8 era passes score = len and seedlen0_frac < 0. ---- */
+typedef struct bsw_cseed {           /* mem_seed_t with its score */
+    int64_t rbeg;
+    int32_t qbeg, len, score, _pad;
+} bsw_cseed;                         /* 24 bytes */
+typedef struct bsw_chain {           /* mem_chain_t: seeds[first_seed, first_seed + n_seeds) */
+    uint32_t read;                   /* the chains are sorted by read (a read's chains contiguous), in bwa's order inside a read (after mem_chain_flt) */
+    int32_t  n_seeds;
+    uint64_t first_seed;             /* chain k's seeds follow chain k-1's: seeds[] is the chains' seeds laid end to end */
+    int64_t  rlo, rhi;               /* the chain's contig in [0, 2*l_pac) coordinates (forward: [offset, offset + len), reverse: mirrored); the
+                                        window is clamped into it as bns_fetch_seq does.  rhi <= rlo: no clamp */
+    int32_t  rid;                    /* copied into the regions */
+    float    frac_rep;
+} bsw_chain;                         /* 40 bytes */
+typedef struct bsw_creg {            /* the fields of mem_alnreg_t that mem_chain2aln writes */
+    int64_t  rb, re;
+    int32_t  qb, qe, score, truesc, w;
+    int32_t  seedcov;                /* sum of len over ALL seeds of the chain inside the region on both axes, skipped ones too */
+    int32_t  seedlen0;               /* length of the seed the region grew from */
+    int32_t  rid;
+    float    frac_rep;
+    uint32_t read, chain, seed;      /* where it came from: indices into lens[] / chains[] / seeds[] */
+} bsw_creg;                          /* 64 bytes */
+typedef struct bsw_c2a_opt {
+    double seedlen0_frac;            /* .1: a region does not explain a seed with len - seedlen0 > seedlen0_frac * l_query; < 0: test off (bwa 0.7.8) */
+    double ovl_len_frac;             /* .95: only a seed t with t.len >= ovl_len_frac * s.len can un-skip s */
+} bsw_c2a_opt;
+typedef struct bsw_c2a_stats {
+    uint64_t seeds_gpu;              /* seeds extended on the GPU: all of them */
+    uint64_t seeds_bwa;              /* seeds bwa would have extended = regions pushed (0 before the replay) */
+    uint64_t regs;
+    uint64_t chains, reads;
+} bsw_c2a_stats;
+void     bsw_c2a_default_opt(bsw_c2a_opt *o);
+/* Pure host.  One task per seed, in seed order: tag = the seed's index in seeds[], init_score = -1, the window of its chain
+ * (bsw_chain_window, then the chain's contig clamp).  rd_tasks[n_seeds] and ref_tasks[n_seeds] may each be NULL; ref_tasks needs
+ * reads[n_reads] (the pointers it stores).  lens[read] = l_query.  err (may be NULL) receives the text of a failure.
+ * BSW_E_INVAL: a seed outside its read or outside [0, 2*l_pac), a negative score, a chain without seeds or of a read >= n_reads,
+ * chains not sorted by read (the chains of a read not contiguous), seeds[] not the chains' seeds end to end, a seed outside its
+ * chain's clamped window; BSW_E_LIMIT: a window side (reference bases left or right of a seed) beyond BSW_MAX_TLEN. */
+int      bsw_chain2aln_plan(const bsw_params *p, int64_t l_pac, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds, size_t n_seeds,
+                            const int32_t *lens, size_t n_reads, const uint8_t *const *reads, bsw_rd_task *rd_tasks, bsw_ref_task *ref_tasks,
+                            char *err, size_t err_cap);
+/* Pure host, one thread.  results[i] = the record of seed i (the plan's task order): bsw_result[] for BSW_RESULT_FULL, bsw_pair[] for
+ * BSW_RESULT_PAIR (the pair record holds everything the replay reads).  opt == NULL: the defaults.  Writes regs[0 .. *n_regs)
+ * (capacity n_seeds): the reads in order, a read's regions contiguous and in bwa's push order; extended[n_seeds] (may be NULL): 1
+ * where bwa runs the extension; reg_start[n_reads + 1] (may be NULL): read r's regions are regs[reg_start[r], reg_start[r + 1]). */
+int      bsw_chain2aln_replay(const bsw_params *p, const bsw_c2a_opt *opt, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds,
+                              size_t n_seeds, const int32_t *lens, size_t n_reads, const void *results, int result_format, bsw_creg *regs,
+                              size_t *n_regs, uint8_t *extended, uint64_t *reg_start);
+/* The two as ONE JOB of the ticket pipeline, in place of the extension ticket: start = plan, the task and result arrays in
+ * DMA-able memory (bsw_host_alloc), bsw_submit_ref_t / bsw_submit_reads_t; finish = bsw_wait_ticket, replay, free.  The job is one
+ * of the context's BSW_MAX_INFLIGHT submits (one more answers BSW_E_BUSY and leaves no job), runs over every device of the
+ * context and reads the context's result_format.  A failed start leaves *job NULL and queues nothing; its code is the plan's or
+ * the submit's (a flank beyond BSW_MAX_QLEN: the submit's BSW_E_LIMIT), the text is in bsw_last_error.  chains[], seeds[], lens[]
+ * and the reads (the block) stay valid AND UNCHANGED until finish (they are checked once, by start's plan).  A start beside
+ * BSW_MAX_INFLIGHT submits is refused before anything is allocated or planned.  n_seeds == 0 makes a job without a ticket that is complete at once.
+ * finish replays on the caller's thread and up to bsw_config.pack_threads - 1 helpers (reads are independent: the block's reads are
+ * split into parts of at least 1 024 seeds); bsw_chain2aln_replay itself runs on the calling thread alone.
+ * bsw_chain2aln_test: 1 complete, 0 in flight, < 0 an error; never blocks.  bsw_chain2aln_finish returns the ticket's failure or the
+ * replay's and frees the job WHATEVER it returns (job == NULL: BSW_E_INVAL); the arrays are bsw_chain2aln_replay's, stats (may be
+ * NULL) receives the counts.  bsw_chain2aln_stats: the same counts of a job that has not been finished (seeds_bwa and regs are
+ * 0 then: they are the replay's).  The calls may come from several threads, one job from one thread at a time. */
+typedef struct bsw_c2a_job bsw_c2a_job;
+int      bsw_chain2aln_ref_start(bsw_ctx *ctx, const bsw_params *p, const bsw_c2a_opt *opt, const bsw_ref *ref, const uint8_t *const *reads,
+                                 const int32_t *lens, size_t n_reads, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds, size_t n_seeds,
+                                 bsw_c2a_job **job);
+int      bsw_chain2aln_reads_start(bsw_ctx *ctx, const bsw_params *p, const bsw_c2a_opt *opt, const bsw_ref *ref, const bsw_reads *rd,
+                                   const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds, size_t n_seeds, bsw_c2a_job **job);
+int      bsw_chain2aln_test(bsw_c2a_job *job);
+int      bsw_chain2aln_finish(bsw_c2a_job *job, bsw_creg *regs, size_t *n_regs, uint8_t *extended, uint64_t *reg_start, bsw_c2a_stats *stats);
+int      bsw_chain2aln_stats(const bsw_c2a_job *job, bsw_c2a_stats *stats);
 
 /* ---- mem_patch_reg (bwamem.c of bwa >= 0.7.10, restated AS RECALLED: bwa's source is not in this tree) against the resident
  * reference: may two regions a, b of one read be joined into one?  Pre-tests on the host (strand, colinearity, the band and

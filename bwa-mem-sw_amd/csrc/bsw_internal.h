@@ -12,6 +12,7 @@
  *   bsw_reads.hip   the resident read store: upload, free, info (its submits live with their pointer forms in the three files above)
  *   bsw_reads_async.hip  the asynchronous upload: the reads cross as they lie and bsw_reads_pack_kernel packs them on the GPU
  *   bsw_chain2aln_job.hip  mem_chain2aln as one job of the pipeline: plan (bsw_chain2aln.c) + extension submit, then wait + replay
+ *   bsw_sdp_job.hip  mem_sort_dedup_patch as a job around the patch tickets: the engine (bsw_sdp.c) + one patch submit per round
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
 #ifndef BSW_INTERNAL_H
@@ -542,6 +543,8 @@ struct drain_on_failure {
 extern "C" BSW_LOCAL int bsw_c2a_replay_planned(const bsw_params *p, const bsw_c2a_opt *opt, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds,
                                                 size_t n_seeds, const int32_t *lens, size_t n_reads, const void *results, int result_format, bsw_creg *regs,
                                                 size_t *n_regs, uint8_t *extended, uint64_t *reg_start, int threads);
+/* bsw_sdp.c: the engine's counts before it has finished, for bsw_sdp_job_stats (bsw_sdp_job.hip) */
+extern "C" BSW_LOCAL int bsw_sdp_peek_stats(const bsw_sdp_eng *eng, bsw_sdp_stats *stats);
 BSW_LOCAL int check_params(errs &e, const bsw_params *p, bsw_dparams *dp);
 BSW_LOCAL int mat_max(const int8_t *mat);
 BSW_LOCAL int gap_limit(const bsw_params *p, int mx, int qlen, int end_bonus);

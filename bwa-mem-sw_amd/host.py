@@ -72,6 +72,13 @@ CREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("s
 C2A_OPT = np.dtype([("seedlen0_frac", "<f8"), ("ovl_len_frac", "<f8")])
 C2A_STATS = np.dtype([("seeds_gpu", "<u8"), ("seeds_bwa", "<u8"), ("regs", "<u8"), ("chains", "<u8"), ("reads", "<u8")])
 assert CSEED.itemsize == 24 and CHAIN.itemsize == 40 and CREG.itemsize == 64 and C2A_OPT.itemsize == 16 and C2A_STATS.itemsize == 40
+# mem_sort_dedup_patch (bsw_sdp_*): the fields of a region it reads or writes, its options and its counts
+SREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("truesc", "<i4"), ("w", "<i4"),
+                 ("seedcov", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("rid", "<i4"), ("n_comp", "<i4"), ("read", "<u4"), ("src", "<u4")])
+SDP_OPT = np.dtype([("mask_level_redun", "<f4"), ("max_chain_gap", "<i4"), ("patch", "<i4"), ("presorted", "<i4")])
+SDP_STATS = np.dtype([(k, "<u8") for k in ("reads", "regs_in", "regs_out", "merges", "kills_p", "kills_q", "dups", "rounds", "tasks_first",
+                                           "tasks", "alns_bwa")])
+assert SREG.itemsize == 64 and SDP_OPT.itemsize == 16 and SDP_STATS.itemsize == 88
 # how the reads of a block are encoded at its upload (BSW_READS_*): codes 0..4, FASTQ letters, 4-bit words
 READS_CODES, READS_ASCII, READS_PACKED = 0, 1, 2
 MAX_DEVICES = 16
@@ -204,6 +211,18 @@ def lib():
             "bsw_chain2aln_test": (C.c_int, [vp]),
             "bsw_chain2aln_finish": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp, vp]),
             "bsw_chain2aln_stats": (C.c_int, [vp, vp]),
+            "bsw_sdp_default_opt": (None, [vp]),
+            "bsw_sdp_from_cregs": (C.c_int, [vp, sz, vp]),
+            "bsw_sdp_open": (C.c_int, [vp, vp, C.c_int64, vp, sz, vp, vp, sz, C.POINTER(vp), C.c_char_p, sz]),
+            "bsw_sdp_needs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz)]),
+            "bsw_sdp_feed": (C.c_int, [vp, vp, sz]),
+            "bsw_sdp_collect": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp]),
+            "bsw_sdp_close": (None, [vp]),
+            "bsw_sdp_ref_start": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(vp)]),
+            "bsw_sdp_reads_start": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(vp)]),
+            "bsw_sdp_test": (C.c_int, [vp]),
+            "bsw_sdp_finish": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp]),
+            "bsw_sdp_job_stats": (C.c_int, [vp, vp]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -240,6 +259,8 @@ def lib():
 
 EXPORTS = ["bsw_c2a_default_opt", "bsw_chain2aln_plan", "bsw_chain2aln_replay", "bsw_chain2aln_ref_start", "bsw_chain2aln_reads_start",
            "bsw_chain2aln_test", "bsw_chain2aln_finish", "bsw_chain2aln_stats",
+           "bsw_sdp_default_opt", "bsw_sdp_from_cregs", "bsw_sdp_open", "bsw_sdp_needs", "bsw_sdp_feed", "bsw_sdp_collect", "bsw_sdp_close",
+           "bsw_sdp_ref_start", "bsw_sdp_reads_start", "bsw_sdp_test", "bsw_sdp_finish", "bsw_sdp_job_stats",
            "ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
            "bsw_patch_ref_batch", "bsw_patch_ref_submit_t", "bsw_patch_reads_submit_t", "bsw_patch_pretest", "bsw_patch_decide",
@@ -775,6 +796,35 @@ class BswContext:
         self._jobs.add(job)
         return job
 
+    # mem_sort_dedup_patch as a job around the patch tickets
+    def sdp_start(self, params, ref, regs, reg_start, rd=None, reads=None, opt=None):
+        """bsw_sdp_reads_start (rd: a resident block) or bsw_sdp_ref_start (reads: a list of uint8 code arrays).  regs: SREG array
+        sorted by read, reg_start: uint64[n_reads + 1] (what Chain2alnJob.finish and sdp_from_cregs give).  Returns an SdpJob."""
+        regs, reg_start = np.ascontiguousarray(regs, dtype=SREG), np.ascontiguousarray(reg_start, dtype=np.uint64)
+        o = sdp_opt(**(opt or {}))
+        h = C.c_void_p()
+        keep = [params, regs, reg_start, o]
+        if rd is not None:
+            n_reads = self.reads_info(rd)["n_reads"]
+            assert len(reg_start) == n_reads + 1
+            rc = lib().bsw_sdp_reads_start(self.handle, params.ctypes.data, o.ctypes.data, ref, rd, regs.ctypes.data, len(regs),
+                                           reg_start.ctypes.data, C.byref(h))
+        else:
+            arrs = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+            ptrs = np.array([r.ctypes.data if len(r) else 0 for r in arrs], dtype=np.uint64)
+            lens = np.array([len(r) for r in arrs], dtype=np.int32)
+            assert len(reg_start) == len(arrs) + 1
+            keep += [arrs, ptrs, lens]
+            rc = lib().bsw_sdp_ref_start(self.handle, params.ctypes.data, o.ctypes.data, ref, ptrs.ctypes.data, lens.ctypes.data, len(arrs),
+                                         regs.ctypes.data, len(regs), reg_start.ctypes.data, C.byref(h))
+            n_reads = len(arrs)
+        self._chk(rc, "bsw_sdp_start")
+        job = SdpJob(self, h, len(regs), n_reads, keep)
+        if not hasattr(self, "_jobs"):
+            self._jobs = weakref.WeakSet()
+        self._jobs.add(job)
+        return job
+
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""
         res = np.zeros(len(atasks), dtype=KSWR)
@@ -929,6 +979,143 @@ def chain2aln_replay(params, chains, seeds, lens, results, opt=None):
     if rc:
         raise BswError(rc, "bsw_chain2aln_replay")
     return regs[:n.value], ext[:len(seeds)], start
+
+
+def sdp_opt(**over):
+    """bsw_sdp_default_opt, with fields replaced (patch=0: the call after mate rescue; presorted=1: keep the caller's tie order)"""
+    o = np.zeros(1, dtype=SDP_OPT)
+    lib().bsw_sdp_default_opt(o.ctypes.data)
+    for k, v in over.items():
+        o[k] = v
+    return o
+
+
+def sdp_from_cregs(cregs):
+    """bsw_sdp_from_cregs: a CREG array (Chain2alnJob.finish) as an SREG array"""
+    cregs = np.ascontiguousarray(cregs, dtype=CREG)
+    s = np.zeros(len(cregs), dtype=SREG)
+    rc = lib().bsw_sdp_from_cregs(cregs.ctypes.data, len(cregs), s.ctypes.data)
+    if rc:
+        raise BswError(rc, "bsw_sdp_from_cregs")
+    return s
+
+
+def _sdp_stats(st):
+    return {k: int(st[k][0]) for k in SDP_STATS.names}
+
+
+class SdpEngine:
+    """One bsw_sdp_eng (pure host): needs() -> RD_PTASK array (a copy; empty: every read is finished), feed(PRESULT array of exactly
+    those tasks), collect() -> (SREG array, out_start, stats dict).  Raises BswError with open's text."""
+
+    def __init__(self, params, l_pac, regs, reg_start, lens, opt=None):
+        regs, reg_start = np.ascontiguousarray(regs, dtype=SREG), np.ascontiguousarray(reg_start, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        assert len(reg_start) == len(lens) + 1
+        o = sdp_opt(**(opt or {}))
+        self.handle, self.n_regs, self.n_reads = C.c_void_p(), len(regs), len(lens)
+        err = C.create_string_buffer(400)
+        rc = lib().bsw_sdp_open(params.ctypes.data, o.ctypes.data, l_pac, regs.ctypes.data, len(regs), reg_start.ctypes.data, lens.ctypes.data,
+                                len(lens), C.byref(self.handle), err, 400)
+        if rc:
+            self.handle = None
+            raise BswError(rc, err.value.decode())
+
+    def needs(self):
+        t, n = C.c_void_p(), C.c_size_t(0)
+        rc = lib().bsw_sdp_needs(self.handle, C.byref(t), C.byref(n))
+        if rc:
+            raise BswError(rc, "bsw_sdp_needs")
+        if not n.value:
+            return np.zeros(0, dtype=RD_PTASK)
+        return np.frombuffer(C.string_at(t.value, n.value * RD_PTASK.itemsize), dtype=RD_PTASK).copy()
+
+    def feed(self, results):
+        results = np.ascontiguousarray(results, dtype=PRESULT)
+        rc = lib().bsw_sdp_feed(self.handle, results.ctypes.data, len(results))
+        if rc:
+            raise BswError(rc, "bsw_sdp_feed")
+
+    def collect(self):
+        out = np.zeros(max(self.n_regs, 1), dtype=SREG)
+        start = np.zeros(self.n_reads + 1, dtype=np.uint64)
+        st = np.zeros(1, dtype=SDP_STATS)
+        n = C.c_size_t(0)
+        rc = lib().bsw_sdp_collect(self.handle, out.ctypes.data, C.byref(n), start.ctypes.data, st.ctypes.data)
+        if rc:
+            raise BswError(rc, "bsw_sdp_collect")
+        return out[:n.value], start, _sdp_stats(st)
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            lib().bsw_sdp_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SdpJob:
+    """One bsw_sdp_job: test() polls and moves the job on a round, finish() waits for the remaining rounds, returns the regions and
+    frees the job.  A job dropped without finish() is released as a Chain2alnJob is."""
+
+    def __init__(self, ctx, handle, n_regs, n_reads, keep):
+        self.ctx, self.handle, self.n_regs, self.n_reads, self._keep = ctx, handle, n_regs, n_reads, keep
+
+    def release(self):
+        h, self.handle = self.handle, None
+        if h and self.ctx.handle:
+            n = C.c_size_t(0)
+            if lib().bsw_sdp_finish(h, None, C.byref(n), None, None) == -6:     # BSW_E_BUSY: the job is intact, the places are others'
+                self.handle = h
+                return
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def test(self):
+        rc = lib().bsw_sdp_test(self.handle)
+        if rc < 0:
+            self.ctx._chk(rc, "bsw_sdp_test")
+        return bool(rc)
+
+    def stats(self):
+        s = np.zeros(1, dtype=SDP_STATS)
+        rc = lib().bsw_sdp_job_stats(self.handle, s.ctypes.data)
+        if rc:
+            raise BswError(rc, "bsw_sdp_job_stats")
+        return _sdp_stats(s)
+
+    def finish(self):
+        """-> (SREG array, out_start uint64[n_reads + 1], stats dict).  BswError BSW_E_BUSY leaves the job intact: collect a ticket, call again."""
+        out = np.zeros(max(self.n_regs, 1), dtype=SREG)
+        start = np.zeros(self.n_reads + 1, dtype=np.uint64)
+        st = np.zeros(1, dtype=SDP_STATS)
+        n = C.c_size_t(0)
+        rc = lib().bsw_sdp_finish(self.handle, out.ctypes.data, C.byref(n), start.ctypes.data, st.ctypes.data)
+        if rc != -6:                                        # finish has freed the job
+            self.handle, self._keep = None, None
+        self.ctx._chk(rc, "bsw_sdp_finish")
+        return out[:n.value], start, _sdp_stats(st)
 
 
 class HostArena:

@@ -37,6 +37,8 @@
  *   bsw_chain2aln_*_start,     mem_chain2aln's driver around ksw_extend2 (bwa 0.7.12 - 0.7.17, as recalled): which seeds of a chain
  *   bsw_chain2aln_finish       are extended, in which order, and the regions with seedcov / seedlen0 / rid / frac_rep; every seed
  *                              is extended as one job of the pipeline, bwa's loop is replayed on the host (bwa host software)
+ *   bsw_sdp_*_start,           mem_sort_dedup_patch (bwa 0.7.12 - 0.7.17, as recalled): the sort, the redundancy test, the merges through
+ *   bsw_sdp_finish             mem_patch_reg and the removal of duplicates, as a job around the patch tickets; both sorts stable
  *   bsw_cigar_ref_submit_t /   the three calls above as tickets of the streaming pipeline:
  *   bsw_matesw_ref_submit_t /  every device of the context, beside extension submits
  *   bsw_patch_ref_submit_t
@@ -282,7 +284,8 @@ int      bsw_host_unregister(void *p);
  *
  * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, bsw_patch_ref_submit_t, the four
  * *_reads_* submits (bsw_patch_reads_submit_t among them), bsw_reads_upload, bsw_reads_upload_enc, bsw_reads_upload_start, bsw_reads_upload_start_enc, bsw_reads_test,
- * bsw_reads_wait, bsw_reads_free, bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
+ * bsw_reads_wait, bsw_reads_free, bsw_sdp_ref_start, bsw_sdp_reads_start, bsw_sdp_test, bsw_sdp_finish, bsw_sdp_job_stats (one job from one thread at a time),
+ * bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
  * every other call that takes the context (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free,
  * bsw_host_stats, bsw_reads_image) needs it to itself.  bsw_set_align_long, bsw_align_long and bsw_align_long_stats take no
  * context and may be called from any thread at any time; a change applies to the calls that enter the library afterwards.
@@ -828,7 +831,7 @@ int      bsw_chain2aln_stats(const bsw_c2a_job *job, bsw_c2a_stats *stats);
  * against the reference [a.rb, b.re), band w_ through bwa_gen_cigar2's formula, both reversed on the reverse strand, the no-gap
  * shortcut when the spans agree and w_ == 0 — and the 0.90 test of that score against the two regions' scores.  No backtrack
  * matrix, no CIGAR, no NM / MD: 8 bytes per alignment come back.  mem_sort_dedup_patch's bookkeeping (a merged region changes
- * later pairs) stays with the caller: INTEGRATION.md "Region patching". ---- */
+ * later pairs) is bsw_sdp_* below, a job around these tickets: INTEGRATION.md "Region patching". ---- */
 typedef struct bsw_preg {            /* the fields of mem_alnreg_t that mem_patch_reg reads */
     int64_t  rb, re;
     int32_t  qb, qe, score, w;
@@ -870,6 +873,98 @@ int      bsw_patch_reads_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_r
  * bsw_patch_decide: mem_patch_reg's return value for bwa_gen_cigar2's score gscore (gscore, or 0 below the 0.90f ratio). */
 int      bsw_patch_pretest(const bsw_params *p, int64_t l_pac, const bsw_preg *a, const bsw_preg *b, int *w);
 int      bsw_patch_decide(const bsw_preg *a, const bsw_preg *b, int gscore);
+
+/* ---- mem_sort_dedup_patch (bwamem.c of bwa 0.7.12 - 0.7.17, restated AS RECALLED: bwa's source is not in this tree):
+ * the first thing bwa does with a read's regions av, and the loop AROUND mem_patch_reg.  Per read with n > 1 regions: sort by re,
+ * n_comp = 1, then for i = 1 .. n-1 (p = a[i]) descend j = i-1, i-2, ... (q = a[j]) WHILE p.rid == q.rid and
+ * p.rb < q.re + max_chain_gap — the condition ends the descent, and it is evaluated again with the smaller p.rb a merge leaves —
+ * skipping a q that was excluded (qe == qb).  A pair that overlaps by more than mask_level_redun of the shorter region on BOTH
+ * axes (binary32 products and comparisons, as bwa's float option makes them) is redundant: the lower score is excluded (p: the
+ * descent breaks; q otherwise, ties included).  Otherwise, when q.rb < p.rb and mem_patch_reg(q, p) > 0, q is merged into p:
+ * p.n_comp += q.n_comp + 1, seedcov / sub / csub the maxima, p.qb = q.qb, p.rb = q.rb, score = truesc = the return value,
+ * p.w = the band, q excluded.  Then the excluded regions are dropped, the rest sorted by score descending, rb, qb ascending, and
+ * of a run with equal (score, rb, qb) only the first is kept.  A read with n <= 1 is returned untouched (n_comp included).
+ * TIES.  bwa's two sorts are ks_introsort, which is not stable; here both are STABLE (equal keys keep their previous order).  A
+ * host that wants bwa's own order among equal re passes opt.presorted = 1 and what its ks_introsort left.  Of a full
+ * (score, rb, qb) tie the survivor may differ from bwa's in the fields outside the key (re, qe, w, seedcov, src, ...).
+ * The loop is sequential and needs alignment scores in the middle, so it is a resumable replay: the engine below (pure host,
+ * no context) asks for the mem_patch_reg pairs it needs as bsw_rd_ptask records, the patch tickets score them on the GPU, and a
+ * merge that a later pair depends on costs one more (small) round.  The engine never aligns anything itself.
+ * mem_sam_pe's second call after mate rescue (bns / pac / query NULL: mem_patch_reg returns 0 at once) is opt.patch = 0: no
+ * task, no GPU; sub / csub then carry values. ---- */
+typedef struct bsw_sreg {            /* the fields of mem_alnreg_t that mem_sort_dedup_patch reads or writes */
+    int64_t  rb, re;
+    int32_t  qb, qe, score, truesc, w, seedcov, sub, csub, rid, n_comp;
+    uint32_t read;
+    uint32_t src;                    /* output: the index in the caller's regs[] of the region this one WAS (the surviving p of its
+                                        merges): bwa's struct copy carries p's other fields (seedlen0, frac_rep, ...) along.  Input: ignored */
+} bsw_sreg;                          /* 64 bytes */
+typedef struct bsw_sdp_opt {
+    float   mask_level_redun;        /* .95f */
+    int32_t max_chain_gap;           /* 10000 */
+    int32_t patch;                   /* 1; 0: mem_patch_reg returns 0 (the call after mate rescue) */
+    int32_t presorted;               /* 0; 1: regs[] is sorted by re inside every read already, keep its order among equal re */
+} bsw_sdp_opt;                       /* 16 bytes */
+typedef struct bsw_sdp_stats {
+    uint64_t reads, regs_in, regs_out;
+    uint64_t merges;
+    uint64_t kills_p, kills_q;       /* regions excluded by the redundancy test: p (with the break), q */
+    uint64_t dups;                   /* removed behind the second sort: equal (score, rb, qb) */
+    uint64_t rounds;                 /* submits the block needed = the most any of its reads needed */
+    uint64_t tasks_first, tasks;     /* mem_patch_reg pairs sent in round 1 / in all rounds */
+    uint64_t alns_bwa;               /* mem_patch_reg calls that reach bwa_gen_cigar2 in bwa's sequential order */
+} bsw_sdp_stats;                     /* 88 bytes */
+void     bsw_sdp_default_opt(bsw_sdp_opt *o);
+/* regs[i] of bsw_chain2aln_finish as a bsw_sreg: sub = csub = 0, n_comp = 0, src = i.  BSW_E_INVAL for a NULL array with n > 0. */
+int      bsw_sdp_from_cregs(const bsw_creg *cregs, size_t n, bsw_sreg *sregs);
+/* The engine.  regs[n_regs] sorted by read with reg_start[n_reads + 1] (read r's regions are regs[reg_start[r], reg_start[r + 1]):
+ * what bsw_chain2aln_finish writes), lens[read] = l_query, p->w = opt->w of mem_patch_reg; opt == NULL: the defaults.  Everything
+ * is checked ONCE, by open, which names the first offender in err (may be NULL).  BSW_E_INVAL: a region with rb >= re, without
+ * 0 <= qb < qe <= lens[read] (qe == qb would read as "excluded"), w < 0, score <= 0, read not the one reg_start puts it in,
+ * reg_start not ascending from 0 to n_regs, presorted with a descending re; BSW_E_LIMIT: more than 2^32 - 1 regions.  The arrays
+ * are copied: the engine does not read them after open.
+ * bsw_sdp_needs advances every unfinished read as far as the scores it holds allow and returns the pairs it now needs (a = q,
+ * b = p; owned by the engine, valid until the next call); *n == 0: every read is finished.  The first call speculates: every
+ * pair (i, j) of the sorted UNMODIFIED regions down to which the descent's condition holds, that is not redundant, has
+ * q.rb < p.rb and passes bsw_patch_pretest.  A later call asks, per stalled read, for the pair it stalled on and for every
+ * further j' below it under the same four conditions on the current states, excluded regions skipped.  bsw_sdp_feed takes the
+ * results of exactly those tasks in that order (BSW_E_INVAL for another n).  A held result is used only when all twelve values
+ * of (a, b) equal the task's it was computed for; status 1 counts as 0.  One round for a block without merges, one more per
+ * merge that a later pair depends on; every round resolves at least one pair of every stalled read, so it ends.
+ * bsw_sdp_collect (once *n == 0 was returned, BSW_E_INVAL before): out[] (capacity n_regs), the reads in order, bwa's order inside
+ * a read; out_start[n_reads + 1] and stats may be NULL.  One engine belongs to one thread at a time; needs runs on the calling
+ * thread alone (what it costs: README). */
+typedef struct bsw_sdp_eng bsw_sdp_eng;
+int      bsw_sdp_open(const bsw_params *p, const bsw_sdp_opt *opt, int64_t l_pac, const bsw_sreg *regs, size_t n_regs, const uint64_t *reg_start,
+                      const int32_t *lens, size_t n_reads, bsw_sdp_eng **eng, char *err, size_t err_cap);
+int      bsw_sdp_needs(bsw_sdp_eng *eng, const bsw_rd_ptask **tasks, size_t *n);
+int      bsw_sdp_feed(bsw_sdp_eng *eng, const bsw_presult *res, size_t n);
+int      bsw_sdp_collect(bsw_sdp_eng *eng, bsw_sreg *out, size_t *n_out, uint64_t *out_start, bsw_sdp_stats *stats);
+void     bsw_sdp_close(bsw_sdp_eng *eng);
+/* The engine as ONE JOB around the patch tickets: start = open, the first needs, the tasks and results in DMA-able memory
+ * (bsw_host_alloc), bsw_patch_ref_submit_t (query = reads[read]) / bsw_patch_reads_submit_t.  While a round is in flight the job
+ * is one of the context's BSW_MAX_INFLIGHT submits and runs over every device of the context.  A failed start leaves *job NULL
+ * and queues nothing (a start with something to submit beside BSW_MAX_INFLIGHT submits: BSW_E_BUSY before anything is allocated);
+ * the text is in bsw_last_error.  With nothing to submit (patch = 0, no pair) the job is complete at once and holds no ticket.
+ * regs[], reg_start[], lens[] and the reads (the block) stay valid and unchanged until finish.
+ * bsw_sdp_test never waits for the GPU: when the round's ticket is complete it collects it, feeds the engine, takes the next
+ * needs and submits them; 1 = the engine has finished, 0 = not yet (also when the follow-up submit answered BSW_E_BUSY: the next
+ * call tries again), < 0 = the job has failed, and finish reports it.  bsw_sdp_finish does the same with bsw_wait_ticket until the
+ * engine has finished, writes bsw_sdp_collect's arrays and frees the job WHATEVER it returns (job == NULL: BSW_E_INVAL) — with one
+ * exception: when a follow-up round's submit answers BSW_E_BUSY (other threads hold the four places), finish returns BSW_E_BUSY
+ * with the job intact and a later finish or test continues there; waiting inside the library could deadlock a caller that
+ * itself holds the uncollected tickets.  bsw_sdp_job_stats: the counts so far of a job not yet finished.
+ * A pair that passes the pre-tests but exceeds BSW_GLOBAL_MAX_QLEN / BSW_MAX_TLEN fails the job with the patch submit's
+ * BSW_E_LIMIT; with the pre-tests' limits on w that needs a read beyond 8 191 bases.  The calls may come from several threads,
+ * one job from one thread at a time. */
+typedef struct bsw_sdp_job bsw_sdp_job;
+int      bsw_sdp_ref_start(bsw_ctx *ctx, const bsw_params *p, const bsw_sdp_opt *opt, const bsw_ref *ref, const uint8_t *const *reads,
+                           const int32_t *lens, size_t n_reads, const bsw_sreg *regs, size_t n_regs, const uint64_t *reg_start, bsw_sdp_job **job);
+int      bsw_sdp_reads_start(bsw_ctx *ctx, const bsw_params *p, const bsw_sdp_opt *opt, const bsw_ref *ref, const bsw_reads *rd,
+                             const bsw_sreg *regs, size_t n_regs, const uint64_t *reg_start, bsw_sdp_job **job);
+int      bsw_sdp_test(bsw_sdp_job *job);
+int      bsw_sdp_finish(bsw_sdp_job *job, bsw_sreg *out, size_t *n_out, uint64_t *out_start, bsw_sdp_stats *stats);
+int      bsw_sdp_job_stats(const bsw_sdp_job *job, bsw_sdp_stats *stats);
 
 /* ---- device sequence format: 4 bits per base, 16 bases per uint64, base k of a word in bits [4k,4k+3];
  * codes > 4 are stored as 4 (N).  words must hold (len+15)/16 entries.  Returns 1 if an N was seen. ---- */

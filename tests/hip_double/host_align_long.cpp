@@ -1,6 +1,6 @@
 /* host_align_long.cpp — the hosts of ksw_align2's long-query route (bsw_set_align_long: bsw_f4.hip, bsw_matesw.hip, bsw_align_long.hip)
  * on the host-memory HIP stand-in, as a stand-alone program per sanitizer (TEST INFRASTRUCTURE; built by
- * tests/_align_long_double_build.py, run by tests/test_align_long_double_cpu.py).
+ * its row in tests/_host_double_build.py, run by tests/test_align_long_double_cpu.py).
  *
  *   host_align_long gate      mode 0 refuses a query of more than 1 024 bases, modes 1 and 2 accept it, 8 192 bases are refused always;
  *                             which stand-in ran which task
@@ -26,24 +26,19 @@ uint64_t long_tasks();
 void reset();
 }  // namespace standin_alnl
 
-struct rng_t {
+/* this program's own generator (a 64-bit LCG's high bits): its stream defines the workloads, which the splitmix rng_t of
+ * host_common.h would change */
+struct lcg_t {
     uint64_t s;
-    explicit rng_t(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
+    explicit lcg_t(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 1) {}
     uint32_t next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33); }
     int below(int n) { return n > 0 ? (int)(next() % (uint32_t)n) : 0; }
 };
 
-static bsw_params default_params()
-{
-    bsw_params p;
-    bsw_default_params(&p);
-    return p;
-}
-
 struct awork {
     std::vector<std::vector<uint8_t>> q, tg;
     std::vector<bsw_atask> t;
-    void add(rng_t &r, int ql, int piece, int flank, int xtra)
+    void add(lcg_t &r, int ql, int piece, int flank, int xtra)
     {
         std::vector<uint8_t> qq((size_t)ql), tt;
         for (uint8_t &c : qq) c = (uint8_t)r.below(4);
@@ -84,7 +79,7 @@ static void same_as_oracle(const bsw_params &p, const std::vector<bsw_atask> &t,
 
 static const int XF = KSW_XSUBO | KSW_XSTART | 19;
 
-static void mixed(awork &w, rng_t &r, bool with_long)
+static void mixed(awork &w, lcg_t &r, bool with_long)
 {
     const int lens[] = {150, 1024, 1025, 1500, 3000, 8191};
     for (int rep = 0; rep < 2; ++rep)
@@ -97,12 +92,12 @@ static void mixed(awork &w, rng_t &r, bool with_long)
 }
 
 /* ---- a tiny genome for the rescue calls ---- */
-struct genome_t {
+struct lcg_genome_t {
     int64_t l_pac = 0;
     std::vector<uint8_t> bases, pac;
     void make(int64_t n, uint64_t seed)
     {
-        rng_t r(seed);
+        lcg_t r(seed);
         l_pac = n;
         bases.resize((size_t)n);
         pac.assign((size_t)(n / 4 + 1), 0);
@@ -122,7 +117,7 @@ struct genome_t {
 struct mwork {
     std::vector<std::vector<uint8_t>> mate;
     std::vector<bsw_mtask> t;
-    void add(const genome_t &g, rng_t &r, int l_ms, int is_rev, int strand, int xtra)
+    void add(const lcg_genome_t &g, lcg_t &r, int l_ms, int is_rev, int strand, int xtra)
     {
         const int wl = l_ms + 300;
         const int64_t rb = (strand ? g.l_pac : 0) + r.below((int)(g.l_pac - wl));
@@ -139,7 +134,7 @@ struct mwork {
     void finish() { for (size_t i = 0; i < t.size(); ++i) t[i].mate = mate[i].data(); }
 };
 
-static void same_rescue(const bsw_params &p, const genome_t &g, const mwork &w, const std::vector<bsw_mresult> &res, const char *what)
+static void same_rescue(const bsw_params &p, const lcg_genome_t &g, const mwork &w, const std::vector<bsw_mresult> &res, const char *what)
 {
     for (size_t i = 0; i < w.t.size(); ++i) {
         const bsw_mtask &t = w.t[i];
@@ -169,7 +164,7 @@ static int gate_mode()
     standin_alnl::reset();
     CHECK(bsw_align_long() == 0, "the switch starts at %d", bsw_align_long());
     {
-        rng_t r(5);
+        lcg_t r(5);
         awork all, shortw;
         mixed(all, r, true);
         mixed(shortw, r, false);
@@ -223,7 +218,7 @@ static int gate_mode()
         CHECK(memcmp(&k, want, sizeof(want)) == 0, "ksw_align under mode 1: score %d, the oracle's %d", k.score, want[0]);
         bsw_set_align_long(0);
         /* mate rescue, the batch call */
-        genome_t g;
+        lcg_genome_t g;
         g.make(40001, 3);
         bsw_ref *ref = nullptr;
         CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
@@ -251,7 +246,7 @@ static int split_mode()
     standin_alnl::reset();
     uint64_t sub = 0;
     {
-        rng_t r(7);
+        lcg_t r(7);
         awork w;
         /* 12 distinct tasks: nine tiny queries against 65 535-base targets with a b[] slice each, three long queries */
         for (int i = 0; i < 12; ++i) {
@@ -290,13 +285,13 @@ static int split_mode()
 static int flip_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    lcg_genome_t g;
     g.make(40001, 3);
     uint64_t chunks = 0;
     for (int mode = 1; mode <= 2; ++mode) {
         fresh(1);
         standin_alnl::reset();
-        rng_t r(11 + (uint64_t)mode);
+        lcg_t r(11 + (uint64_t)mode);
         mwork mw;
         for (int k = 0; k < 12; ++k) mw.add(g, r, mode == 1 ? (k % 3 == 0 ? 1025 : k % 3 == 1 ? 1500 : 3000) : 100 + 17 * k, k & 1, (k >> 1) & 1, XF | ((k & 4) ? KSW_XBYTE : 0));
         mw.finish();
@@ -335,76 +330,57 @@ static int flip_mode()
 static int faults_mode()
 {
     const bsw_params p = default_params();
-    uint64_t Csum = 0, failed = 0, ignored = 0, long_failed = 0;
+    uint64_t long_failed = 0;
+    sweep_t s;
+    s.releases = {"hipFree", "hipHostFree", "hipGetLastError"};
+    s.tickets = false;
+    s.exact = true;
     for (int reg = 0; reg < 2; ++reg) {                        /* both memory kinds: the gather and the direct branch */
         std::vector<bsw_kswr> clean;
-        uint64_t C = 0;
-        for (uint64_t k = 0;; ++k) {
-            bool made = true;
-            fresh(1);
-            {
-                rng_t r(31);
-                awork w;
-                mixed(w, r, true);
-                const size_t n = w.t.size();
-                uint8_t *arena = nullptr;
-                if (reg) {                                     /* one registered arena holds every sequence */
-                    size_t tot = 64;
-                    for (const bsw_atask &t : w.t) tot += (size_t)t.qlen + (size_t)t.tlen + 2;
-                    arena = (uint8_t *)bsw_host_alloc(tot);
-                    CHECK(arena, "bsw_host_alloc");
-                    size_t at = 0;
-                    for (bsw_atask &t : w.t) {
-                        memcpy(arena + at, t.query, (size_t)t.qlen); t.query = arena + at; at += (size_t)t.qlen + 1;
-                        memcpy(arena + at, t.target, (size_t)t.tlen); t.target = arena + at; at += (size_t)t.tlen + 1;
-                    }
+        fault_sweep(s, 1, [&](sweep_t &s) {
+            const unsigned long long k = s.k;
+            lcg_t r(31);
+            awork w;
+            mixed(w, r, true);
+            const size_t n = w.t.size();
+            uint8_t *arena = nullptr;
+            if (reg) {                                     /* one registered arena holds every sequence */
+                size_t tot = 64;
+                for (const bsw_atask &t : w.t) tot += (size_t)t.qlen + (size_t)t.tlen + 2;
+                arena = (uint8_t *)bsw_host_alloc(tot);
+                CHECK(arena, "bsw_host_alloc");
+                size_t at = 0;
+                for (bsw_atask &t : w.t) {
+                    memcpy(arena + at, t.query, (size_t)t.qlen); t.query = arena + at; at += (size_t)t.qlen + 1;
+                    memcpy(arena + at, t.target, (size_t)t.tlen); t.target = arena + at; at += (size_t)t.tlen + 1;
                 }
-                bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256, 2, 3000);
-                bsw_set_align_long(1);
-                std::vector<bsw_kswr> first(n), again(n);
-                memset(first.data(), 0, n * sizeof(bsw_kswr));
-                hipdbl::reset_counters();
-                if (k) hipdbl::fail_overall(k);
-                const int rc = bsw_align_batch(ctx, &p, w.t.data(), n, first.data());
-                const char *f = hipdbl::fired();
-                const std::string fname = f ? f : "";
-                hipdbl::clear_failures();
-                if (k == 0) {
-                    C = hipdbl::overall_calls();
-                    CHECK(rc == BSW_OK, "the clean call -> %d (%s)", rc, bsw_last_error(ctx));
-                    CHECK(hipdbl::calls("launch_align_long") >= 4, "the batch of the fault sweep makes %llu long launches", (unsigned long long)hipdbl::calls("launch_align_long"));
-                    same_as_oracle(p, w.t, first, n, "faults, clean");
-                    clean = first;
-                    Csum += C;
-                } else if (!f) {
-                    CHECK(k > C && rc == BSW_OK && memcmp(first.data(), clean.data(), n * sizeof(bsw_kswr)) == 0, "k=%llu: no failure happened and the results differ", (unsigned long long)k);
-                    made = false;
-                } else if (rc != BSW_OK) {
-                    ++failed;
-                    long_failed += fname == "launch_align_long";
-                    const char *msg = bsw_last_error(ctx);
-                    const bool alloc = fname == "hipMalloc" || fname == "hipHostMalloc";
-                    CHECK(rc == (alloc ? BSW_E_NOMEM : BSW_E_HIP), "k=%llu: %s failed and the call answered %d (%s)", (unsigned long long)k, fname.c_str(), rc, msg);
-                    CHECK(msg && *msg, "k=%llu: %s failed, the call answered %d without a text", (unsigned long long)k, fname.c_str(), rc);
-                } else {
-                    ++ignored;
-                    CHECK(fname == "hipFree" || fname == "hipHostFree" || fname == "hipGetLastError", "k=%llu: %s failed and the call reported success", (unsigned long long)k, fname.c_str());
-                    CHECK(memcmp(first.data(), clean.data(), n * sizeof(bsw_kswr)) == 0, "k=%llu: %s failed, the call reported success and its results differ", (unsigned long long)k, fname.c_str());
-                }
-                const int rc2 = bsw_align_batch(ctx, &p, w.t.data(), n, again.data());      /* the same call on the same context */
-                CHECK(rc2 == BSW_OK, "k=%llu (%s failed): the same call repeated -> %d (%s)", (unsigned long long)k, fname.c_str(), rc2, bsw_last_error(ctx));
-                CHECK(memcmp(again.data(), clean.data(), n * sizeof(bsw_kswr)) == 0, "k=%llu (%s failed): the same call repeated is not bit-exact", (unsigned long long)k, fname.c_str());
-                bsw_set_align_long(0);
-                bsw_destroy(ctx);
-                if (arena) bsw_host_free(arena);
             }
-            CHECK(hipdbl::live_objects() == 0, "k=%llu: %zu HIP objects left alive after bsw_destroy", (unsigned long long)k, hipdbl::live_objects());
-            if (!made) break;
-        }
+            bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256, 2, 3000);
+            bsw_set_align_long(1);
+            std::vector<bsw_kswr> first(n), again(n);
+            memset(first.data(), 0, n * sizeof(bsw_kswr));
+            s.arm();
+            const int rc = bsw_align_batch(ctx, &p, w.t.data(), n, first.data());
+            s.judge({{rc, rc ? bsw_last_error(ctx) : ""}});
+            if (k == 0) {
+                CHECK(hipdbl::calls("launch_align_long") >= 4, "the batch of the fault sweep makes %llu long launches", (unsigned long long)hipdbl::calls("launch_align_long"));
+                same_as_oracle(p, w.t, first, n, "faults, clean");
+                clean = first;
+            } else if (rc == BSW_OK)                           /* no failure happened, or that of a release */
+                CHECK(memcmp(first.data(), clean.data(), n * sizeof(bsw_kswr)) == 0, "k=%llu: %s failed, the call reported success and its results differ", k, s.fname.c_str());
+            else
+                long_failed += s.fname == "launch_align_long";
+            const int rc2 = bsw_align_batch(ctx, &p, w.t.data(), n, again.data());      /* the same call on the same context */
+            CHECK(rc2 == BSW_OK, "k=%llu (%s failed): the same call repeated -> %d (%s)", k, s.fname.c_str(), rc2, bsw_last_error(ctx));
+            CHECK(memcmp(again.data(), clean.data(), n * sizeof(bsw_kswr)) == 0, "k=%llu (%s failed): the same call repeated is not bit-exact", k, s.fname.c_str());
+            bsw_set_align_long(0);
+            bsw_destroy(ctx);
+            if (arena) bsw_host_free(arena);
+        });
     }
-    printf("faults: C = %llu, visited %llu, failed %llu, ignored %llu, long launches failed %llu\n", (unsigned long long)Csum, (unsigned long long)(failed + ignored),
-           (unsigned long long)failed, (unsigned long long)ignored, (unsigned long long)long_failed);
-    CHECK(failed + ignored == Csum, "visited %llu of %llu", (unsigned long long)(failed + ignored), (unsigned long long)Csum);
+    printf("faults: C = %llu, visited %llu, failed %llu, ignored %llu, long launches failed %llu\n", (unsigned long long)s.Csum, (unsigned long long)s.visited,
+           (unsigned long long)s.failed, (unsigned long long)s.ignored, (unsigned long long)long_failed);
+    s.done();
     return 0;
 }
 
@@ -417,7 +393,7 @@ static std::vector<std::string> call_names(int mode, uint64_t *total)
         fresh(1);
         bool made = true;
         {
-            rng_t r(41);
+            lcg_t r(41);
             awork w;
             mixed(w, r, false);
             const size_t n = w.t.size();

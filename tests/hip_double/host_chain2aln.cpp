@@ -1,6 +1,6 @@
 /* host_chain2aln.cpp — the mem_chain2aln job (bsw_chain2aln_ref_start / _reads_start / _test / _finish / _stats:
  * bsw_chain2aln_job.hip over bsw_chain2aln.c and bsw_batch.hip's pipeline) on the host-memory HIP stand-in, plain and under ASan /
- * UBSan or TSan (TEST INFRASTRUCTURE; tests/test_chain2aln_double_cpu.py builds it with tests/_chain2aln_double_build.py and runs it).
+ * UBSan or TSan (TEST INFRASTRUCTURE; tests/test_chain2aln_double_cpu.py builds it with its row in tests/_host_double_build.py and runs it).
  * A stand-alone program: nothing is preloaded, no GPU is opened.
  *
  * What the job must hand back is bsw_chain2aln_replay over the CPU oracle's records of the plan's tasks (the sequences cut on the
@@ -13,33 +13,8 @@
  *                           job; finish after a failed start; a plan failure and a submit failure from start
  *   host_chain2aln faults   every HIP / launcher call of a start .. finish of each form fails in turn; the job is freed
  */
-#include <algorithm>
 #include <climits>
-#include "host_common.h"
-
-struct rng_t {
-    uint64_t s;
-    explicit rng_t(uint64_t seed) : s(seed * 0x9e3779b97f4a7c15ull + 1) {}
-    uint64_t next() { uint64_t z = (s += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
-    int below(int n) { return (int)(next() % (uint64_t)n); }
-    int in(int lo, int hi) { return lo + below(hi - lo + 1); }           /* inclusive */
-    double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
-
-struct genome_t {
-    int64_t l_pac = 0;
-    std::vector<uint8_t> both, pac;
-    void make(int64_t n, uint64_t seed)
-    {
-        rng_t r(seed);
-        l_pac = n;
-        both.resize((size_t)(2 * n));
-        for (int64_t x = 0; x < n; ++x) both[(size_t)x] = (uint8_t)r.below(4);
-        for (int64_t x = n; x < 2 * n; ++x) both[(size_t)x] = (uint8_t)(3 - both[(size_t)(2 * n - 1 - x)]);
-        pac.assign((size_t)((n + 3) >> 2), 0);
-        for (int64_t x = 0; x < n; ++x) pac[(size_t)(x >> 2)] |= (uint8_t)(both[(size_t)x] << ((~x & 3) << 1));
-    }
-};
+#include "host_ref_patch.h"
 
 /* reads of 100 - 250 bases off both strands with substitutions; per read the true chain (its exact-match runs as seeds, long runs
  * cut in two), sometimes a thinned copy of it, sometimes a decoy chain; some chains carry a contig interval close around them */
@@ -190,18 +165,6 @@ static bsw_params params_of(int variant)
     bsw_default_params(&p);
     p.variant = variant;
     return p;
-}
-static bsw_ref *upload(bsw_ctx *ctx, const genome_t &g)
-{
-    bsw_ref *ref = nullptr;
-    CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK && ref, "bsw_ref_upload: %s", bsw_last_error(ctx));
-    return ref;
-}
-static bsw_reads *upload_reads(bsw_ctx *ctx, const cwork &w)
-{
-    bsw_reads *rd = nullptr;
-    CHECK(bsw_reads_upload(ctx, w.ptr.data(), w.len.data(), w.ptr.size(), &rd) == BSW_OK && rd, "bsw_reads_upload: %s", bsw_last_error(ctx));
-    return rd;
 }
 static int start_ref(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const cwork &w, bsw_c2a_job **j)
 {
@@ -373,79 +336,47 @@ static int faults_mode()
     genome_t g;
     g.make(70001, 5);
     const bsw_params p = params_of(BSW_VARIANT_H);
-    uint64_t visited = 0, failed = 0, ignored = 0, C = 0;
     rng_t r0(31);
     cwork w;
     make_chains(w, g, r0, 60);
     expect(w, g, p, false);
     CHECK(w.seeds.size() >= 3 * 128, "the workload: %zu seeds make fewer than three chunks", w.seeds.size());
-    for (uint64_t k = 0;; ++k) {
-        bool made = true;
-        fresh(2);
-        {
-            const size_t live0 = hipdbl::live_objects();
-            bsw_ctx *ctx = ctx_of(2, 128, BSW_RESULT_FULL, 4000, 1);
-            bsw_ref *ref = upload(ctx, g);
-            both_forms(ctx, p, ref, w, "the warm-up");
-            bsw_reads *rd = upload_reads(ctx, w);
-            hipdbl::reset_counters();
-            if (k) hipdbl::fail_overall(k);
-            bsw_c2a_job *j[2] = {nullptr, nullptr};
-            outs o0(w), o1(w);
-            int rc[2];
-            std::string text[2];
-            /* one job after the other: with both in flight the order of the two slots' calls would be the threads' */
-            for (int f = 0; f < 2; ++f) {
-                rc[f] = f ? start_reads(ctx, p, ref, rd, w, &j[f]) : start_ref(ctx, p, ref, w, &j[f]);
-                CHECK((rc[f] != 0) == (j[f] == nullptr), "k=%llu: start %d -> %d and job %p", (unsigned long long)k, f, rc[f], (void *)j[f]);
-                if (!rc[f]) rc[f] = finish(j[f], f ? o1 : o0);
-                if (rc[f]) text[f] = bsw_last_error(ctx);
-            }
-            const char *fn = hipdbl::fired();
-            const std::string fname = fn ? fn : "";
-            const uint64_t calls = hipdbl::overall_calls();
-            hipdbl::clear_failures();
-            if (rc[0] == BSW_OK) same_c(o0, w, "a pointer job that reported success");
-            if (rc[1] == BSW_OK) same_c(o1, w, "a reads job that reported success");
-            const int nfail = (rc[0] != 0) + (rc[1] != 0);
-            if (k == 0) {
-                C = calls;
-                CHECK(nfail == 0, "the clean scenario -> %d %d (%s)", rc[0], rc[1], bsw_last_error(ctx));
-                printf("faults: C = %llu\n", (unsigned long long)C);
-            } else if (!fn) {
-                CHECK(k == C + 1 && calls == C, "call %llu of the scenario was never made: this run made %llu calls, the clean one %llu", (unsigned long long)k, (unsigned long long)calls, (unsigned long long)C);
-                CHECK(nfail == 0, "k=%llu: no failure happened and a job failed", (unsigned long long)k);
-                made = false;
-            } else {
-                ++visited;
-                if (nfail) {
-                    ++failed;
-                    CHECK(nfail == 1, "k=%llu: %s failed once and %d jobs failed", (unsigned long long)k, fname.c_str(), nfail);
-                    const bool alloc = fname == "hipMalloc" || fname == "hipHostMalloc";
-                    for (int f = 0; f < 2; ++f)
-                        if (rc[f]) {
-                            CHECK(rc[f] == BSW_E_HIP || (alloc && rc[f] == BSW_E_NOMEM), "k=%llu: %s failed and job %d answered %d (%s)", (unsigned long long)k, fname.c_str(), f, rc[f], text[f].c_str());
-                            CHECK(!text[f].empty() && text[f].compare(0, 7, "aborted") != 0, "k=%llu: %s failed, job %d reports '%s'", (unsigned long long)k, fname.c_str(), f, text[f].c_str());
-                        }
-                } else {
-                    ++ignored;                       /* a release whose code is ignored by design */
-                    CHECK(fname == "hipFree" || fname == "hipHostFree" || fname == "hipGetLastError" || fname == "hipEventDestroy" || fname == "hipStreamDestroy" ||
-                          fname == "hipHostUnregister", "k=%llu: %s failed and every job reported success", (unsigned long long)k, fname.c_str());
-                }
-            }
-            /* both jobs are gone: no ticket, the block is free, and what they pinned is released */
-            CHECK(bsw_inflight(ctx) == 0, "k=%llu: tickets left", (unsigned long long)k);
-            CHECK(bsw_reads_free(ctx, rd) == BSW_OK, "k=%llu: bsw_reads_free after the jobs: %s", (unsigned long long)k, bsw_last_error(ctx));
-            /* the context is alive: both forms once more, exact */
-            both_forms(ctx, p, ref, w, "after the failure");
-            bsw_ref_free(ctx, ref);
-            bsw_destroy(ctx);
-            CHECK(hipdbl::live_objects() == live0, "k=%llu (%s failed): %zu HIP objects left alive after bsw_destroy", (unsigned long long)k, fname.c_str(), hipdbl::live_objects() - live0);
+    sweep_t s;
+    s.releases = {"hipFree", "hipHostFree", "hipGetLastError", "hipEventDestroy", "hipStreamDestroy", "hipHostUnregister"};      /* ignored by design */
+    s.exact = true;
+    s.min_failed = 30;
+    fault_sweep(s, 2, [&](sweep_t &s) {
+        const unsigned long long k = s.k;
+        bsw_ctx *ctx = ctx_of(2, 128, BSW_RESULT_FULL, 4000, 1);
+        bsw_ref *ref = upload(ctx, g);
+        both_forms(ctx, p, ref, w, "the warm-up");
+        bsw_reads *rd = upload_reads(ctx, w);
+        s.arm();
+        bsw_c2a_job *j[2] = {nullptr, nullptr};
+        outs o0(w), o1(w);
+        int rc[2];
+        std::string text[2];
+        /* one job after the other: with both in flight the order of the two slots' calls would be the threads' */
+        for (int f = 0; f < 2; ++f) {
+            rc[f] = f ? start_reads(ctx, p, ref, rd, w, &j[f]) : start_ref(ctx, p, ref, w, &j[f]);
+            CHECK((rc[f] != 0) == (j[f] == nullptr), "k=%llu: start %d -> %d and job %p", k, f, rc[f], (void *)j[f]);
+            if (!rc[f]) rc[f] = finish(j[f], f ? o1 : o0);
+            if (rc[f]) text[f] = bsw_last_error(ctx);
         }
-        if (!made) break;
-    }
-    printf("faults: injection points visited = %llu, a job failed %llu times, ignored %llu\n", (unsigned long long)visited, (unsigned long long)failed, (unsigned long long)ignored);
-    CHECK(visited == C && failed >= 30, "the sweep visited %llu of %llu calls, %llu failed", (unsigned long long)visited, (unsigned long long)C, (unsigned long long)failed);
+        s.judge({{rc[0], text[0]}, {rc[1], text[1]}});
+        if (rc[0] == BSW_OK) same_c(o0, w, "a pointer job that reported success");
+        if (rc[1] == BSW_OK) same_c(o1, w, "a reads job that reported success");
+        if (k == 0) printf("faults: C = %llu\n", (unsigned long long)s.C);
+        /* both jobs are gone: no ticket, the block is free, and what they pinned is released */
+        CHECK(bsw_inflight(ctx) == 0, "k=%llu: tickets left", k);
+        CHECK(bsw_reads_free(ctx, rd) == BSW_OK, "k=%llu: bsw_reads_free after the jobs: %s", k, bsw_last_error(ctx));
+        /* the context is alive: both forms once more, exact */
+        both_forms(ctx, p, ref, w, "after the failure");
+        bsw_ref_free(ctx, ref);
+        bsw_destroy(ctx);
+    });
+    printf("faults: injection points visited = %llu, a job failed %llu times, ignored %llu\n", (unsigned long long)s.visited, (unsigned long long)s.failed, (unsigned long long)s.ignored);
+    s.done();
     return 0;
 }
 

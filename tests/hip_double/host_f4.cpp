@@ -14,388 +14,7 @@
  * for mate rescue it writes inputs and results to FILE and the Python test compares them with tests/_gencigar_ref.reg2aln and
  * tests/_matesw_ref.matesw.
  */
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <climits>
-#include "host_common.h"
-#include "../../bwa-mem-sw_amd/csrc/bsw_f4_host.h"
-
-extern "C" void ksw_align2_ref(int qlen, const uint8_t *query, int tlen, const uint8_t *target, int m, const int8_t *mat, int o_del, int e_del,
-                               int o_ins, int e_ins, int xtra, int32_t *out, uint64_t *cells);
-
-struct rng_t {
-    uint64_t s;
-    explicit rng_t(uint64_t seed) : s(seed * 0x9e3779b97f4a7c15ull + 1) {}
-    uint64_t next() { uint64_t z = (s += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
-    int below(int n) { return (int)(next() % (uint64_t)n); }
-    int in(int lo, int hi) { return lo + below(hi - lo + 1); }           /* inclusive */
-    double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
-
-/* a genome and its 2-bit pac (bwa's layout: base x in bits ((~x & 3) << 1) of byte x >> 2) */
-struct genome_t {
-    int64_t l_pac = 0;
-    std::vector<uint8_t> bases, pac;
-    void make(int64_t n, uint64_t seed)
-    {
-        rng_t r(seed);
-        l_pac = n;
-        bases.resize((size_t)n);
-        for (auto &b : bases) b = (uint8_t)r.below(4);
-        pac.assign((size_t)((n + 3) >> 2), 0);
-        for (int64_t x = 0; x < n; ++x) pac[(size_t)(x >> 2)] |= (uint8_t)(bases[(size_t)x] << ((~x & 3) << 1));
-    }
-    /* bns_get_seq for an interval that lies on one strand */
-    std::vector<uint8_t> seq(int64_t rb, int64_t re) const
-    {
-        std::vector<uint8_t> out;
-        for (int64_t x = rb; x < re; ++x) out.push_back(x >= l_pac ? (uint8_t)(3 - bases[(size_t)(2 * l_pac - 1 - x)]) : bases[(size_t)x]);
-        return out;
-    }
-};
-
-static std::vector<uint8_t> mutate(rng_t &r, const std::vector<uint8_t> &src, double sub, double indel, double nrate = 0.0)
-{
-    std::vector<uint8_t> out;
-    for (size_t i = 0; i < src.size(); ++i) {
-        const double u = r.unit();
-        if (u < indel / 2) continue;                                       /* deletion from the read */
-        if (u < indel) out.push_back((uint8_t)r.below(4));                 /* insertion */
-        uint8_t b = src[i];
-        if (r.unit() < sub) b = (uint8_t)((b + 1 + r.below(3)) & 3);
-        if (nrate > 0 && r.unit() < nrate) b = 4;
-        out.push_back(b);
-    }
-    if (out.empty()) out.push_back(src.empty() ? 0 : src[0]);
-    return out;
-}
-
-static std::vector<uint8_t> revcomp(const std::vector<uint8_t> &s)
-{
-    std::vector<uint8_t> o(s.rbegin(), s.rend());
-    for (auto &c : o) c = c < 4 ? (uint8_t)(3 - c) : (uint8_t)4;
-    return o;
-}
-
-/* the caller's sequence bytes: one arena, registered (bsw_host_alloc: the hosts' `direct` branch) or pageable (the gather branch) */
-struct arena_t {
-    uint8_t *p = nullptr;
-    size_t cap = 0, at = 0;
-    bool registered = false;
-    arena_t(size_t bytes, bool reg) : cap(bytes + 64), registered(reg)
-    {
-        p = (uint8_t *)(reg ? bsw_host_alloc(cap) : malloc(cap));
-        CHECK(p, "arena of %zu bytes", cap);
-        memset(p, 0, cap);
-    }
-    ~arena_t() { if (registered) bsw_host_free(p); else free(p); }
-    arena_t(const arena_t &) = delete;
-    const uint8_t *put(const std::vector<uint8_t> &s)
-    {
-        CHECK(at + s.size() <= cap, "arena full");
-        uint8_t *q = p + at;
-        if (!s.empty()) memcpy(q, s.data(), s.size());
-        at += s.size();
-        return q;
-    }
-};
-
-static bsw_params default_params()
-{
-    bsw_params p;
-    bsw_default_params(&p);
-    return p;
-}
-
-static std::string digits(const uint8_t *s, int n)
-{
-    std::string o;
-    for (int i = 0; i < n; ++i) o += (char)('0' + s[i]);
-    return o.empty() ? "-" : o;
-}
-
-static void write_genome(FILE *f, const genome_t &g, const bsw_params &p)
-{
-    fprintf(f, "genome %lld ", (long long)g.l_pac);
-    for (uint8_t b : g.pac) fprintf(f, "%02x", b);
-    fprintf(f, "\nparams");
-    for (int i = 0; i < 25; ++i) fprintf(f, " %d", p.mat[i]);
-    fprintf(f, " %d %d %d %d\n", p.o_del, p.e_del, p.o_ins, p.e_ins);
-}
-
-/* ---- global ---- */
-struct gwork {
-    std::vector<bsw_gtask> t;
-    std::vector<std::vector<uint8_t>> q, tg;
-};
-
-static const int G_LONG[] = {63, 64, 127, 128, 255, 256, 400, 511, 512, 700, 1023, 1024, 1100, 1500};
-
-static void make_global(gwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) {
-        int tl = (i % 23 == 5) ? G_LONG[(i / 23) % (sizeof(G_LONG) / sizeof(int))] : r.in(1, 62);
-        const int64_t at = r.below((int)(g.l_pac - tl - 1));
-        std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl);
-        std::vector<uint8_t> q = mutate(r, tg, 0.05, tl > 300 ? 0.01 : 0.04, 0.01);
-        if (tl > 62 && (int)q.size() != tl && tl != 400 && tl != 700 && tl != 1100 && tl != 1500) q.resize((size_t)tl, 1);   /* (class edges: the query length decides) */
-        w.q.push_back(q);
-        w.tg.push_back(tg);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        bsw_gtask t;
-        memset(&t, 0, sizeof(t));
-        t.qlen = (int)w.q[i].size(); t.tlen = (int)w.tg[i].size();
-        t.query = ar.put(w.q[i]); t.target = ar.put(w.tg[i]);
-        const int d = abs(t.qlen - t.tlen);
-        t.w = d + 3 + (int)(i % 17);
-        if (t.tlen == 1100) t.w = 200;                                    /* ring classes 0 (narrow bands), 1 (n_col 401) and 3 (1201) */
-        if (t.tlen == 1500) t.w = 600;
-        w.t.push_back(t);
-    }
-}
-
-static void check_global(bsw_ctx *ctx, const bsw_params &p, const gwork &w, int max_cigar, bool want_cigar, const char *what)
-{
-    const size_t n = w.t.size();
-    std::vector<bsw_gresult> res(n + 1);
-    std::vector<uint32_t> cig(n * (size_t)max_cigar + 1, 0xdeadbeefu);
-    memset(res.data(), 0x5a, res.size() * sizeof(bsw_gresult));
-    const int rc = bsw_global_batch(ctx, &p, w.t.data(), n, max_cigar, res.data(), want_cigar ? cig.data() : nullptr);
-    CHECK(rc == BSW_OK, "%s: bsw_global_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
-    for (size_t i = 0; i < n; ++i) {
-        int nc = 0;
-        uint32_t *cg = nullptr;
-        const int score = ksw_global2_ref(w.t[i].qlen, w.q[i].data(), w.t[i].tlen, w.tg[i].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, w.t[i].w, &nc, &cg, nullptr);
-        CHECK(res[i].score == score, "%s: task %zu of %zu (%d x %d, w %d): score %d, the oracle's %d", what, i, n, w.t[i].qlen, w.t[i].tlen, w.t[i].w, res[i].score, score);
-        if (want_cigar) {
-            CHECK(res[i].n_cigar == (nc <= max_cigar ? nc : -nc), "%s: task %zu of %zu: n_cigar %d, the oracle's %d (room %d)", what, i, n, res[i].n_cigar, nc, max_cigar);
-            if (nc <= max_cigar)
-                for (int k = 0; k < nc; ++k) CHECK(cig[i * (size_t)max_cigar + (size_t)k] == cg[k], "%s: task %zu of %zu: CIGAR word %d differs", what, i, n, k);
-        } else
-            CHECK(res[i].n_cigar == 0, "%s: task %zu: n_cigar %d without a CIGAR buffer", what, i, res[i].n_cigar);
-        free(cg);
-    }
-}
-
-/* ---- local alignment ---- */
-struct awork {
-    std::vector<bsw_atask> t;
-    std::vector<std::vector<uint8_t>> q, tg;
-};
-
-static const int A_LONG[] = {128, 129, 160, 161, 256, 257, 512, 513, 1024};
-
-static int xtra_for(size_t i, int qlen)
-{
-    int x = (i & 1) ? KSW_XBYTE : 0;
-    if (i % 5 != 4) x |= KSW_XSUBO | (qlen > 30 ? 19 : 3);
-    if (i % 3 != 2) x |= KSW_XSTART;
-    if (i % 11 == 10) x = (x & KSW_XBYTE) | KSW_XSTOP | 12;
-    return x;
-}
-
-static void make_align(awork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) {
-        const int ql = (i % 19 == 3) ? A_LONG[(i / 19) % (sizeof(A_LONG) / sizeof(int))] : r.in(1, 128);
-        const int tl = ql + r.in(0, 200);
-        const int64_t at = r.below((int)(g.l_pac - tl - 1));
-        std::vector<uint8_t> tg(g.bases.begin() + at, g.bases.begin() + at + tl);
-        const int off = r.below(tl - ql + 1);
-        std::vector<uint8_t> piece(tg.begin() + off, tg.begin() + off + ql);
-        std::vector<uint8_t> q = mutate(r, piece, 0.05, 0.02, 0.01);
-        q.resize((size_t)ql, 2);
-        if (i % 7 == 0 && tl >= 2 * ql + 4) std::copy(piece.begin(), piece.end(), tg.begin() + (tl - ql));       /* a planted repeat: score2 */
-        w.q.push_back(q);
-        w.tg.push_back(tg);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        bsw_atask t;
-        memset(&t, 0, sizeof(t));
-        t.qlen = (int)w.q[i].size(); t.tlen = (int)w.tg[i].size();
-        t.query = ar.put(w.q[i]); t.target = ar.put(w.tg[i]);
-        t.xtra = xtra_for(i, t.qlen);
-        w.t.push_back(t);
-    }
-}
-
-static void check_align(bsw_ctx *ctx, const bsw_params &p, const awork &w, const char *what)
-{
-    const size_t n = w.t.size();
-    std::vector<bsw_kswr> res(n + 1);
-    memset(res.data(), 0x5a, res.size() * sizeof(bsw_kswr));
-    const int rc = bsw_align_batch(ctx, &p, w.t.data(), n, res.data());
-    CHECK(rc == BSW_OK, "%s: bsw_align_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
-    for (size_t i = 0; i < n; ++i) {
-        int32_t want[7];
-        ksw_align2_ref(w.t[i].qlen, w.q[i].data(), w.t[i].tlen, w.tg[i].data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, w.t[i].xtra, want, nullptr);
-        CHECK(memcmp(&res[i], want, sizeof(want)) == 0, "%s: task %zu of %zu (%d x %d, xtra 0x%x): score %d te %d qe %d score2 %d te2 %d tb %d qb %d, the oracle's %d %d %d %d %d %d %d",
-              what, i, n, w.t[i].qlen, w.t[i].tlen, (unsigned)w.t[i].xtra, res[i].score, res[i].te, res[i].qe, res[i].score2, res[i].te2, res[i].tb, res[i].qb,
-              want[0], want[1], want[2], want[3], want[4], want[5], want[6]);
-    }
-}
-
-/* ---- bwa_gen_cigar2 on the resident reference ---- */
-struct cwork {
-    std::vector<bsw_ctask> t;
-    std::vector<std::vector<uint8_t>> q;
-};
-
-/* a read of [rb, re) (in the strand's own order) whose path leaves the diagonal by `off` bases between two indels */
-static std::vector<uint8_t> offset_read(rng_t &r, const std::vector<uint8_t> &rs, int off)
-{
-    std::vector<uint8_t> o(rs.begin(), rs.begin() + 40);
-    o.insert(o.end(), rs.begin() + 40 + off, rs.begin() + 100);            /* a deletion of `off` bases ... */
-    for (int k = 0; k < off; ++k) o.push_back((uint8_t)r.below(4));        /* ... and an insertion of as many */
-    o.insert(o.end(), rs.begin() + 100, rs.end());
-    return o;
-}
-
-static void make_cigar(cwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
-{
-    const int64_t L = g.l_pac;
-    for (size_t i = 0; i < n; ++i) {
-        bsw_ctask t;
-        memset(&t, 0, sizeof(t));
-        t.min_score = INT_MIN; t.max_tries = 1; t.w = 100;
-        const int kind = (int)(i % 13);
-        const bool rev = (i / 13) % 2 == 1;
-        int rl = r.in(60, 150);
-        if (kind == 11) rl = (i % 3 == 0) ? 1100 : r.in(200, 600);
-        if (kind >= 7 && kind <= 9) rl = 150;
-        int64_t rb = (rev ? L : 0) + r.below((int)(L - rl - 1));
-        int64_t re = rb + rl;
-        std::vector<uint8_t> q;
-        if (kind == 2) { rb = L - 30; re = L + 40; q = g.seq(100, 170); }                 /* bridges l_pac: status 1 */
-        else if (kind == 3) { re = rb - (i % 2); q = g.seq(100, 170); }                   /* empty interval: status 1 */
-        else if (kind == 4) {
-            if (i % 2) { rb = 2 * L - 20; re = 2 * L + 30; q = g.seq(100, 150); }         /* leaves [0, 2 l_pac): status 1 */
-            else q.clear();                                                              /* an empty read: status 1 */
-        } else {
-            const std::vector<uint8_t> rs = g.seq(rb, re);                               /* (reverse strand: bwa reverses both) */
-            std::vector<uint8_t> fw;
-            if (kind == 5 || kind == 6) {                                                /* the no-gap shortcut */
-                fw = mutate(r, rs, kind == 6 ? 0.2 : 0.03, 0.0, 0.01);
-                fw.resize(rs.size(), 0);
-                t.w = 0;
-                if (kind == 6) { t.w_cap = 50; t.max_tries = 2 + (int)(i % 2); t.min_score = (i % 4 < 2) ? rl : -1000; }
-            } else if (kind >= 7 && kind <= 9) {                                         /* retries: 1, 2 and 3 tries */
-                const std::vector<uint8_t> rr = rev ? std::vector<uint8_t>(rs.rbegin(), rs.rend()) : rs;
-                std::vector<uint8_t> o = offset_read(r, rr, kind == 7 ? 2 : kind == 8 ? 4 : 8);
-                fw = rev ? std::vector<uint8_t>(o.rbegin(), o.rend()) : o;
-                t.w = 2; t.w_cap = 64; t.max_tries = 3; t.min_score = 100;
-                if (i % 5 == 0) t.max_tries = 2;
-            } else
-                fw = mutate(r, rs, 0.03, kind == 10 ? 0.06 : 0.01, kind == 1 ? 0.02 : 0.0);
-            /* a reverse-strand read arrives in READ order: the reverse of what aligns to bns_get_seq(rb, re) reversed */
-            q = fw;
-            if ((kind == 0 || kind == 12) && i % 4 == 0) t.w = 5;
-        }
-        w.q.push_back(q);
-        t.l_query = (int)q.size(); t.rb = rb; t.re = re;
-        w.t.push_back(t);
-    }
-    for (size_t i = 0; i < n; ++i) w.t[i].query = w.q[i].empty() ? nullptr : ar.put(w.q[i]);
-}
-
-static void run_cigar(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const cwork &w, int max_cigar, int max_md, bool want_cigar, bool want_md,
-                      FILE *f, const char *what, size_t emit_first = SIZE_MAX, std::vector<bsw_cresult> *res_out = nullptr,
-                      std::vector<uint32_t> *cig_out = nullptr, std::vector<char> *md_out = nullptr)
-{
-    const size_t n = w.t.size();
-    std::vector<bsw_cresult> res(n + 1);
-    std::vector<uint32_t> cig(n * (size_t)max_cigar + 1, 0xdeadbeefu);
-    std::vector<char> md(n * (size_t)max_md + 1, '#');
-    memset(res.data(), 0x5a, res.size() * sizeof(bsw_cresult));
-    const int rc = bsw_cigar_ref_batch(ctx, &p, ref, w.t.data(), n, max_cigar, want_cigar ? cig.data() : nullptr, max_md, want_md ? md.data() : nullptr, res.data());
-    CHECK(rc == BSW_OK, "%s: bsw_cigar_ref_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
-    CHECK(cig[n * (size_t)max_cigar] == 0xdeadbeefu && md[n * (size_t)max_md] == '#', "%s: a write behind the caller's arrays", what);
-    if (f) {
-        const size_t m = std::min(n, emit_first);
-        fprintf(f, "cigarcase %zu %d %d %d %d %s\n", m, max_cigar, max_md, want_cigar ? 1 : 0, want_md ? 1 : 0, what);
-        for (size_t i = 0; i < m; ++i) {
-            const bsw_ctask &t = w.t[i];
-            const bsw_cresult &r = res[i];
-            fprintf(f, "c %s %lld %lld %d %d %d %d | %d %d %d %d %d %d %d %d |", digits(t.query, t.l_query).c_str(), (long long)t.rb, (long long)t.re, t.w, t.w_cap,
-                    t.min_score, t.max_tries, r.score, r.n_cigar, r.nm, r.md_len, r.w, r.tries, r.status, r._pad);
-            if (want_cigar)
-                for (int k = 0; k < r.n_cigar && k < max_cigar; ++k) fprintf(f, " %u", cig[i * (size_t)max_cigar + (size_t)k]);
-            fprintf(f, " | ");
-            if (want_md) {
-                const char *s = md.data() + i * (size_t)max_md;
-                CHECK(memchr(s, 0, (size_t)max_md) != nullptr, "%s: task %zu: the MD slot holds no NUL", what, i);
-                fprintf(f, "%s", *s ? s : "-");
-            } else
-                fprintf(f, "?");
-            fprintf(f, "\n");
-        }
-    }
-    if (res_out) *res_out = res;
-    if (cig_out) *cig_out = cig;
-    if (md_out) *md_out = md;
-}
-
-/* ---- mate rescue ---- */
-struct mwork {
-    std::vector<bsw_mtask> t;
-    std::vector<std::vector<uint8_t>> m;
-};
-
-static void make_matesw(mwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t n)
-{
-    const int64_t L = g.l_pac;
-    for (size_t i = 0; i < n; ++i) {
-        bsw_mtask t;
-        memset(&t, 0, sizeof(t));
-        const int kind = (int)(i % 11);
-        const bool strand = (i / 11) % 2 == 1;
-        const int lm = (i % 19 == 3) ? A_LONG[(i / 19) % (sizeof(A_LONG) / sizeof(int))] : r.in(8, 150);
-        const int tl = lm + r.in(20, 400);
-        int64_t rb = (strand ? L : 0) + r.below((int)(L - tl - 1)), re = rb + tl;
-        t.is_rev = (int)(i % 2);
-        std::vector<uint8_t> win = g.seq(rb, re);
-        const int off = r.below(tl - lm + 1);
-        std::vector<uint8_t> piece(win.begin() + off, win.begin() + off + lm);
-        std::vector<uint8_t> aligned = mutate(r, piece, kind == 9 ? 0.4 : 0.04, 0.02, 0.01);
-        aligned.resize((size_t)lm, 1);
-        std::vector<uint8_t> ms = t.is_rev ? revcomp(aligned) : aligned;   /* the mate in read order */
-        if (kind == 2) { rb = L - 50; re = L + 60; }                       /* bridges l_pac */
-        if (kind == 3) re = rb;                                           /* empty window */
-        if (kind == 4 && i % 2) { rb = 2 * L - 40; re = 2 * L + 10; }      /* leaves [0, 2 l_pac) */
-        if (kind == 4 && !(i % 2)) ms.clear();                             /* empty mate */
-        t.xtra = KSW_XSUBO | KSW_XSTART | (i % 3 ? KSW_XBYTE : 0) | (i % 4 == 0 ? 5 : 19);
-        if (i % 13 == 7) t.xtra &= ~KSW_XSUBO;
-        t.min_score = i % 6 == 0 ? 60 : 19;
-        t.l_ms = (int)ms.size(); t.rb = rb; t.re = re;
-        w.m.push_back(ms);
-        w.t.push_back(t);
-    }
-    for (size_t i = 0; i < n; ++i) w.t[i].mate = w.m[i].empty() ? nullptr : ar.put(w.m[i]);
-}
-
-static void run_matesw(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const mwork &w, FILE *f, const char *what, size_t emit_first = SIZE_MAX,
-                       std::vector<bsw_mresult> *res_out = nullptr)
-{
-    const size_t n = w.t.size();
-    std::vector<bsw_mresult> res(n + 1);
-    memset(res.data(), 0x5a, res.size() * sizeof(bsw_mresult));
-    const int rc = bsw_matesw_ref_batch(ctx, &p, ref, w.t.data(), n, res.data());
-    CHECK(rc == BSW_OK, "%s: bsw_matesw_ref_batch -> %d (%s)", what, rc, bsw_last_error(ctx));
-    if (f) {
-        const size_t m = std::min(n, emit_first);
-        fprintf(f, "matecase %zu %s\n", m, what);
-        for (size_t i = 0; i < m; ++i) {
-            const bsw_mtask &t = w.t[i];
-            const bsw_mresult &r = res[i];
-            fprintf(f, "m %s %d %lld %lld %d %d | %d %d %d %d %d %d %d | %d %lld %lld %d %d %d %d %d %d\n", digits(t.mate, t.l_ms).c_str(), t.is_rev, (long long)t.rb,
-                    (long long)t.re, t.xtra, t.min_score, r.aln.score, r.aln.te, r.aln.qe, r.aln.score2, r.aln.te2, r.aln.tb, r.aln.qb, r.status, (long long)r.rb,
-                    (long long)r.re, r.qb, r.qe, r.score, r.csub, r.seedcov, r._pad);
-        }
-    }
-    if (res_out) *res_out = res;
-}
+#include "host_f4_work.h"
 
 /* ---- f4: parity over n x memory kind ---- */
 static const size_t F4_NS[] = {0, 1, 63, 64, 65, 2600};
@@ -405,7 +24,7 @@ static int f4_mode(const char *path)
     FILE *f = fopen(path, "w");
     CHECK(f, "cannot write %s", path);
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(150001, 77);
     write_genome(f, g, p);
     size_t cases = 0;
@@ -557,7 +176,7 @@ static void matesw_split(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, mwork 
 }
 
 /* D distinct tiny tasks, D odd, neighbours of different lengths */
-static void tiny_global(gwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D)
+static void tiny_global(gwork &w, arena_t &ar, const genome1_t &g, rng_t &r, size_t D)
 {
     for (size_t i = 0; i < D; ++i) {
         const int ql = 1 + (int)((i * 3) % 8), tl = 1 + (int)((i * 5 + 2) % 10);
@@ -575,7 +194,7 @@ static void tiny_global(gwork &w, arena_t &ar, const genome_t &g, rng_t &r, size
     }
 }
 
-static void tiny_align(awork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D, int tlen_fixed, int no_subo_every)
+static void tiny_align(awork &w, arena_t &ar, const genome1_t &g, rng_t &r, size_t D, int tlen_fixed, int no_subo_every)
 {
     for (size_t i = 0; i < D; ++i) {
         const int ql = 1 + (int)((i * 3) % 8), tl = tlen_fixed ? tlen_fixed - (int)(i % 2) * 7 : 9 + (int)((i * 7) % 30);
@@ -596,7 +215,7 @@ static void tiny_align(awork &w, arena_t &ar, const genome_t &g, rng_t &r, size_
     }
 }
 
-static void tiny_cigar(cwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D)
+static void tiny_cigar(cwork &w, arena_t &ar, const genome1_t &g, rng_t &r, size_t D)
 {
     const int64_t L = g.l_pac;
     for (size_t i = 0; i < D; ++i) {
@@ -620,7 +239,7 @@ static void tiny_cigar(cwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_
     for (size_t i = 0; i < D; ++i) w.t[i].query = ar.put(w.q[i]);
 }
 
-static void tiny_matesw(mwork &w, arena_t &ar, const genome_t &g, rng_t &r, size_t D, int tlen_fixed, int no_subo_every)
+static void tiny_matesw(mwork &w, arena_t &ar, const genome1_t &g, rng_t &r, size_t D, int tlen_fixed, int no_subo_every)
 {
     const int64_t L = g.l_pac;
     for (size_t i = 0; i < D; ++i) {
@@ -650,7 +269,7 @@ static int f4split_mode(const std::string &which, const char *path)
     FILE *f = fopen(path, "w");
     CHECK(f, "cannot write %s", path);
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(which == "b" ? 700001 : 150001, 91);
     write_genome(f, g, p);
     uint64_t sub[4] = {0, 0, 0, 0};
@@ -722,7 +341,7 @@ static int f4split_mode(const std::string &which, const char *path)
 static int f4scalar_mode()
 {
     fresh(1);
-    genome_t g;
+    genome1_t g;
     g.make(60001, 5);
     const int T = 12, ROUNDS = 40;
     struct scoring { int8_t mat[25]; int od, ed, oi, ei; };
@@ -831,17 +450,17 @@ struct f4_outputs {
 static int f4faults_mode(const std::string &call)
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(90001, 13);
     const size_t n = 180;
-    uint64_t Csum = 0, failed = 0, ignored = 0;
+    sweep_t s;
+    s.releases = {"hipFree", "hipHostFree", "hipGetLastError"};        /* releases whose return code is ignored by design */
+    s.tickets = false;
+    s.exact = true;
     for (int reg = 0; reg < 2; ++reg) {                        /* both memory kinds: the gather and the direct branch */
-    f4_outputs clean;
-    uint64_t C = 0;
-    for (uint64_t k = 0;; ++k) {
-        bool made = true;
-        fresh(1);
-        {
+        f4_outputs clean;
+        fault_sweep(s, 1, [&](sweep_t &s) {
+            const unsigned long long k = s.k;
             rng_t r(31);
             arena_t ar(n * 900 + 8192, reg != 0);
             gwork gw; awork aw; cwork cw; mwork mw;
@@ -851,8 +470,7 @@ static int f4faults_mode(const std::string &call)
             else if (call == "matesw") make_matesw(mw, ar, g, r, n);
             else CHECK(false, "faults global|align|cigar|matesw");
             bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256, 2, 3000);
-            bsw_ref *ref = nullptr;
-            CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
+            bsw_ref *ref = upload(ctx, g);
             auto run = [&](f4_outputs &o) {
                 o = f4_outputs();
                 if (call == "global") { o.g.assign(n, bsw_gresult{0, 0}); o.gc.assign(n * 48, 0); return bsw_global_batch(ctx, &p, gw.t.data(), n, 48, o.g.data(), o.gc.data()); }
@@ -864,52 +482,30 @@ static int f4faults_mode(const std::string &call)
                 o.m.resize(n); memset(o.m.data(), 0, n * sizeof(bsw_mresult));
                 return bsw_matesw_ref_batch(ctx, &p, ref, mw.t.data(), n, o.m.data());
             };
-            hipdbl::reset_counters();
-            if (k) hipdbl::fail_overall(k);
+            s.arm();
             f4_outputs first, again;
             const int rc = run(first);
-            const char *f = hipdbl::fired();
-            const std::string fname = f ? f : "";
-            hipdbl::clear_failures();
+            s.judge({{rc, rc ? bsw_last_error(ctx) : ""}});
             if (k == 0) {
-                C = hipdbl::overall_calls();
-                CHECK(rc == BSW_OK, "the clean %s call -> %d (%s)", call.c_str(), rc, bsw_last_error(ctx));
                 clean = first;
                 if (call == "cigar") {
                     int two = 0;
                     for (const bsw_cresult &c : clean.c) two += c.tries >= 2 && c.status == 0;
                     CHECK(two >= 10 && hipdbl::calls("launch_global") + hipdbl::calls("launch_global_long") >= 3, "the cigar batch of the fault sweep needs no second try");
                 }
-                Csum += C;
-                printf("faults %s, %s memory: C = %llu\n", call.c_str(), reg ? "registered" : "pageable", (unsigned long long)C);
-            } else if (!f) {
-                CHECK(k > C, "call %llu of the %s batch was never made (C = %llu)", (unsigned long long)k, call.c_str(), (unsigned long long)C);
-                CHECK(rc == BSW_OK && first == clean, "k=%llu: no failure happened and the results differ", (unsigned long long)k);
-                made = false;
-            } else if (rc != BSW_OK) {
-                ++failed;
-                const char *msg = bsw_last_error(ctx);
-                const bool alloc = fname == "hipMalloc" || fname == "hipHostMalloc";
-                CHECK(rc == (alloc ? BSW_E_NOMEM : BSW_E_HIP), "k=%llu: %s failed and the %s call answered %d (%s)", (unsigned long long)k, fname.c_str(), call.c_str(), rc, msg);
-                CHECK(msg && *msg, "k=%llu: %s failed, the call answered %d without a text", (unsigned long long)k, fname.c_str(), rc);
-            } else {
-                ++ignored;                                     /* (a release whose return code is ignored by design) */
-                CHECK(fname == "hipFree" || fname == "hipHostFree" || fname == "hipGetLastError", "k=%llu: %s failed and the %s call reported success", (unsigned long long)k, fname.c_str(), call.c_str());
-                CHECK(first == clean, "k=%llu: %s failed, the call reported success and its results differ", (unsigned long long)k, fname.c_str());
-            }
+                printf("faults %s, %s memory: C = %llu\n", call.c_str(), reg ? "registered" : "pageable", (unsigned long long)s.C);
+            } else if (rc == BSW_OK)                           /* no failure happened, or that of a release */
+                CHECK(first == clean, "k=%llu: %s failed, the call reported success and its results differ", k, s.fname.c_str());
             const int rc2 = run(again);                         /* the same call on the same context */
-            CHECK(rc2 == BSW_OK, "k=%llu (%s failed): the same call repeated -> %d (%s)", (unsigned long long)k, fname.c_str(), rc2, bsw_last_error(ctx));
-            CHECK(again == clean, "k=%llu (%s failed): the same call repeated is not bit-exact", (unsigned long long)k, fname.c_str());
+            CHECK(rc2 == BSW_OK, "k=%llu (%s failed): the same call repeated -> %d (%s)", k, s.fname.c_str(), rc2, bsw_last_error(ctx));
+            CHECK(again == clean, "k=%llu (%s failed): the same call repeated is not bit-exact", k, s.fname.c_str());
             bsw_ref_free(ctx, ref);
             bsw_destroy(ctx);
-        }
-        CHECK(hipdbl::live_objects() == 0, "k=%llu: %zu HIP objects left alive after bsw_destroy", (unsigned long long)k, hipdbl::live_objects());
-        if (!made) break;
+        });
     }
-    }
-    printf("faults %s: C = %llu, injection points visited = %llu, failed calls %llu, ignored releases %llu, skipped 0\n", call.c_str(), (unsigned long long)Csum,
-           (unsigned long long)(failed + ignored), (unsigned long long)failed, (unsigned long long)ignored);
-    CHECK(failed + ignored == Csum, "visited %llu of %llu", (unsigned long long)(failed + ignored), (unsigned long long)Csum);
+    printf("faults %s: C = %llu, injection points visited = %llu, failed calls %llu, ignored releases %llu, skipped 0\n", call.c_str(), (unsigned long long)s.Csum,
+           (unsigned long long)s.visited, (unsigned long long)s.failed, (unsigned long long)s.ignored);
+    s.done();
     return 0;
 }
 
@@ -996,7 +592,7 @@ static int cuts_mode()
 static int rejects_mode()
 {
     fresh(1);
-    genome_t g;
+    genome1_t g;
     g.make(40001, 9);
     rng_t r(4242);
     bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256);

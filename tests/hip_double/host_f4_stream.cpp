@@ -11,116 +11,17 @@
  *   host_f4_stream watchdog   a stalled stream under a short timeout: BSW_E_HIP, the context is dead
  *
  * The workloads are those the synchronous calls are tested with: this file takes make_cigar / make_matesw, the genome and the
- * arena from host_f4.cpp (included below with its main() renamed), so a kind, strand or retry count added there is run here too.
+ * arena from host_f4_work.h, as host_f4.cpp does, so a kind, strand or retry count added there is run here too.
  * The expected values are the synchronous calls' results, which tests/test_host_double_cpu.py compares with the restatements of
  * bwa (tests/_gencigar_ref.py, tests/_matesw_ref.py) on the same workloads.
  */
-#define main host_f4_main
-#include "host_f4.cpp"
-#undef main
-
-static const int MAXC = 64, MAXMD = 512;
-
-struct c_out {
-    std::vector<bsw_cresult> res;
-    std::vector<uint32_t> cig;
-    std::vector<char> md;
-    void init(size_t n)
-    {
-        res.resize(n + 1); cig.assign(n * MAXC + 1, 0xdeadbeefu); md.assign(n * MAXMD + 1, '#');
-        memset(res.data(), 0x5a, res.size() * sizeof(bsw_cresult));
-    }
-};
-
-/* every byte of the result records (the _pad fields included), the CIGAR words a result announces, the MD strings */
-static bool same_c(const c_out &a, const c_out &b, size_t n, std::string *why = nullptr)
-{
-    char buf[160];
-    for (size_t i = 0; i < n; ++i) {
-        if (memcmp(&a.res[i], &b.res[i], sizeof(bsw_cresult)) != 0) {
-            snprintf(buf, sizeof(buf), "record %zu of %zu (score %d / %d, tries %d / %d, status %d / %d)", i, n, a.res[i].score, b.res[i].score, a.res[i].tries, b.res[i].tries,
-                     a.res[i].status, b.res[i].status);
-            if (why) *why = buf;
-            return false;
-        }
-        const int nc = std::min(std::max(a.res[i].n_cigar, 0), MAXC);
-        if (nc && memcmp(&a.cig[i * MAXC], &b.cig[i * MAXC], (size_t)nc * 4) != 0) { if (why) *why = "CIGAR of record " + std::to_string(i); return false; }
-        if (a.res[i].status == 0 && strcmp(&a.md[i * MAXMD], &b.md[i * MAXMD]) != 0) { if (why) *why = "MD of record " + std::to_string(i); return false; }
-    }
-    return a.cig[n * MAXC] == 0xdeadbeefu && a.md[n * MAXMD] == '#' && b.cig[n * MAXC] == 0xdeadbeefu && b.md[n * MAXMD] == '#';
-}
-
-static bool same_m(const std::vector<bsw_mresult> &a, const std::vector<bsw_mresult> &b, size_t n)
-{
-    return n == 0 || memcmp(a.data(), b.data(), n * sizeof(bsw_mresult)) == 0;
-}
-
-static void m_init(std::vector<bsw_mresult> &r, size_t n)
-{
-    r.resize(n + 1);
-    memset(r.data(), 0x5a, r.size() * sizeof(bsw_mresult));
-}
-
-static int submit_c(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const cwork &w, c_out &o, bsw_ticket *t)
-{
-    o.init(w.t.size());
-    return bsw_cigar_ref_submit_t(ctx, &p, ref, w.t.data(), w.t.size(), MAXC, o.cig.data(), MAXMD, o.md.data(), o.res.data(), t);
-}
-
-static int submit_m(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const mwork &w, std::vector<bsw_mresult> &o, bsw_ticket *t)
-{
-    m_init(o, w.t.size());
-    return bsw_matesw_ref_submit_t(ctx, &p, ref, w.t.data(), w.t.size(), o.data(), t);
-}
-
-static void sync_c(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const cwork &w, c_out &o)
-{
-    o.init(w.t.size());
-    const int rc = bsw_cigar_ref_batch(ctx, &p, ref, w.t.data(), w.t.size(), MAXC, o.cig.data(), MAXMD, o.md.data(), o.res.data());
-    CHECK(rc == BSW_OK, "bsw_cigar_ref_batch -> %d (%s)", rc, bsw_last_error(ctx));
-}
-
-static void sync_m(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const mwork &w, std::vector<bsw_mresult> &o)
-{
-    m_init(o, w.t.size());
-    const int rc = bsw_matesw_ref_batch(ctx, &p, ref, w.t.data(), w.t.size(), o.data());
-    CHECK(rc == BSW_OK, "bsw_matesw_ref_batch -> %d (%s)", rc, bsw_last_error(ctx));
-}
-
-static bsw_stats stats_of(bsw_ctx *ctx)
-{
-    bsw_stats s;
-    CHECK(bsw_host_stats(ctx, &s, sizeof(s)) == BSW_OK, "bsw_host_stats");
-    return s;
-}
-
-static bsw_ref *upload(bsw_ctx *ctx, const genome_t &g)
-{
-    bsw_ref *ref = nullptr;
-    CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK, "bsw_ref_upload: %s", bsw_last_error(ctx));
-    return ref;
-}
-
-/* the expected values of one workload pair: the synchronous calls on a one-device context */
-struct want_t {
-    c_out c;
-    std::vector<bsw_mresult> m;
-};
-static void expected_f4(const bsw_params &p, const genome_t &g, const cwork &cw, const mwork &mw, want_t &want)
-{
-    bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256);
-    bsw_ref *ref = upload(ctx, g);
-    sync_c(ctx, p, ref, cw, want.c);
-    sync_m(ctx, p, ref, mw, want.m);
-    bsw_ref_free(ctx, ref);
-    bsw_destroy(ctx);
-}
+#include "host_f4_tickets.h"
 
 /* ---- parity ---- */
 static int parity_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(150001, 77);
     const size_t n = 1300;
     size_t cases = 0;
@@ -218,7 +119,7 @@ static int parity_mode()
 static int reach_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(120001, 31);
     const size_t n = 900;
     for (int kind = 0; kind < 2; ++kind) {
@@ -282,7 +183,7 @@ static int reach_mode()
 static int mixed_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(120001, 41);
     const size_t n = 700, ne = 900;
     fresh(2);
@@ -351,7 +252,7 @@ static int mixed_mode()
 static int storm_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(90001, 51);
     fresh(2);
     {
@@ -439,7 +340,7 @@ static int storm_mode()
 static int faults_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(90001, 13);
     const size_t n = 150, ne = 500;
     uint64_t visited = 0, failed = 0, ignored = 0, dead = 0, C = 0;
@@ -553,7 +454,7 @@ static int faults_mode()
 static int watchdog_mode()
 {
     const bsw_params p = default_params();
-    genome_t g;
+    genome1_t g;
     g.make(90001, 61);
     const size_t n = 300;
     for (int kind = 0; kind < 2; ++kind) {

@@ -1,6 +1,6 @@
 /* host_patch.cpp — bsw_patch_ref_batch, bsw_patch_ref_submit_t and bsw_patch_reads_submit_t (mem_patch_reg: bsw_cigar.hip, its
  * tickets through bsw_batch.hip's pipeline) on the host-memory HIP stand-in, plain and under ASan / UBSan or TSan (TEST INFRASTRUCTURE;
- * tests/test_patch_double_cpu.py builds it with tests/_patch_double_build.py and runs it).  A stand-alone program: nothing is
+ * tests/test_patch_double_cpu.py builds it with its row in tests/_host_double_build.py and runs it).  A stand-alone program: nothing is
  * preloaded, no GPU is opened.
  *
  *   host_patch parity   the batch call and both ticket forms on 1, 2 and 3 devices, registered and pageable reads, against the C
@@ -12,83 +12,8 @@
  *                       is BUSY until the reads ticket is collected
  *   host_patch faults   every HIP / launcher call of one submit of each patch form fails in turn
  */
-#include <algorithm>
 #include <climits>
-#include <cmath>
-#include "host_common.h"
-
-struct rng_t {
-    uint64_t s;
-    explicit rng_t(uint64_t seed) : s(seed * 0x9e3779b97f4a7c15ull + 1) {}
-    uint64_t next() { uint64_t z = (s += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
-    int below(int n) { return (int)(next() % (uint64_t)n); }
-    int in(int lo, int hi) { return lo + below(hi - lo + 1); }           /* inclusive */
-    double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
-
-/* a genome, its 2-bit pac (bwa's layout) and both strands in bwa's coordinates */
-struct genome_t {
-    int64_t l_pac = 0;
-    std::vector<uint8_t> both, pac;
-    void make(int64_t n, uint64_t seed)
-    {
-        rng_t r(seed);
-        l_pac = n;
-        both.resize((size_t)(2 * n));
-        for (int64_t x = 0; x < n; ++x) both[(size_t)x] = (uint8_t)r.below(4);
-        for (int64_t x = n; x < 2 * n; ++x) both[(size_t)x] = (uint8_t)(3 - both[(size_t)(2 * n - 1 - x)]);
-        pac.assign((size_t)((n + 3) >> 2), 0);
-        for (int64_t x = 0; x < n; ++x) pac[(size_t)(x >> 2)] |= (uint8_t)(both[(size_t)x] << ((~x & 3) << 1));
-    }
-};
-
-/* ---- mem_patch_reg restated in C from its text (bwamem.c, bwa >= 0.7.10, as recalled) ---- */
-static int ref_band(const bsw_params &p, int l_query, int rlen, int w_)
-{
-    const int max_ins = (int)((double)(((l_query + 1) >> 1) * p.mat[0] - p.o_ins) / p.e_ins + 1.);
-    const int max_del = (int)((double)(((l_query + 1) >> 1) * p.mat[0] - p.o_del) / p.e_del + 1.);
-    int max_gap = max_ins > max_del ? max_ins : max_del;
-    max_gap = max_gap > 1 ? max_gap : 1;
-    int w = (max_gap + abs(rlen - l_query) + 1) >> 1;
-    w = w < w_ ? w : w_;
-    const int min_w = abs(rlen - l_query) + 3;
-    return w > min_w ? w : min_w;
-}
-
-static bsw_presult ref_patch(const bsw_params &p, const genome_t &g, const uint8_t *query, const bsw_preg &a, const bsw_preg &b, bool *shortcut = nullptr)
-{
-    const bsw_presult none = {0, 0, 0, 1};
-    const int64_t l_pac = g.l_pac;
-    if (shortcut) *shortcut = false;
-    if (a.rb < l_pac && b.rb >= l_pac) return none;
-    if (a.qb >= b.qb || a.qe >= b.qe || a.re >= b.re) return none;
-    int w = (int)((a.re - b.rb) - (a.qe - b.qb));
-    w = w > 0 ? w : -w;
-    double r = (double)(a.re - b.rb) / (b.re - a.rb) - (double)(a.qe - b.qb) / (b.qe - a.qb);
-    r = r > 0. ? r : -r;
-    if (a.re < b.rb || a.qe < b.qb) { if (w > p.w << 1 || r >= 0.05f) return none; }
-    else { if (w > p.w << 2 || r >= 0.05f * 2) return none; }
-    w += a.w + b.w;
-    w = w < p.w << 2 ? w : p.w << 2;
-    /* bwa_gen_cigar2, the score only */
-    const int64_t rb = a.rb, re = b.re;
-    const int lq = b.qe - a.qb;
-    if (lq <= 0 || rb >= re || (rb < l_pac && re > l_pac) || rb < 0 || re > 2 * l_pac) return none;
-    std::vector<uint8_t> q(query + a.qb, query + b.qe), t(g.both.begin() + rb, g.both.begin() + re);
-    if (rb >= l_pac) { std::reverse(q.begin(), q.end()); std::reverse(t.begin(), t.end()); }
-    int score = 0;
-    if (lq == (int)(re - rb) && w == 0) {
-        for (int i = 0; i < lq; ++i) score += p.mat[std::min<int>(t[(size_t)i], 4) * 5 + std::min<int>(q[(size_t)i], 4)];
-        if (shortcut) *shortcut = true;
-    } else {
-        uint64_t cells = 0;
-        score = ksw_global2_ref(lq, q.data(), (int)(re - rb), t.data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, ref_band(p, lq, (int)(re - rb), w), nullptr, nullptr, &cells);
-    }
-    const int q_s = (int)((double)(b.qe - a.qb) / ((b.qe - b.qb) + (a.qe - a.qb)) * (b.score + a.score) + .499);
-    const int r_s = (int)((double)(b.re - a.rb) / ((b.re - b.rb) + (a.re - a.rb)) * (b.score + a.score) + .499);
-    const int ret = (double)score / (q_s > r_s ? q_s : r_s) < 0.90f ? 0 : score;
-    return bsw_presult{ret, w, score, ret > 0 ? 0 : 2};
-}
+#include "host_ref_patch.h"
 
 /* ---- the workload: reads of 150 / 250 / a few long bases off both strands, cut into two regions around an indel ---- */
 struct pwork {
@@ -187,32 +112,6 @@ static std::vector<bsw_presult> fresh_out(size_t n)
 static void guard_ok(const std::vector<bsw_presult> &o, const char *what)
 {
     CHECK(o.back().score == 0x5a5a5a5a && o.back().status == 0x5a5a5a5a, "%s: a write behind the caller's array", what);
-}
-
-static bsw_params default_params()
-{
-    bsw_params p;
-    bsw_default_params(&p);
-    return p;
-}
-static bsw_ref *upload(bsw_ctx *ctx, const genome_t &g)
-{
-    bsw_ref *ref = nullptr;
-    CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK && ref, "bsw_ref_upload: %s", bsw_last_error(ctx));
-    return ref;
-}
-static bsw_reads *upload_reads(bsw_ctx *ctx, const pwork &w)
-{
-    bsw_reads *rd = nullptr;
-    CHECK(bsw_reads_upload(ctx, w.ptr.data(), w.len.data(), w.ptr.size(), &rd) == BSW_OK && rd, "bsw_reads_upload: %s", bsw_last_error(ctx));
-    return rd;
-}
-static bsw_stats stats_of(bsw_ctx *ctx)
-{
-    bsw_stats s;
-    memset(&s, 0, sizeof(s));
-    CHECK(bsw_host_stats(ctx, &s, sizeof(s)) == BSW_OK, "bsw_host_stats");
-    return s;
 }
 
 /* the three forms on one context; returns the chunks the two tickets ran */
@@ -588,81 +487,50 @@ static int faults_mode()
     const bsw_params p = default_params();
     genome_t g;
     g.make(70001, 5);
-    uint64_t visited = 0, failed = 0, ignored = 0, C = 0;
+    sweep_t s;
+    /* releases whose code is ignored by design; a slot thread's hipSetDevice when the slot gets no chunk of these one-chunk
+       tickets (it tries again in front of its next job) */
+    s.releases = {"hipSetDevice", "hipFree", "hipHostFree", "hipGetLastError", "hipEventDestroy", "hipStreamDestroy", "hipHostUnregister", "hipEventQuery"};
+    s.min_visited = 60; s.min_failed = 50;
     for (int reg = 0; reg < 2; ++reg)
-        for (uint64_t k = 0;; ++k) {
-            bool made = true;
-            fresh(2);
-            {
-                rng_t r(31);
-                pwork w;
-                make_patch(w, g, p, r, 96, reg != 0);
-                const size_t n = w.t.size(), live0 = hipdbl::live_objects();
-                bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 256, 2, 4000);
-                bsw_ref *ref = upload(ctx, g);
-                bsw_reads *rd = upload_reads(ctx, w);
-                std::vector<bsw_presult> o0 = fresh_out(n), o1 = fresh_out(n), o2 = fresh_out(n);
-                hipdbl::reset_counters();
-                if (k) hipdbl::fail_overall(k);
-                bsw_ticket t[2] = {0, 0};
-                const int rb = bsw_patch_ref_batch(ctx, &p, ref, w.t.data(), n, o0.data());
-                const std::string tb = rb ? bsw_last_error(ctx) : "";
-                int rs[2], rc[3];
-                std::string text[3];
-                rs[0] = bsw_patch_ref_submit_t(ctx, &p, ref, w.t.data(), n, o1.data(), &t[0]);
-                rs[1] = bsw_patch_reads_submit_t(ctx, &p, ref, rd, w.rt.data(), n, o2.data(), &t[1]);
-                /* (the pipeline's own start may be what fails: then the submit answers, no ticket is made) */
-                for (int j = 0; j < 2; ++j) {
-                    rc[j] = rs[j] ? rs[j] : bsw_wait_ticket(ctx, t[j]);
-                    text[j] = rc[j] ? bsw_last_error(ctx) : "";
-                }
-                rc[2] = rb; text[2] = tb;
-                const char *f = hipdbl::fired();
-                const std::string fname = f ? f : "";
-                const uint64_t calls = hipdbl::overall_calls();
-                hipdbl::clear_failures();
-                if (rc[2] == BSW_OK) same_p(o0, w, n, "a batch call that reported success");
-                if (rc[0] == BSW_OK) same_p(o1, w, n, "a ticket that reported success");
-                if (rc[1] == BSW_OK) same_p(o2, w, n, "a reads ticket that reported success");
-                const int nfail = (rc[0] != 0) + (rc[1] != 0) + (rc[2] != 0);
-                if (k == 0) {
-                    C = calls;
-                    CHECK(nfail == 0, "the clean scenario -> %d %d %d (%s)", rc[0], rc[1], rc[2], bsw_last_error(ctx));
-                    printf("faults, %s memory: C = %llu\n", reg ? "registered" : "pageable", (unsigned long long)C);
-                } else if (!f) {
-                    CHECK(k > calls && 10 * k > 9 * C, "call %llu of the scenario was never made (this run made %llu, the clean one %llu)", (unsigned long long)k, (unsigned long long)calls, (unsigned long long)C);
-                    CHECK(nfail == 0, "k=%llu: no failure happened and a call failed", (unsigned long long)k);
-                    made = false;
-                } else {
-                    ++visited;
-                    if (nfail) {
-                        ++failed;
-                        CHECK(nfail == 1, "k=%llu: %s failed once and %d calls failed", (unsigned long long)k, fname.c_str(), nfail);
-                        const bool alloc = fname == "hipMalloc" || fname == "hipHostMalloc";
-                        for (int j = 0; j < 3; ++j)
-                            if (rc[j]) {
-                                CHECK(rc[j] == BSW_E_HIP || (alloc && rc[j] == BSW_E_NOMEM), "k=%llu: %s failed and call %d answered %d (%s)", (unsigned long long)k, fname.c_str(), j, rc[j], text[j].c_str());
-                                CHECK(!text[j].empty() && text[j].compare(0, 7, "aborted") != 0, "k=%llu: %s failed, call %d reports '%s'", (unsigned long long)k, fname.c_str(), j, text[j].c_str());
-                            }
-                    } else {
-                        ++ignored;                                 /* a release whose code is ignored by design; a slot thread's hipSetDevice when the
-                                                                      slot gets no chunk of these one-chunk tickets (it tries again in front of its next job) */
-                        CHECK(fname == "hipSetDevice" || fname == "hipFree" || fname == "hipHostFree" || fname == "hipGetLastError" || fname == "hipEventDestroy" || fname == "hipStreamDestroy" ||
-                              fname == "hipHostUnregister" || fname == "hipEventQuery", "k=%llu: %s failed and every call reported success", (unsigned long long)k, fname.c_str());
-                    }
-                }
-                CHECK(bsw_inflight(ctx) == 0, "tickets left");
-                /* the context is alive (an injected return code never kills it): every form once more, bit-exact */
-                CHECK(bsw_reads_free(ctx, rd) == BSW_OK, "k=%llu: bsw_reads_free after the tickets: %s", (unsigned long long)k, bsw_last_error(ctx));
-                three_forms(ctx, p, ref, w, "after the failure");
-                bsw_ref_free(ctx, ref);
-                bsw_destroy(ctx);
-                CHECK(hipdbl::live_objects() == live0, "k=%llu (%s failed): %zu HIP objects left alive after bsw_destroy", (unsigned long long)k, fname.c_str(), hipdbl::live_objects() - live0);
+        fault_sweep(s, 2, [&](sweep_t &s) {
+            const unsigned long long k = s.k;
+            rng_t r(31);
+            pwork w;
+            make_patch(w, g, p, r, 96, reg != 0);
+            const size_t n = w.t.size();
+            bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 256, 2, 4000);
+            bsw_ref *ref = upload(ctx, g);
+            bsw_reads *rd = upload_reads(ctx, w);
+            std::vector<bsw_presult> o0 = fresh_out(n), o1 = fresh_out(n), o2 = fresh_out(n);
+            s.arm();
+            bsw_ticket t[2] = {0, 0};
+            const int rb = bsw_patch_ref_batch(ctx, &p, ref, w.t.data(), n, o0.data());
+            const std::string tb = rb ? bsw_last_error(ctx) : "";
+            int rs[2], rc[3];
+            std::string text[3];
+            rs[0] = bsw_patch_ref_submit_t(ctx, &p, ref, w.t.data(), n, o1.data(), &t[0]);
+            rs[1] = bsw_patch_reads_submit_t(ctx, &p, ref, rd, w.rt.data(), n, o2.data(), &t[1]);
+            /* (the pipeline's own start may be what fails: then the submit answers, no ticket is made) */
+            for (int j = 0; j < 2; ++j) {
+                rc[j] = rs[j] ? rs[j] : bsw_wait_ticket(ctx, t[j]);
+                text[j] = rc[j] ? bsw_last_error(ctx) : "";
             }
-            if (!made) break;
-        }
-    printf("faults: injection points visited = %llu, a call failed %llu times, ignored %llu\n", (unsigned long long)visited, (unsigned long long)failed, (unsigned long long)ignored);
-    CHECK(visited >= 60 && failed >= 50, "the sweep visited %llu calls, %llu failed", (unsigned long long)visited, (unsigned long long)failed);
+            rc[2] = rb; text[2] = tb;
+            s.judge({{rc[0], text[0]}, {rc[1], text[1]}, {rc[2], text[2]}});
+            if (rc[2] == BSW_OK) same_p(o0, w, n, "a batch call that reported success");
+            if (rc[0] == BSW_OK) same_p(o1, w, n, "a ticket that reported success");
+            if (rc[1] == BSW_OK) same_p(o2, w, n, "a reads ticket that reported success");
+            if (k == 0) printf("faults, %s memory: C = %llu\n", reg ? "registered" : "pageable", (unsigned long long)s.C);
+            CHECK(bsw_inflight(ctx) == 0, "tickets left");
+            /* the context is alive (an injected return code never kills it): every form once more, bit-exact */
+            CHECK(bsw_reads_free(ctx, rd) == BSW_OK, "k=%llu: bsw_reads_free after the tickets: %s", k, bsw_last_error(ctx));
+            three_forms(ctx, p, ref, w, "after the failure");
+            bsw_ref_free(ctx, ref);
+            bsw_destroy(ctx);
+        });
+    printf("faults: injection points visited = %llu, a call failed %llu times, ignored %llu\n", (unsigned long long)s.visited, (unsigned long long)s.failed, (unsigned long long)s.ignored);
+    s.done();
     return 0;
 }
 

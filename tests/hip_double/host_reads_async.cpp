@@ -1,7 +1,7 @@
 /* host_reads_async.cpp — the asynchronous read-block upload (bsw_reads_upload_start / bsw_reads_test / bsw_reads_wait /
  * bsw_reads_image: bsw_reads_async.hip, the upload jobs of bsw_batch.hip, reads_order in the three submit paths) on the
  * host-memory HIP stand-in, under ASan / UBSan or TSan (TEST INFRASTRUCTURE; tests/test_reads_async_double_cpu.py builds it with
- * tests/_reads_async_double_build.py and runs it).
+ * its row in tests/_host_double_build.py and runs it).
  *
  *   host_reads_async parity     the image equals bsw_reads_upload's on 1, 2, 3 and 8 devices, one and several pieces per device,
  *                               reads in registered and in pageable memory; the three *_reads_* tickets submitted right behind
@@ -12,20 +12,10 @@
  *   host_reads_async faults     every HIP / launcher call of a start and of its pieces fails in turn
  *   host_reads_async threads    start / test / wait / submit from nine threads
  *
- * The workloads and the expected values are host_reads.cpp's (included inside a namespace). */
-#include <algorithm>
+ * The workloads and the expected values are host_reads' (host_reads_work.h). */
 #include <atomic>
 #include <chrono>
-#include <climits>
-#include <memory>
-#include "host_common.h"
-#include "../../bwa-mem-sw_amd/csrc/bsw_f4_host.h"      /* (host_f4.cpp's, for its cuts mode: in before the namespace opens) */
-#include "launchers_reads.h"
-
-namespace hr {                                       /* (its main() becomes hr::main; the headers above are in already) */
-#include "host_reads.cpp"
-}
-using namespace hr;
+#include "host_reads_work.h"
 
 namespace standin_rdpack {
 uint64_t launches();
@@ -142,7 +132,7 @@ static int parity_mode_async()
                 standin_reads::reset();
                 standin_rdpack::reset();
                 bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, G, 256, 2);
-                bsw_ref *ref = hr::upload(ctx, S.g);
+                bsw_ref *ref = upload(ctx, S.g);
                 block_t &B = direct ? RB.blk : S.blk;
                 /* the image */
                 bsw_reads *sync = nullptr;
@@ -213,7 +203,7 @@ static int limits_mode_async()
         S.expect(p);
         setenv("BSW_READS_UP_BYTES", "5000", 1);
         bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 256, 2);
-        bsw_ref *ref = hr::upload(ctx, S.g);
+        bsw_ref *ref = upload(ctx, S.g);
         stall_all();
         bsw_reads *a = start(ctx, S.blk), *b = start(ctx, S.blk), *c = (bsw_reads *)16;
         std::this_thread::sleep_for(std::chrono::milliseconds(60));      /* (every slot sits in a piece's wait by now: nothing moves) */
@@ -268,7 +258,7 @@ static int watchdog_mode_async()
         S.make(100, 200, 29);
         S.expect(p);
         bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 256, 2, 300);
-        kept_ref = hr::upload(ctx, S.g);
+        kept_ref = upload(ctx, S.g);
         stall_all();
         kept = start(ctx, S.blk);
         tickets3 T;
@@ -306,7 +296,7 @@ static int faults_mode_async()
              * that says why, NO pack launch reads the block, and a pointer-form ticket beside them is left alone */
             fresh(1);
             bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 1, 128, 2, 4000);
-            bsw_ref *ref = hr::upload(ctx, S.g);
+            bsw_ref *ref = upload(ctx, S.g);
             standin_reads::reset();
             hipdbl::reset_counters();
             hipdbl::fail_named(who, 1);
@@ -334,7 +324,7 @@ static int faults_mode_async()
         for (uint64_t k = 0;; ++k) {
             standin::reset();                         /* (ledgers are keyed by device addresses: nothing of the last context's may be left) */
             bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 128, 2, 4000);
-            bsw_ref *ref = hr::upload(ctx, S.g);
+            bsw_ref *ref = upload(ctx, S.g);
             S.blk.seal();
             standin_reads::reset();
             const size_t live0 = hipdbl::live_objects();
@@ -425,7 +415,7 @@ static int threads_mode_async()
         S.expect(p);
         setenv("BSW_READS_UP_BYTES", "7000", 1);
         bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 256, 2);
-        bsw_ref *ref = hr::upload(ctx, S.g);
+        bsw_ref *ref = upload(ctx, S.g);
         S.blk.seal();
         const size_t ne = S.ew.rt.size();
         std::atomic<int> rounds{0}, busy{0};

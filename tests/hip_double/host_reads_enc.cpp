@@ -1,6 +1,6 @@
 /* host_reads_enc.cpp — the upload encodings of a resident read block (bsw_reads_upload_enc / bsw_reads_upload_start_enc:
  * bsw_reads.hip, bsw_reads_async.hip) on the host-memory HIP stand-in, under ASan / UBSan or TSan (TEST INFRASTRUCTURE;
- * tests/test_reads_enc_double_cpu.py builds it with tests/_reads_enc_double_build.py and runs it).
+ * tests/test_reads_enc_double_cpu.py builds it with its row in tests/_host_double_build.py and runs it).
  *
  *   host_reads_enc parity      codes, letters and words; reads in one registered arena (direct) and in pageable memory (gathered);
  *                              one device and the same ordinal twice; 4 KiB pieces: every device's image of the _start_enc upload
@@ -25,19 +25,13 @@ void reset();
 static const int ENCS[3] = {BSW_READS_CODES, BSW_READS_ASCII, BSW_READS_PACKED};
 static const char *ENC_NAME[3] = {"codes", "letters", "words"};
 
-struct rng_t {
+/* this program's own generator: its stream defines the blocks, which the splitmix rng_t of host_common.h would change */
+struct xorshift_t {
     uint64_t s;
-    explicit rng_t(uint64_t seed) : s(seed * 2654435761u + 88172645463325252ull) {}
+    explicit xorshift_t(uint64_t seed) : s(seed * 2654435761u + 88172645463325252ull) {}
     uint32_t next() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (uint32_t)(s >> 16); }
     uint32_t below(uint32_t n) { return next() % n; }
 };
-
-static bsw_stats stats_of(bsw_ctx *ctx)
-{
-    bsw_stats s;
-    CHECK(bsw_host_stats(ctx, &s, sizeof(s)) == BSW_OK, "bsw_host_stats");
-    return s;
-}
 
 static uint8_t code_of_letter(uint8_t b)
 {
@@ -66,7 +60,7 @@ struct enc_block {
     {
         enc = e;
         len = lens;
-        rng_t r(seed);
+        xorshift_t r(seed);
         static const char letters[] = "ACGTacgtNnRYKMUu-.*";
         size_t arena_len = 64;
         for (size_t i = 0; i < len.size(); ++i) {
@@ -105,7 +99,7 @@ struct enc_block {
 static std::vector<int32_t> block_lens()
 {
     std::vector<int32_t> l = {0};
-    rng_t r(17);
+    xorshift_t r(17);
     for (int rep = 0; rep < 3; ++rep) {
         for (int n : {1, 15, 16, 17, 31, 32, 33, 150, 250, 255, 256, 257, 513, 1000}) l.push_back(n);
         for (int k = 0; k < 12; ++k) l.push_back(1 + (int32_t)r.below(300));

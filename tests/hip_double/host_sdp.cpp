@@ -1,6 +1,6 @@
 /* host_sdp.cpp — the mem_sort_dedup_patch job (bsw_sdp_ref_start / _reads_start / _test / _finish / _job_stats: bsw_sdp_job.hip over
  * the engine of bsw_sdp.c and the patch tickets of bsw_cigar.hip) on the host-memory HIP stand-in, plain and under ASan / UBSan or
- * TSan (TEST INFRASTRUCTURE; tests/test_sdp_double_cpu.py builds it with tests/_sdp_double_build.py and runs it).  A stand-alone
+ * TSan (TEST INFRASTRUCTURE; tests/test_sdp_double_cpu.py builds it with its row in tests/_host_double_build.py and runs it).  A stand-alone
  * program: nothing is preloaded, no GPU is opened.
  *
  * What the job must hand back is the engine driven in-process, its pairs answered by a C restatement of mem_patch_reg over the
@@ -13,80 +13,9 @@
  *                     intact; once a ticket is collected finish completes with the right bytes
  *   host_sdp faults   every HIP / launcher call of a start .. finish of each form fails in turn; the job is freed
  */
-#include <algorithm>
 #include <atomic>
 #include <climits>
-#include <cmath>
-#include "host_common.h"
-
-struct rng_t {
-    uint64_t s;
-    explicit rng_t(uint64_t seed) : s(seed * 0x9e3779b97f4a7c15ull + 1) {}
-    uint64_t next() { uint64_t z = (s += 0x9e3779b97f4a7c15ull); z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; return z ^ (z >> 31); }
-    int below(int n) { return (int)(next() % (uint64_t)n); }
-    int in(int lo, int hi) { return lo + below(hi - lo + 1); }           /* inclusive */
-    double unit() { return (double)(next() >> 11) / 9007199254740992.0; }
-};
-
-struct genome_t {
-    int64_t l_pac = 0;
-    std::vector<uint8_t> both, pac;
-    void make(int64_t n, uint64_t seed)
-    {
-        rng_t r(seed);
-        l_pac = n;
-        both.resize((size_t)(2 * n));
-        for (int64_t x = 0; x < n; ++x) both[(size_t)x] = (uint8_t)r.below(4);
-        for (int64_t x = n; x < 2 * n; ++x) both[(size_t)x] = (uint8_t)(3 - both[(size_t)(2 * n - 1 - x)]);
-        pac.assign((size_t)((n + 3) >> 2), 0);
-        for (int64_t x = 0; x < n; ++x) pac[(size_t)(x >> 2)] |= (uint8_t)(both[(size_t)x] << ((~x & 3) << 1));
-    }
-};
-
-/* ---- mem_patch_reg restated in C from its text (bwamem.c, bwa >= 0.7.10, as recalled) ---- */
-static int ref_band(const bsw_params &p, int l_query, int rlen, int w_)
-{
-    const int max_ins = (int)((double)(((l_query + 1) >> 1) * p.mat[0] - p.o_ins) / p.e_ins + 1.);
-    const int max_del = (int)((double)(((l_query + 1) >> 1) * p.mat[0] - p.o_del) / p.e_del + 1.);
-    int max_gap = max_ins > max_del ? max_ins : max_del;
-    max_gap = max_gap > 1 ? max_gap : 1;
-    int w = (max_gap + abs(rlen - l_query) + 1) >> 1;
-    w = w < w_ ? w : w_;
-    const int min_w = abs(rlen - l_query) + 3;
-    return w > min_w ? w : min_w;
-}
-
-static bsw_presult ref_patch(const bsw_params &p, const genome_t &g, const uint8_t *query, const bsw_preg &a, const bsw_preg &b)
-{
-    const bsw_presult none = {0, 0, 0, 1};
-    const int64_t l_pac = g.l_pac;
-    if (a.rb < l_pac && b.rb >= l_pac) return none;
-    if (a.qb >= b.qb || a.qe >= b.qe || a.re >= b.re) return none;
-    int w = (int)((a.re - b.rb) - (a.qe - b.qb));
-    w = w > 0 ? w : -w;
-    double r = (double)(a.re - b.rb) / (b.re - a.rb) - (double)(a.qe - b.qb) / (b.qe - a.qb);
-    r = r > 0. ? r : -r;
-    if (a.re < b.rb || a.qe < b.qb) { if (w > p.w << 1 || r >= 0.05f) return none; }
-    else { if (w > p.w << 2 || r >= 0.05f * 2) return none; }
-    w += a.w + b.w;
-    w = w < p.w << 2 ? w : p.w << 2;
-    const int64_t rb = a.rb, re = b.re;
-    const int lq = b.qe - a.qb;
-    if (lq <= 0 || rb >= re || (rb < l_pac && re > l_pac) || rb < 0 || re > 2 * l_pac) return none;
-    std::vector<uint8_t> q(query + a.qb, query + b.qe), t(g.both.begin() + rb, g.both.begin() + re);
-    if (rb >= l_pac) { std::reverse(q.begin(), q.end()); std::reverse(t.begin(), t.end()); }
-    int score = 0;
-    if (lq == (int)(re - rb) && w == 0) {
-        for (int i = 0; i < lq; ++i) score += p.mat[std::min<int>(t[(size_t)i], 4) * 5 + std::min<int>(q[(size_t)i], 4)];
-    } else {
-        uint64_t cells = 0;
-        score = ksw_global2_ref(lq, q.data(), (int)(re - rb), t.data(), 5, p.mat, p.o_del, p.e_del, p.o_ins, p.e_ins, ref_band(p, lq, (int)(re - rb), w), nullptr, nullptr, &cells);
-    }
-    const int q_s = (int)((double)(b.qe - a.qb) / ((b.qe - b.qb) + (a.qe - a.qb)) * (b.score + a.score) + .499);
-    const int r_s = (int)((double)(b.re - a.rb) / ((b.re - b.rb) + (a.re - a.rb)) * (b.score + a.score) + .499);
-    const int ret = (double)score / (q_s > r_s ? q_s : r_s) < 0.90f ? 0 : score;
-    return bsw_presult{ret, w, score, ret > 0 ? 0 : 2};
-}
+#include "host_ref_patch.h"
 
 /* ---- the workload: reads of 1 - 4 colinear pieces of the genome with a small indel between them, a region per piece (in a
  * scrambled order), sometimes a shadow of a region one base on (the redundancy test), sometimes a region of another rid ---- */
@@ -201,24 +130,6 @@ static void same_s(const outs &o, const swork &w, const char *what)
           (unsigned long long)o.st.merges, (unsigned long long)w.want_st.merges);
 }
 
-static bsw_params default_params()
-{
-    bsw_params p;
-    bsw_default_params(&p);
-    return p;
-}
-static bsw_ref *upload(bsw_ctx *ctx, const genome_t &g)
-{
-    bsw_ref *ref = nullptr;
-    CHECK(bsw_ref_upload(ctx, g.pac.data(), g.l_pac, &ref) == BSW_OK && ref, "bsw_ref_upload: %s", bsw_last_error(ctx));
-    return ref;
-}
-static bsw_reads *upload_reads(bsw_ctx *ctx, const swork &w)
-{
-    bsw_reads *rd = nullptr;
-    CHECK(bsw_reads_upload(ctx, w.ptr.data(), w.len.data(), w.ptr.size(), &rd) == BSW_OK && rd, "bsw_reads_upload: %s", bsw_last_error(ctx));
-    return rd;
-}
 static int start_ref(bsw_ctx *ctx, const bsw_params &p, bsw_ref *ref, const swork &w, bsw_sdp_job **j, const bsw_sdp_opt *opt = nullptr)
 {
     return bsw_sdp_ref_start(ctx, &p, opt, ref, w.ptr.data(), w.len.data(), w.len.size(), w.regs.data(), w.regs.size(), w.start.data(), j);
@@ -459,78 +370,46 @@ static int faults_mode()
     genome_t g;
     g.make(70001, 5);
     const bsw_params p = default_params();
-    uint64_t visited = 0, failed = 0, ignored = 0, C = 0;
     rng_t r0(31);
     swork w;
     make_regions(w, g, r0, 60);
     expect(w, g, p);
     CHECK(w.want_st.rounds >= 3, "the workload: %llu rounds", (unsigned long long)w.want_st.rounds);
-    for (uint64_t k = 0;; ++k) {
-        bool made = true;
-        fresh(2);
-        {
-            const size_t live0 = hipdbl::live_objects();
-            bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 128, 1, 4000);
-            bsw_ref *ref = upload(ctx, g);
-            both_forms(ctx, p, ref, w, "the warm-up");
-            bsw_reads *rd = upload_reads(ctx, w);
-            hipdbl::reset_counters();
-            if (k) hipdbl::fail_overall(k);
-            bsw_sdp_job *j[2] = {nullptr, nullptr};
-            outs o0(w), o1(w);
-            int rc[2];
-            std::string text[2];
-            for (int f = 0; f < 2; ++f) {            /* one job after the other: with both in flight the order of the slots' calls would be the threads' */
-                rc[f] = f ? start_reads(ctx, p, ref, rd, w, &j[f]) : start_ref(ctx, p, ref, w, &j[f]);
-                CHECK((rc[f] != 0) == (j[f] == nullptr), "k=%llu: start %d -> %d and job %p", (unsigned long long)k, f, rc[f], (void *)j[f]);
-                if (!rc[f]) rc[f] = finish(j[f], f ? o1 : o0);
-                CHECK(rc[f] != BSW_E_BUSY, "k=%llu: BSW_E_BUSY on one thread", (unsigned long long)k);
-                if (rc[f]) text[f] = bsw_last_error(ctx);
-            }
-            const char *fn = hipdbl::fired();
-            const std::string fname = fn ? fn : "";
-            const uint64_t calls = hipdbl::overall_calls();
-            hipdbl::clear_failures();
-            if (rc[0] == BSW_OK) same_s(o0, w, "a pointer job that reported success");
-            if (rc[1] == BSW_OK) same_s(o1, w, "a reads job that reported success");
-            const int nfail = (rc[0] != 0) + (rc[1] != 0);
-            if (k == 0) {
-                C = calls;
-                CHECK(nfail == 0, "the clean scenario -> %d %d (%s)", rc[0], rc[1], bsw_last_error(ctx));
-                printf("faults: C = %llu\n", (unsigned long long)C);
-            } else if (!fn) {
-                CHECK(k > calls && 10 * k > 9 * C, "call %llu of the scenario was never made (this run made %llu, the clean one %llu)", (unsigned long long)k, (unsigned long long)calls, (unsigned long long)C);
-                CHECK(nfail == 0, "k=%llu: no failure happened and a job failed", (unsigned long long)k);
-                made = false;
-            } else {
-                ++visited;
-                if (nfail) {
-                    ++failed;
-                    CHECK(nfail == 1, "k=%llu: %s failed once and %d jobs failed", (unsigned long long)k, fname.c_str(), nfail);
-                    const bool alloc = fname == "hipMalloc" || fname == "hipHostMalloc";
-                    for (int f = 0; f < 2; ++f)
-                        if (rc[f]) {
-                            CHECK(rc[f] == BSW_E_HIP || (alloc && rc[f] == BSW_E_NOMEM), "k=%llu: %s failed and job %d answered %d (%s)", (unsigned long long)k, fname.c_str(), f, rc[f], text[f].c_str());
-                            CHECK(!text[f].empty() && text[f].compare(0, 7, "aborted") != 0, "k=%llu: %s failed, job %d reports '%s'", (unsigned long long)k, fname.c_str(), f, text[f].c_str());
-                        }
-                } else {
-                    ++ignored;                       /* a release whose code is ignored by design; a slot's hipSetDevice when it gets no chunk */
-                    CHECK(fname == "hipSetDevice" || fname == "hipFree" || fname == "hipHostFree" || fname == "hipGetLastError" || fname == "hipEventDestroy" || fname == "hipStreamDestroy" ||
-                          fname == "hipHostUnregister" || fname == "hipEventQuery", "k=%llu: %s failed and every job reported success", (unsigned long long)k, fname.c_str());
-                }
-            }
-            /* both jobs are gone: no ticket, the block is free, and what they pinned is released */
-            CHECK(bsw_inflight(ctx) == 0, "k=%llu: tickets left", (unsigned long long)k);
-            CHECK(bsw_reads_free(ctx, rd) == BSW_OK, "k=%llu: bsw_reads_free after the jobs: %s", (unsigned long long)k, bsw_last_error(ctx));
-            both_forms(ctx, p, ref, w, "after the failure");
-            bsw_ref_free(ctx, ref);
-            bsw_destroy(ctx);
-            CHECK(hipdbl::live_objects() == live0, "k=%llu (%s failed): %zu HIP objects left alive after bsw_destroy", (unsigned long long)k, fname.c_str(), hipdbl::live_objects() - live0);
+    sweep_t s;
+    /* releases whose code is ignored by design; a slot's hipSetDevice when it gets no chunk */
+    s.releases = {"hipSetDevice", "hipFree", "hipHostFree", "hipGetLastError", "hipEventDestroy", "hipStreamDestroy", "hipHostUnregister", "hipEventQuery"};
+    s.min_visited = 60; s.min_failed = 50;
+    fault_sweep(s, 2, [&](sweep_t &s) {
+        const unsigned long long k = s.k;
+        bsw_ctx *ctx = make_ctx(BSW_KERNEL_AUTO, 2, 128, 1, 4000);
+        bsw_ref *ref = upload(ctx, g);
+        both_forms(ctx, p, ref, w, "the warm-up");
+        bsw_reads *rd = upload_reads(ctx, w);
+        s.arm();
+        bsw_sdp_job *j[2] = {nullptr, nullptr};
+        outs o0(w), o1(w);
+        int rc[2];
+        std::string text[2];
+        for (int f = 0; f < 2; ++f) {            /* one job after the other: with both in flight the order of the slots' calls would be the threads' */
+            rc[f] = f ? start_reads(ctx, p, ref, rd, w, &j[f]) : start_ref(ctx, p, ref, w, &j[f]);
+            CHECK((rc[f] != 0) == (j[f] == nullptr), "k=%llu: start %d -> %d and job %p", k, f, rc[f], (void *)j[f]);
+            if (!rc[f]) rc[f] = finish(j[f], f ? o1 : o0);
+            CHECK(rc[f] != BSW_E_BUSY, "k=%llu: BSW_E_BUSY on one thread", k);
+            if (rc[f]) text[f] = bsw_last_error(ctx);
         }
-        if (!made) break;
-    }
-    printf("faults: injection points visited = %llu, a job failed %llu times, ignored %llu\n", (unsigned long long)visited, (unsigned long long)failed, (unsigned long long)ignored);
-    CHECK(visited >= 60 && failed >= 50, "the sweep visited %llu of %llu calls, %llu failed", (unsigned long long)visited, (unsigned long long)C, (unsigned long long)failed);
+        s.judge({{rc[0], text[0]}, {rc[1], text[1]}});
+        if (rc[0] == BSW_OK) same_s(o0, w, "a pointer job that reported success");
+        if (rc[1] == BSW_OK) same_s(o1, w, "a reads job that reported success");
+        if (k == 0) printf("faults: C = %llu\n", (unsigned long long)s.C);
+        /* both jobs are gone: no ticket, the block is free, and what they pinned is released */
+        CHECK(bsw_inflight(ctx) == 0, "k=%llu: tickets left", k);
+        CHECK(bsw_reads_free(ctx, rd) == BSW_OK, "k=%llu: bsw_reads_free after the jobs: %s", k, bsw_last_error(ctx));
+        both_forms(ctx, p, ref, w, "after the failure");
+        bsw_ref_free(ctx, ref);
+        bsw_destroy(ctx);
+    });
+    printf("faults: injection points visited = %llu, a job failed %llu times, ignored %llu\n", (unsigned long long)s.visited, (unsigned long long)s.failed, (unsigned long long)s.ignored);
+    s.done();
     return 0;
 }
 

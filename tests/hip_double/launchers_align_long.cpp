@@ -1,5 +1,5 @@
 /* launchers_align_long.cpp — bsw::launch_align_long and its class functions for the host-double program of ksw_align2's
- * long-query route (TEST INFRASTRUCTURE; built by tests/_align_long_double_build.py, never part of the library).
+ * long-query route (TEST INFRASTRUCTURE; built by its row in tests/_host_double_build.py, never part of the library).
  *
  * The class table is restated from the header's contract (bsw_align_long_stats: 8-bit mode slen bounds 16 .. 512, then 16-bit mode
  * 32 .. 1 024, slen = ceil(qlen / lanes)).  The stand-in computes every listed task with oracle/ksw_align_ref.c from the staged

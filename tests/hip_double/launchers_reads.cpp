@@ -1,5 +1,5 @@
 /* launchers_reads.cpp — bsw::launch_pack for the host-double programs that use resident read blocks (TEST INFRASTRUCTURE; built
- * by tests/_reads_double_build.py, never part of the library).
+ * by its row in tests/_host_double_build.py, never part of the library).
  *
  * launchers.cpp stays as it is: this builder compiles it a second time with -Dlaunch_pack=launch_pack_bytes, so its byte stand-in
  * (and the ledger of pack launches it keeps for the alignment stand-ins) is reachable under that name, and this file provides

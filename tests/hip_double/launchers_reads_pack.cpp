@@ -1,5 +1,5 @@
 /* launchers_reads_pack.cpp — bsw::launch_reads_pack for the host-double program of the asynchronous read-block upload (TEST
- * INFRASTRUCTURE; built by tests/_reads_async_double_build.py, never part of the library).
+ * INFRASTRUCTURE; built by its row in tests/_host_double_build.py, never part of the library).
  *
  * The kernel's word function (csrc/bsw_reads_pack.h) is restated from its contract by a nibble loop: base j of a read is the byte
  * raw[raw_off + j], stored as min(byte, 4) in nibble j & 15 of word woff + (j >> 4); the nibbles behind the last base are zero; a

@@ -1,5 +1,5 @@
 /* launchers_reads_pack_enc.cpp — bsw::launch_reads_pack for the host-double program of the upload encodings (TEST INFRASTRUCTURE;
- * built by tests/_reads_enc_double_build.py in place of launchers_reads_pack.cpp, never part of the library).
+ * built by its row in tests/_host_double_build.py in place of launchers_reads_pack.cpp, never part of the library).
  *
  * The kernel's word function (csrc/bsw_reads_pack.h) is restated from its contract per base, honouring the record's `enc`:
  *   BSW_READS_CODES   base j is the byte raw[raw_off + j], stored as min(byte, 4)

@@ -1,61 +1,23 @@
 """bsw_cigar_ref_submit_t / bsw_matesw_ref_submit_t — the CIGAR and mate-rescue jobs of the slot pipeline — on the host-memory HIP
 stand-in (tests/hip_double/), under ASan + UBSan and under TSan.  No GPU is opened.
 
-tests/hip_double/host_f4_stream.cpp is compiled here and linked against the objects tests/_host_double_build.py makes (the
-library's host-side translation units, the stand-in runtime and launchers, the oracles).  Its workloads are those of host_f4.cpp;
+tests/hip_double/host_f4_stream.cpp is a row of tests/_host_double_build.py's table, linked against the objects of the base
+programs (the library's host-side translation units, the stand-in runtime and launchers, the oracles).  Its workloads are those of host_f4.cpp;
 its expected values are the synchronous calls' results on a one-device context, which tests/test_host_double_cpu.py compares with
 the restatements of bwa on the same workloads.  Every run has a time limit: a ticket that hangs is a failure.
 
 The ABI side (header, host.EXPORTS, the Python bindings) is checked at the end of the file without a GPU."""
+import functools
 import os
 import re
-import subprocess
 
 import pytest
 
 import _host_double_build as B
 
 LIMIT = 900          # seconds per program run: the fault sweep rebuilds its scenario once per injection point
-
-_exe = {}
-
-
-def program(san):
-    """host_f4_stream for one sanitizer: compiled and linked once per process, next to the objects it is linked with."""
-    if san in _exe:
-        return _exe[san]
-    b = B.build(san)
-    flags = ["-O1", "-g", "-fno-omit-frame-pointer"] + B.SAN[san]
-    obj = os.path.join(b["dir"], "host_f4_stream.o")
-    exe = os.path.join(b["dir"], "host_f4_stream")
-    B._cc([B.HIPCC, "--cuda-host-only", "-x", "hip", "-std=c++17", "-fno-gpu-sanitize"] + flags +
-          ["-I", os.path.join(B.ROOT, "include"), "-I", B.DBL, "-c", os.path.join(B.DBL, "host_f4_stream.cpp"), "-o", obj])
-    shared = [b["objs"][n] for n in B.HOST_HIP + B.HOST_C + ["hip_double", "launchers", "oracle_extend", "oracle_global", "oracle_align", "oracle_rtl"]]
-    B._cc([B.HIPCC, "-fno-gpu-sanitize"] + B.SAN[san] + [obj] + shared + ["-o", exe, "-lpthread"])
-    _exe[san] = exe
-    return exe
-
-
-def run(san, mode):
-    exe = program(san)
-    log = os.path.join(os.path.dirname(exe), "san_f4_stream_%s" % mode)
-    e = B.env(san)
-    for k in ("ASAN_OPTIONS", "TSAN_OPTIONS", "UBSAN_OPTIONS"):
-        e[k] += ":log_path=" + log
-    try:
-        out = subprocess.run([exe, mode], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=LIMIT, env=e)
-    except subprocess.TimeoutExpired as ex:
-        raise AssertionError("host_f4_stream %s (%s) hit the time limit of %d s; last output: %r" % (mode, san, LIMIT, (ex.stdout or b"")[-600:]))
-    reports = ""
-    d = os.path.dirname(log)
-    for f in sorted(os.listdir(d)):
-        if f.startswith(os.path.basename(log) + "."):
-            reports += open(os.path.join(d, f)).read()[-6000:]
-    assert out.returncode == 0 and not reports, (mode, san, out.returncode, out.stdout[-1500:], out.stderr[-4000:], reports[-6000:])
-    return out.stdout
-
-
 SANS = ["asan", "tsan"]
+run = functools.partial(B.run, "host_f4_stream", limit=LIMIT)
 
 
 @pytest.mark.parametrize("san", SANS)
@@ -65,7 +27,7 @@ def test_submits_equal_the_synchronous_calls_on_1_2_3_and_8_devices(san):
     all statuses, both strands, is_rev 0 and 1, 1 / 2 / 3 tries and the no-gap shortcut (checked by the program).  The stand-in
     pack launch dies when a chunk's reference copy does not live on its stream's device: the runs on 2, 3 and 8 devices used each
     device's own copy.  Malformed tasks are refused with the synchronous calls' code and text and make no ticket."""
-    out = run(san, "parity")
+    out = run(san, "parity").stdout
     m = re.search(r"parity: (\d+) cases, (\d+) chunks", out)
     assert m and int(m.group(1)) == 8 and int(m.group(2)) > 8 * 40, out[-400:]
 
@@ -74,21 +36,21 @@ def test_submits_equal_the_synchronous_calls_on_1_2_3_and_8_devices(san):
 def test_a_submit_reaches_every_device(san):
     """Every stream of device 1 of a two-device context stalled: a multi-chunk submit completes device 0's chunks and no more,
     bsw_test stays 0; released, it completes with the right results."""
-    assert "reach: ok" in run(san, "reach")
+    assert "reach: ok" in run(san, "reach").stdout
 
 
 @pytest.mark.parametrize("san", SANS)
 def test_four_mixed_submits_in_flight_and_busy_for_the_fifth(san):
     """Extension, rescue, CIGAR and extension again in flight on one context: a fifth submit of any kind and the synchronous calls
     answer BSW_E_BUSY and change nothing; every ticket gets its own results; the synchronous calls work again afterwards."""
-    assert "mixed: ok" in run(san, "mixed")
+    assert "mixed: ok" in run(san, "mixed").stdout
 
 
 @pytest.mark.parametrize("san", SANS)
 def test_nine_threads_submit_and_collect_mixed_tickets(san):
     """The scenario of host_tickets.cpp with three kinds of tickets: eight threads submit, poll and collect, a ninth keeps calling
     bsw_wait and bsw_inflight."""
-    out = run(san, "storm")
+    out = run(san, "storm").stdout
     assert re.search(r"storm: 40 submits", out), out[-400:]
 
 
@@ -98,7 +60,7 @@ def test_every_hip_call_of_a_three_ticket_scenario_fails_in_turn(san):
     ticket completes; a failing ticket carries the failure itself (code and text); tickets that report success have correct
     results; a context that is not dead completes a further submit of every kind bit-exactly; nothing is left alive after
     bsw_destroy; ASan sees no read of a freed host vector."""
-    out = run(san, "faults")
+    out = run(san, "faults").stdout
     m = re.search(r"injection points visited = (\d+), a ticket failed (\d+) times", out)
     assert m and int(m.group(1)) >= 150 and int(m.group(2)) >= 100, out[-600:]
 
@@ -107,7 +69,7 @@ def test_every_hip_call_of_a_three_ticket_scenario_fails_in_turn(san):
 def test_the_watchdog_fails_the_ticket_and_marks_the_context_dead(san):
     """A stalled stream under timeout_ms = 300: the wait answers BSW_E_HIP with a timeout text, later submits and the synchronous
     call answer BSW_E_HIP on the dead context."""
-    assert "watchdog: ok" in run(san, "watchdog")
+    assert "watchdog: ok" in run(san, "watchdog").stdout
 
 
 # ---- ABI -------------------------------------------------------------------------------------------------------------------

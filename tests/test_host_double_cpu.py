@@ -10,6 +10,7 @@ compared over every class, strand, status, retry count and memory kind (f4), acr
 sub-optimal-list bounds of their sub-batch loops (f4split; the 2^31 sequence-byte bound is not reached here), from many threads
 through the scalar queue (f4scalar), and with every single HIP call failing in turn.  The ticket-lifetime hazard in slot_main's BSW_DEBUG_TIMING print (id read after chunk_done) was closed by inspection:
 neither the ticket storm nor a failure sweep with the switch set made the old code fault."""
+import functools
 import os
 import re
 import subprocess
@@ -22,28 +23,7 @@ import _host_double_build as B
 import _matesw_ref as ms
 
 LIMIT = 300          # seconds per program, as tests/test_sanitizers_cpu.py gives asan_plan: the deadlock detector
-
-
-def run(san, prog, *args, env=None, quiet_stderr=False, expect_ok=True):
-    b = B.build(san)
-    log = os.path.join(b["dir"], "san_%s_%s" % (prog, "_".join(args)))
-    e = B.env(san, **(env or {}))
-    for k in ("ASAN_OPTIONS", "TSAN_OPTIONS", "UBSAN_OPTIONS"):
-        e[k] += ":log_path=" + log                   # reports survive a discarded stderr
-    try:
-        out = subprocess.run([b[prog]] + list(args), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL if quiet_stderr else subprocess.PIPE,
-                             text=True, timeout=LIMIT, env=e)
-    except subprocess.TimeoutExpired as ex:
-        tail = (ex.stdout or b"")[-600:]
-        raise AssertionError("%s %s (%s) hit the time limit of %d s; last output: %r" % (prog, " ".join(args), san, LIMIT, tail))
-    reports = ""
-    d = os.path.dirname(log)
-    for f in sorted(os.listdir(d)):
-        if f.startswith(os.path.basename(log) + "."):
-            reports += open(os.path.join(d, f)).read()[-6000:]
-    if expect_ok:
-        assert out.returncode == 0 and not reports, (prog, args, san, out.returncode, out.stdout[-1500:], (out.stderr or "")[-4000:], reports[-6000:])
-    return out, reports
+run = functools.partial(B.run, limit=LIMIT)
 
 
 SANS = ["asan", "tsan"]
@@ -75,7 +55,7 @@ def test_no_hip_symbol_is_left_to_the_runtime_library():
 def test_standin_class_tables_equal_the_librarys(host):
     """The stand-ins restate the kernels' class tables.  One probe seed per query length through bsw_plan_batch: the program (its
     own tables) and the built library (the kernels' tables) must put every probe into the same segment."""
-    out, _ = run("asan", "host_parity", "tables")
+    out = run("host_parity", "asan", "tables")
     rows = [tuple(int(x) for x in l.split()[1:]) for l in out.stdout.splitlines() if l.startswith("table ")]
     assert len(rows) > 800
     bases = np.ones(16384, dtype=np.uint8)
@@ -100,7 +80,7 @@ def test_standin_class_tables_equal_the_librarys(host):
 def test_standin_align_and_global_class_tables_equal_the_kernel_sources():
     """The stand-ins restate kAlignClasses, kGlobalClasses and the ring of the long global classes.  The initialisers are parsed
     from the kernel sources: a class added or changed there without the stand-ins fails here."""
-    out, _ = run("asan", "host_parity", "tables")
+    out = run("host_parity", "asan", "tables")
     lines = [l.split() for l in out.stdout.splitlines()]
 
     def src(name):
@@ -140,7 +120,7 @@ def test_parity_through_the_host_path(san, mode):
     (ref), bsw_refbatch_* (wire), ksw_extend2 from 8 threads (scalar): equal to the oracle byte for byte, n in {0, 1, 63, 64, 65,
     5 000}, kernel AUTO / LANE / WAVE, 150 and 250 bp reads with Ns and junk, registered and pageable memory, variants H, M, RTL;
     chunk_tasks = 256, so 5 000 seeds are 20 chunks."""
-    out, _ = run(san, "host_parity", mode)
+    out = run("host_parity", san, mode)
     assert (mode + ":") in out.stdout
 
 
@@ -148,7 +128,7 @@ def test_parity_through_the_host_path(san, mode):
 def test_large_resident_batch_reaches_the_n_list(kernel):
     """120 000 two-sided 250 bp seeds as one resident batch.  Under AUTO such a chunk is what nsplit_candidate admits: the launch_bin
     stand-in must have seen an N list that ends behind order[4n+16), the capacity the header used to document."""
-    out, _ = run("asan", "host_parity", "big", str(kernel))
+    out = run("host_parity", "asan", "big", str(kernel))
     m = re.search(r"big: kernel (\d+), n (\d+), N list ends at (\d+), 4n\+16 = (\d+), beyond (\d+)", out.stdout)
     assert m, out.stdout
     if kernel == 0:
@@ -166,7 +146,7 @@ def test_parity_on_2_3_and_8_devices(san, tmp_path):
         dd.mkdir()
         (dd / "numa_node").write_text("%d\n" % (d % 2))
         (dd / "local_cpulist").write_text("%d\n" % min(os.sched_getaffinity(0)))      # one CPU this process may run on
-    out, _ = run(san, "host_parity", "devices", env={"BSW_SYSFS_PCI": str(tmp_path)})
+    out = run("host_parity", san, "devices", env={"BSW_SYSFS_PCI": str(tmp_path)})
     assert "devices: ok" in out.stdout
 
 
@@ -181,7 +161,7 @@ def test_every_single_hip_failure_in_three_submits(san, part):
     the release: call k of the clean run's C fails, for every k (this case: k = part mod 4).  Every wait returns, the ticket that
     met the failure answers BSW_E_NOMEM / BSW_E_HIP with a text that names the step, every other ticket is bit-exact, nothing stays
     in flight, the context stays usable (a return code never kills it; only the watchdog does), bsw_destroy returns, nothing leaks."""
-    out, _ = run(san, "host_faults", "sweep", str(part), str(PARTS))
+    out = run("host_faults", san, "sweep", str(part), str(PARTS))
     m = re.search(r"C = (\d+), injection points visited = (\d+), fired = (\d+) .* skipped 0", out.stdout)
     assert m, out.stdout[-1500:]
     C, visited, fired = (int(x) for x in m.groups())
@@ -193,7 +173,7 @@ def test_every_single_hip_failure_in_three_submits(san, part):
 def test_every_single_hip_failure_in_construction(san, mode):
     """bsw_create on three devices / bsw_ref_upload on three devices with call k failing, k = 1 .. C: a refused construction unwinds
     completely; a context created without its optional part (fork events, chain flags, placement) computes bit-exact results."""
-    out, _ = run(san, "host_faults", mode)
+    out = run("host_faults", san, mode)
     m = re.search(r"C = (\d+), injection points visited = (\d+)", out.stdout)
     assert m and int(m.group(1)) == int(m.group(2)) and int(m.group(1)) > (20 if mode == "create" else 5), out.stdout[-800:]
 
@@ -203,7 +183,7 @@ def test_every_single_hip_failure_in_construction(san, mode):
 def test_watchdog_marks_only_its_context_dead(san):
     """timeout_ms = 300 and a stalled stream: the waiting call (resident upload; ticket wait) answers BSW_E_HIP "timeout", later
     calls say the context is dead, a third context of the process computes bit-exact results, bsw_destroy returns."""
-    out, _ = run(san, "host_watchdog", "stall")
+    out = run("host_watchdog", san, "stall")
     assert "watchdog: ok" in out.stdout
 
 
@@ -212,7 +192,7 @@ def test_chain_timeouts_counts_expired_waits(selftest):
     """bsw_chain_timeouts: with BSW_CHAIN_SELFTEST=1 (a target no count reaches) exactly the number of waits the chain queued,
     otherwise at most that (a stand-in raises its flag when its launch is done, which may be later than the wait's 20 ms).
     Results do not change."""
-    out, _ = run("asan", "host_watchdog", "chain", env={"BSW_CHAIN_SELFTEST": "1"} if selftest else None)
+    out = run("host_watchdog", "asan", "chain", env={"BSW_CHAIN_SELFTEST": "1"} if selftest else None)
     m = re.search(r"chain: (\d+) waits queued, (\d+) expired", out.stdout)
     assert m and int(m.group(1)) > 0 and (int(m.group(2)) == int(m.group(1)) if selftest else int(m.group(2)) <= int(m.group(1))), out.stdout
 
@@ -225,7 +205,7 @@ def test_tickets_from_many_threads(san, mode, debug_timing):
     """The threading contract of include/bwa_sw_mi355.h: 8 threads submit / bsw_test / bsw_wait_ticket on one context while a ninth
     calls bsw_wait and bsw_inflight (storm); a ticket collected by bsw_wait while another thread waits on it answers BSW_E_INVAL
     or its own code and never touches freed memory (collide).  Once more with BSW_DEBUG_TIMING=1 and stderr discarded."""
-    out, _ = run(san, "host_tickets", mode, env={"BSW_DEBUG_TIMING": "1"} if debug_timing else None, quiet_stderr=debug_timing)
+    out = run("host_tickets", san, mode, env={"BSW_DEBUG_TIMING": "1"} if debug_timing else None, quiet_stderr=debug_timing)
     assert (mode + ":") in out.stdout
 
 
@@ -234,7 +214,7 @@ def test_tickets_from_many_threads(san, mode, debug_timing):
 def test_plan_batch_stays_inside_the_documented_order_capacity(switches):
     """bsw_plan_batch under AUTO with more than 100 000 two-sided 250 bp seeds and order[] malloc'ed with exactly the capacity the
     header documents; ASan is the witness (seg[] does not describe the N list).  The switches are read once per process."""
-    out, _ = run("asan", "asan_plan", "big", env=switches)
+    out = run("asan_plan", "asan", "big", env=switches)
     assert "asan_plan big ok" in out.stdout
     lens = [(int(a), int(b), int(c)) for a, b, c in re.findall(r"n (\d+), order_len (\d+), 4n\+16 = (\d+)", out.stdout)]
     assert len(lens) == 3
@@ -327,7 +307,7 @@ def test_f4_hosts_parity(san, oracle, tmp_path):
     bytes.  The workload's reach is asserted on the expectations: status 1, both strands, the no-gap shortcut with one and two
     tries, retry loops of 1, 2 and 3 tries, CIGAR and MD overflow, cigars == NULL, md == NULL."""
     path = str(tmp_path / "f4.txt")
-    out, _ = run(san, "host_f4", "f4", path)
+    out = run("host_f4", san, "f4", path)
     assert re.search(r"f4: 12 cases", out.stdout), out.stdout
     f = F4File(path)
     assert len(f.cigar) == 2 * (6 + 4) and len(f.mate) == 12
@@ -365,7 +345,7 @@ def test_f4_hosts_across_a_sub_batch_bound(which, oracle, tmp_path):
     the first D with the oracle (global, align) or hands them over (CIGAR, mate rescue: compared here).  Every call must have
     made at least two sub-batches."""
     path = str(tmp_path / "split.txt")
-    out, _ = run("asan", "host_f4", "f4split", which, path)
+    out = run("host_f4", "asan", "f4split", which, path)
     m = re.search(r"f4split %s: sub-batches global (\d+) align (\d+) cigar (\d+) matesw (\d+)" % which, out.stdout)
     assert m, out.stdout[-800:]
     assert all(int(x) >= 2 for x in m.groups()), out.stdout[-300:]
@@ -391,7 +371,7 @@ def test_scalar_queue_groups_of_three_kinds(san):
     """12 threads call ksw_global2, ksw_global, ksw_align2, ksw_align and ksw_extend2 at once under three scorings (one trip holds
     several groups of each kind); a 13th keeps calling ksw_align2 with a 2 000-base query.  Everyone but the offender gets the
     oracle's answer every time, the offender gets score -1, and bsw_scalar_stats shows fewer trips than calls."""
-    out, _ = run(san, "host_f4", "f4scalar", quiet_stderr=True)
+    out = run("host_f4", san, "f4scalar", quiet_stderr=True)
     m = re.search(r"f4scalar: (\d+) calls in (\d+) trips, offender calls (\d+)", out.stdout)
     assert m and int(m.group(2)) < int(m.group(1)) and int(m.group(3)) >= 3, out.stdout
 
@@ -401,7 +381,7 @@ def test_byte_mode_tasks_the_align_hosts_reject():
     bsw_align_batch, bsw_matesw_ref_batch, ksw_align2 and ksw_align: the code, a text that names KSW_XBYTE, the reason and the
     task; the scalar calls answer score -1.  The same batches in 16-bit mode, a smallest entry of 0 and sums of 255 in 8-bit mode
     run and equal the oracle (ASan)."""
-    out, _ = run("asan", "host_f4", "rejects", quiet_stderr=True)
+    out = run("host_f4", "asan", "rejects", quiet_stderr=True)
     assert re.search(r"rejects: 4 cases refused, 4 ran", out.stdout), out.stdout
 
 
@@ -412,7 +392,7 @@ def test_every_single_hip_failure_in_an_f4_batch_call(san, call):
     the call answers BSW_E_NOMEM / BSW_E_HIP with a text (a release whose code is ignored by design: success and exact results),
     the same call repeated on the same context is bit-exact, bsw_destroy returns, nothing leaks.  The cigar batch runs up to three
     tries, so failures inside the retry loop are reached."""
-    out, _ = run(san, "host_f4", "faults", call)
+    out = run("host_f4", san, "faults", call)
     m = re.search(r"faults %s: C = (\d+), injection points visited = (\d+), failed calls (\d+), ignored releases (\d+), skipped 0" % call, out.stdout)
     assert m and int(m.group(1)) == int(m.group(2)) and int(m.group(1)) >= 40 and int(m.group(3)) >= 36, out.stdout[-800:]
 
@@ -424,6 +404,6 @@ def test_the_sub_batch_cutter_on_made_up_costs(san):
     under a work target closes at the first task boundary at or past the target and not before; each of the five hard bounds
     (tasks, backtrack bytes, sequence bytes, list entries, output bytes) and the work target closes spans on its own — the
     sequence-byte bound too, which no batch of the other programs reaches; n = 0 yields no span, one task over every cap one."""
-    out, _ = run(san, "host_f4", "cuts")
+    out = run("host_f4", san, "cuts")
     m = re.search(r"cuts: ok, (\d+) spans, closed by tasks (\d+) z (\d+) seq (\d+) bl (\d+) out (\d+) work (\d+)", out.stdout)
     assert m and all(int(x) >= 20 for x in m.groups()), out.stdout[-600:]

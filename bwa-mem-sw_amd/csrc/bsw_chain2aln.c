@@ -304,3 +304,21 @@ int bsw_c2a_replay_planned(const bsw_params *p, const bsw_c2a_opt *opt, const bs
     *n_regs = rc ? 0 : total;
     return rc;
 }
+
+/* ---- for the device replay (bsw_c2a_device.hip); not part of the C ABI ---- */
+/* bsw_chain2aln_replay's pass over the arrays under another name, with the text */
+__attribute__((visibility("hidden")))
+int bsw_c2a_check_arrays(const char *who, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds, size_t n_seeds, const int32_t *lens,
+                         size_t n_reads, char *err, size_t err_cap)
+{
+    if (err && err_cap) err[0] = 0;
+    return c2a_check(who, chains, n_chains, seeds, n_seeds, lens, n_reads, err, err_cap);
+}
+/* the host's loop over chains[c0, c1) — whole reads — into regs[0 .. *n_regs); indices in the regions are global; extended[] (may be
+ * NULL) is only added to */
+__attribute__((visibility("hidden")))
+int bsw_c2a_replay_chains(const bsw_params *p, const bsw_c2a_opt *o, const bsw_chain *chains, size_t c0, size_t c1, const bsw_cseed *seeds,
+                          const int32_t *lens, const void *results, size_t stride, bsw_creg *regs, size_t *n_regs, uint8_t *extended)
+{
+    return c2a_replay_range(p, o, chains, c0, c1, seeds, lens, results, stride, regs, n_regs, extended, NULL);
+}

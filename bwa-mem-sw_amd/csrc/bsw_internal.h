@@ -12,6 +12,7 @@
  *   bsw_reads.hip   the resident read store: upload, free, info (its submits live with their pointer forms in the three files above)
  *   bsw_reads_async.hip  the asynchronous upload: the reads cross as they lie and bsw_reads_pack_kernel packs them on the GPU
  *   bsw_chain2aln_job.hip  mem_chain2aln as one job of the pipeline: plan (bsw_chain2aln.c) + extension submit, then wait + replay
+ *   bsw_c2a_device.hip  the replay of mem_chain2aln's loop on the GPU: the companion's launcher table, the switch, chunks, both calls
  *   bsw_sdp_job.hip  mem_sort_dedup_patch as a job around the patch tickets: the engine (bsw_sdp.c) + one patch submit per round
  * Everything here has hidden visibility: the shared object exports the C ABI only.
  */
@@ -272,8 +273,10 @@ struct f4_bufs {
     hbuf<uint8_t> h_back;             /* pinned: what a slot's chunk reads back (scores per try, then results, CIGARs, MD) */
     hbuf<uint8_t> h_in;               /* pinned: the records a slot's chunk builds on the host (alignment / CIGAR tasks, order lists) —
                                          the slot's DMAs never read a vector of a function that may return first (watchdog) */
+    dbuf<uint8_t> c2a;                /* the chain2aln replay's arena (bsw_c2a_device.hip): records, seeds, result records, regions, counts, flags */
     void release()
     {
+        c2a.release();
         g_tasks.release(); g_z.release(); g_cig.release(); g_order.release(); g_res.release();
         a_tasks.release(); a_bl.release(); a_res.release();
         c_tasks.release(); c_res.release(); c_md.release();
@@ -486,6 +489,20 @@ inline int align_long_snapshot()
     const int m = o ? o->mode() : 0;
     return m == 1 || m == 2 ? m : 0;
 }
+/* ---- bsw_c2a_device.hip: the replay of mem_chain2aln's seed loop on the GPU.  Its kernel lives in the companion library
+ * libbwasw_c2a.so, which hands this table (bsw_c2a_core.h) over when it is loaded; a program without the companion keeps NULL. ---- */
+struct c2a_dev_ops;
+BSW_LOCAL void c2a_dev_register(const c2a_dev_ops *ops);
+BSW_LOCAL const c2a_dev_ops *c2a_dev_registered();
+/* ---- bsw_chain2aln_job.hip: the job never refers to bsw_c2a_device.hip.  That unit registers this table when the library is
+ * loaded; a program linked without it (the host-double programs of before the device replay) keeps NULL: the switch reads as off. ---- */
+struct c2a_job_ops {
+    int (*on)();                      /* bsw_c2a_device() */
+    int (*submit)(bsw_ctx *ctx, const bsw_params *p, const bsw_c2a_opt *opt, const bsw_chain *chains, size_t n_chains, const bsw_cseed *seeds, size_t n_seeds,
+                  const int32_t *lens, size_t n_reads, const void *results, int result_format, bsw_creg *regs, size_t *n_regs, uint8_t *extended,
+                  uint64_t *reg_start, bsw_c2a_dev_stats *stats, bsw_ticket *ticket);      /* bsw_chain2aln_replay_submit_t */
+};
+BSW_LOCAL void c2a_job_register(const c2a_job_ops *ops);
 /* the class of a task behind the ncls classes of bsw_align_kernel, -1: the register kernel takes it (al_mode: the snapshot) */
 inline int align_long_route(int al_mode, int qlen, bool byte_mode)
 {

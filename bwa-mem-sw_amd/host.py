@@ -71,6 +71,8 @@ CREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("s
                  ("seed", "<u4")])
 C2A_OPT = np.dtype([("seedlen0_frac", "<f8"), ("ovl_len_frac", "<f8")])
 C2A_STATS = np.dtype([("seeds_gpu", "<u8"), ("seeds_bwa", "<u8"), ("regs", "<u8"), ("chains", "<u8"), ("reads", "<u8")])
+C2A_DEV_STATS = np.dtype([("reads_gpu", "<u8"), ("reads_host", "<u8"), ("chunks", "<u8"), ("h2d_bytes", "<u8"), ("d2h_bytes", "<u8")])
+C2A_DEV_MAX_CHAIN = 512        # BSW_C2A_DEV_MAX_CHAIN: a read with a longer chain is replayed on the host
 assert CSEED.itemsize == 24 and CHAIN.itemsize == 40 and CREG.itemsize == 64 and C2A_OPT.itemsize == 16 and C2A_STATS.itemsize == 40
 # mem_sort_dedup_patch (bsw_sdp_*): the fields of a region it reads or writes, its options and its counts
 SREG = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("truesc", "<i4"), ("w", "<i4"),
@@ -211,6 +213,14 @@ def lib():
             "bsw_chain2aln_test": (C.c_int, [vp]),
             "bsw_chain2aln_finish": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp, vp]),
             "bsw_chain2aln_stats": (C.c_int, [vp, vp]),
+            "bsw_c2a_device_register": (C.c_int, [vp]),
+            "bsw_c2a_device_load": (C.c_int, [C.c_char_p]),
+            "bsw_c2a_device_error": (C.c_char_p, []),
+            "bsw_set_c2a_device": (C.c_int, [C.c_int]),
+            "bsw_c2a_device": (C.c_int, []),
+            "bsw_chain2aln_replay_batch": (C.c_int, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, C.c_int, vp, C.POINTER(sz), vp, vp, vp]),
+            "bsw_chain2aln_replay_submit_t": (C.c_int, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, C.c_int, vp, C.POINTER(sz), vp, vp, vp,
+                                                        C.POINTER(C.c_uint64)]),
             "bsw_sdp_default_opt": (None, [vp]),
             "bsw_sdp_from_cregs": (C.c_int, [vp, sz, vp]),
             "bsw_sdp_open": (C.c_int, [vp, vp, C.c_int64, vp, sz, vp, vp, sz, C.POINTER(vp), C.c_char_p, sz]),
@@ -259,6 +269,8 @@ def lib():
 
 EXPORTS = ["bsw_c2a_default_opt", "bsw_chain2aln_plan", "bsw_chain2aln_replay", "bsw_chain2aln_ref_start", "bsw_chain2aln_reads_start",
            "bsw_chain2aln_test", "bsw_chain2aln_finish", "bsw_chain2aln_stats",
+           "bsw_c2a_device_register", "bsw_c2a_device_load", "bsw_c2a_device_error", "bsw_set_c2a_device", "bsw_c2a_device",
+           "bsw_chain2aln_replay_batch", "bsw_chain2aln_replay_submit_t",
            "bsw_sdp_default_opt", "bsw_sdp_from_cregs", "bsw_sdp_open", "bsw_sdp_needs", "bsw_sdp_feed", "bsw_sdp_collect", "bsw_sdp_close",
            "bsw_sdp_ref_start", "bsw_sdp_reads_start", "bsw_sdp_test", "bsw_sdp_finish", "bsw_sdp_job_stats",
            "ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
@@ -796,6 +808,15 @@ class BswContext:
         self._jobs.add(job)
         return job
 
+    def submit_chain2aln_replay(self, params, chains, seeds, lens, results, opt=None, want_extended=True):
+        """chain2aln_replay_batch as a ticket (bsw_chain2aln_replay_submit_t).  Returns (ticket, C2aReplay); once the ticket is
+        collected, C2aReplay.result() gives (CREG array, extended or None, reg_start, stats dict)."""
+        r = C2aReplay(params, chains, seeds, lens, results, opt, want_extended)
+        t = C.c_uint64(0)
+        self._chk(lib().bsw_chain2aln_replay_submit_t(self.handle, *r.args(), C.byref(t)), "bsw_chain2aln_replay_submit")
+        self._keep_alive(t.value, r)
+        return t.value, r
+
     # mem_sort_dedup_patch as a job around the patch tickets
     def sdp_start(self, params, ref, regs, reg_start, rd=None, reads=None, opt=None):
         """bsw_sdp_reads_start (rd: a resident block) or bsw_sdp_ref_start (reads: a list of uint8 code arrays).  regs: SREG array
@@ -892,7 +913,10 @@ class Chain2alnJob:
         h, self.handle = self.handle, None
         if h and self.ctx.handle:                           # (a context that is closed has released its jobs itself)
             n = C.c_size_t(0)
-            lib().bsw_chain2aln_finish(h, None, C.byref(n), None, None, None)      # waits; frees the job whatever it returns
+            # waits; frees the job whatever it returns but BSW_E_BUSY (a device replay in flight that found no place: the job is intact)
+            if lib().bsw_chain2aln_finish(h, None, C.byref(n), None, None, None) == -6:
+                self.handle = h
+                return
         self._keep = None
 
     def __enter__(self):
@@ -927,12 +951,17 @@ class Chain2alnJob:
         start = np.zeros(self.n_reads + 1, dtype=np.uint64)
         st = np.zeros(1, dtype=C2A_STATS)
         n = C.c_size_t(0)
-        h, self.handle = self.handle, None                  # finish frees the job whatever it returns
+        h, self.handle = self.handle, None                  # finish frees the job whatever it returns ...
         try:
             self.ctx._chk(lib().bsw_chain2aln_finish(h, regs.ctypes.data, C.byref(n), ext.ctypes.data, start.ctypes.data, st.ctypes.data),
                           "bsw_chain2aln_finish")
+        except BswError as err:
+            if err.code == -6:                              # ... but BSW_E_BUSY (the device replay found no place): call again
+                self.handle = h
+            raise
         finally:
-            self._keep = None
+            if self.handle is None:
+                self._keep = None
         return regs[:n.value], ext[:self.n_seeds], start, {k: int(st[k][0]) for k in C2A_STATS.names}
 
 
@@ -979,6 +1008,59 @@ def chain2aln_replay(params, chains, seeds, lens, results, opt=None):
     if rc:
         raise BswError(rc, "bsw_chain2aln_replay")
     return regs[:n.value], ext[:len(seeds)], start
+
+
+class C2aReplay:
+    """the arrays of one device replay: they stay alive, and where they are, until the call has returned or the ticket is collected"""
+
+    def __init__(self, params, chains, seeds, lens, results, opt, want_extended):
+        self.params = params
+        self.chains, self.seeds = np.ascontiguousarray(chains, dtype=CHAIN), np.ascontiguousarray(seeds, dtype=CSEED)
+        self.lens = np.ascontiguousarray(lens, dtype=np.int32)
+        self.results = np.ascontiguousarray(results)
+        assert self.results.dtype in (RESULT, PAIR) and len(self.results) == len(self.seeds)
+        self.o = c2a_opt(**(opt or {}))
+        self.regs = np.zeros(max(len(self.seeds), 1), dtype=CREG)
+        self.ext = np.zeros(max(len(self.seeds), 1), dtype=np.uint8) if want_extended else None
+        self.start = np.zeros(len(self.lens) + 1, dtype=np.uint64)
+        self.n = C.c_size_t(0)
+        self.st = np.zeros(1, dtype=C2A_DEV_STATS)
+
+    def args(self):
+        return (self.params.ctypes.data, self.o.ctypes.data, self.chains.ctypes.data, len(self.chains), self.seeds.ctypes.data, len(self.seeds),
+                self.lens.ctypes.data, len(self.lens), self.results.ctypes.data, RESULT_PAIR if self.results.dtype == PAIR else RESULT_FULL,
+                self.regs.ctypes.data, C.byref(self.n), self.ext.ctypes.data if self.ext is not None else None, self.start.ctypes.data,
+                self.st.ctypes.data)
+
+    def result(self):
+        return (self.regs[:self.n.value], self.ext[:len(self.seeds)] if self.ext is not None else None, self.start,
+                {k: int(self.st[k][0]) for k in C2A_DEV_STATS.names})
+
+
+def chain2aln_replay_batch(ctx, params, chains, seeds, lens, results, opt=None, want_extended=True):
+    """bsw_chain2aln_replay_batch: chain2aln_replay on the GPU, on the context's own lane (needs c2a_device_load) ->
+    (CREG array, extended or None, reg_start, stats dict of C2A_DEV_STATS)"""
+    r = C2aReplay(params, chains, seeds, lens, results, opt, want_extended)
+    ctx._chk(lib().bsw_chain2aln_replay_batch(ctx.handle, *r.args()), "bsw_chain2aln_replay_batch")
+    return r.result()
+
+
+def c2a_device_load(path=None):
+    """bsw_c2a_device_load: the companion library with the replay kernel (None: libbwasw_c2a.so next to the main library)"""
+    rc = lib().bsw_c2a_device_load(path.encode() if path else None)
+    if rc:
+        raise BswError(rc, (lib().bsw_c2a_device_error() or b"").decode())
+
+
+def set_c2a_device(on):
+    """bsw_set_c2a_device: chain2aln jobs started from now on replay on the GPU (refused without a loaded companion)"""
+    rc = lib().bsw_set_c2a_device(1 if on else 0)
+    if rc:
+        raise BswError(rc, (lib().bsw_c2a_device_error() or b"").decode())
+
+
+def c2a_device():
+    return int(lib().bsw_c2a_device())
 
 
 def sdp_opt(**over):

@@ -825,6 +825,52 @@ int      bsw_chain2aln_test(bsw_c2a_job *job);
 int      bsw_chain2aln_finish(bsw_c2a_job *job, bsw_creg *regs, size_t *n_regs, uint8_t *extended, uint64_t *reg_start, bsw_c2a_stats *stats);
 int      bsw_chain2aln_stats(const bsw_c2a_job *job, bsw_c2a_stats *stats);
 
+/* ---- the replay on the GPU (opt-in; off unless asked for).  bsw_chain2aln_replay's loop as a kernel, one 16-lane row per read: the
+ * kernel lives in a COMPANION library, libbwasw_c2a.so next to this one, which links against this library and hands it a launcher
+ * when it is loaded; every entry point is here.  regs, n_regs, extended and reg_start are byte for byte bsw_chain2aln_replay's.
+ *   bsw_c2a_device_load(path)   dlopen the companion (NULL: libbwasw_c2a.so in this library's own directory).  BSW_OK (also when a
+ *                               launcher is registered already), or BSW_E_INVAL when the file or its registration is missing: the
+ *                               text is bsw_c2a_device_error()'s (process-wide; the call has no context; a diagnostic that is
+ *                               NOT thread-safe: read it from the thread that made the failing call, with no other load or switch call beside it).
+ *   bsw_c2a_device_register     what the companion's constructor calls: INTERNAL to the pair of libraries.
+ *   bsw_set_c2a_device(on) / bsw_c2a_device()   a process-wide switch, initially BSW_C2A_DEVICE=1 (which implies one
+ *                               bsw_c2a_device_load(NULL) attempt on first use).  Turning it on without a registered launcher is
+ *                               refused with BSW_E_INVAL and leaves it off.  A chain2aln job reads it ONCE, at start, in the caller's thread.
+ *   bsw_chain2aln_replay_batch  synchronous, on the context's own lane (BSW_E_BUSY while any ticket is uncollected).  It needs a
+ *                               registered launcher (BSW_E_INVAL) but not the switch.  The arrays are checked first, with
+ *                               bsw_chain2aln_replay's codes; results may be pageable, registered memory is DMA'd where it lies.
+ *   bsw_chain2aln_replay_submit_t   the same as a ticket: one ticket space and BSW_MAX_INFLIGHT with every other submit, chunk k on
+ *                               device k mod n; every array (the outputs and stats included) stays the ticket's until it is
+ *                               collected.  A failed ticket leaves *n_regs 0.
+ * Chunks are ranges of chains cut between two reads, sized in seeds (BSW_C2A_DEV_CHUNK overrides the size: tests, measurements); a
+ * read with a chain of more than 512 seeds (BSW_C2A_DEV_MAX_CHAIN) is replayed by the host routine on the thread that runs its
+ * chunk and merged into place.  Per chunk the chain records, the seeds and the result records go up (32 or 96 bytes per seed
+ * AGAIN: DESIGN.md §9) and 4 bytes per read, 64 per region and, when extended is asked for, 1 per seed come back.
+ * With the switch on, a chain2aln job replays through such a ticket: bsw_chain2aln_test never blocks — once the extension ticket is
+ * complete it collects it and submits the replay ticket (BSW_E_BUSY there is not test's error: it answers 0 and tries again on the
+ * next call) and answers 1 when the replay ticket is complete.  bsw_chain2aln_finish does the same blocking; BSW_E_BUSY from it
+ * means the BSW_MAX_INFLIGHT places are taken by other tickets: THE JOB STAYS INTACT and the caller calls again (bsw_sdp_finish's
+ * contract); every other answer frees the job as before.  While either ticket is in flight the job is one submit, never two. ---- */
+typedef struct bsw_c2a_dev_stats {
+    uint64_t reads_gpu;              /* reads with a chain that the kernel replayed */
+    uint64_t reads_host;             /* reads with a chain above BSW_C2A_DEV_MAX_CHAIN seeds: replayed on the host */
+    uint64_t chunks;
+    uint64_t h2d_bytes, d2h_bytes;
+} bsw_c2a_dev_stats;
+int      bsw_c2a_device_register(const void *ops);
+int      bsw_c2a_device_load(const char *path);
+const char *bsw_c2a_device_error(void);
+int      bsw_set_c2a_device(int on);
+int      bsw_c2a_device(void);
+int      bsw_chain2aln_replay_batch(bsw_ctx *ctx, const bsw_params *p, const bsw_c2a_opt *opt, const bsw_chain *chains, size_t n_chains,
+                                    const bsw_cseed *seeds, size_t n_seeds, const int32_t *lens, size_t n_reads, const void *results,
+                                    int result_format, bsw_creg *regs, size_t *n_regs, uint8_t *extended, uint64_t *reg_start,
+                                    bsw_c2a_dev_stats *stats);
+int      bsw_chain2aln_replay_submit_t(bsw_ctx *ctx, const bsw_params *p, const bsw_c2a_opt *opt, const bsw_chain *chains, size_t n_chains,
+                                       const bsw_cseed *seeds, size_t n_seeds, const int32_t *lens, size_t n_reads, const void *results,
+                                       int result_format, bsw_creg *regs, size_t *n_regs, uint8_t *extended, uint64_t *reg_start,
+                                       bsw_c2a_dev_stats *stats, bsw_ticket *ticket);
+
 /* ---- mem_patch_reg (bwamem.c of bwa >= 0.7.10, restated AS RECALLED: bwa's source is not in this tree) against the resident
  * reference: may two regions a, b of one read be joined into one?  Pre-tests on the host (strand, colinearity, the band and
  * ratio limits), bwa_gen_cigar2 with n_cigar = 0, cigar = 0 — the SCORE of the banded global alignment of read[a.qb, b.qe)

@@ -94,6 +94,46 @@ def _M(H, E, F, i, j, mat, t, q):
     return H[i - 1][j - 1] + mat[t[i - 1]][q[j - 1]]
 
 
+def banded_global_dp(query, target, mat, o_del, e_del, o_ins, e_ins, w, m=5):
+    """Independent BANDED global affine-gap alignment score, the second opinion for oracle/ksw_global_ref.c when its band
+    binds: global_dp's recurrence (gaps open from M only, mat[target][query]) on the cells (i, j) of the (tlen + 1) x (qlen + 1)
+    matrix with |i - j| <= w, the borders included (the first row reaches column w, the first column row w); every other cell
+    is NEG.  Row-vectorised in numpy: a gap opens from M only, so F along a row does not depend on the row's own H and is a
+    running maximum, F(i, j) = max_{k < j} (M(i, k) + k e_ins) - o_ins - j e_ins.  Defined for w >= |qlen - tlen| only (below
+    that the last cell is outside the band and bwa's result is unspecified): raises ValueError there."""
+    q = np.asarray(query, dtype=np.int64)
+    t = np.asarray(target, dtype=np.int64)
+    mat = np.asarray(mat, dtype=np.int64).reshape(m, m)
+    ql, tl = len(q), len(t)
+    if w < abs(ql - tl):
+        raise ValueError("banded_global_dp: the band %d does not reach the last cell of %d x %d" % (w, tl, ql))
+    cols = np.arange(ql + 1, dtype=np.int64)
+    H = np.full(ql + 1, NEG, dtype=np.int64)               # row 0: a leading insertion, inside the band
+    top = min(w, ql)
+    H[:top + 1] = -(o_ins + e_ins * cols[:top + 1])
+    H[0] = 0
+    M = np.full(ql + 1, NEG, dtype=np.int64)               # M(i, j): the path ends with a (mis)match at (i, j)
+    M[0] = 0                                               # the corner opens both leading gaps
+    E = np.full(ql + 1, NEG, dtype=np.int64)               # ends with a deletion (consumes target)
+    for i in range(1, tl + 1):
+        lo, hi = max(0, i - w), min(ql, i + w)             # the row's cells: columns lo .. hi
+        Mn = np.full(ql + 1, NEG, dtype=np.int64)
+        En = np.full(ql + 1, NEG, dtype=np.int64)
+        Hn = np.full(ql + 1, NEG, dtype=np.int64)
+        a = max(lo, 1)                                     # the cells right of the border column: a .. hi
+        if a <= hi:
+            Mn[a:hi + 1] = H[a - 1:hi] + mat[t[i - 1]][q[a - 1:hi]]
+            En[a:hi + 1] = np.maximum(E[a:hi + 1] - e_del, M[a:hi + 1] - o_del - e_del)
+            run = np.maximum.accumulate(Mn[lo:hi] + e_ins * cols[lo:hi])          # over k = lo .. j - 1
+            F = np.full(hi + 1 - a, NEG, dtype=np.int64)
+            F[lo + 1 - a:] = run - o_ins - e_ins * cols[lo + 1:hi + 1]
+            Hn[a:hi + 1] = np.maximum(np.maximum(Mn[a:hi + 1], En[a:hi + 1]), F)
+        if lo == 0:                                        # the border: a leading deletion
+            Hn[0] = En[0] = -(o_del + e_del * i)
+        H, M, E = Hn, Mn, En
+    return int(H[ql])
+
+
 def local_dp(query, target, mat, o_del, e_del, o_ins, e_ins, m=5):
     """Textbook Gotoh LOCAL alignment (second opinion for ksw_align): whole matrices, row-vectorised in numpy.
     E (gap along the target, "deletion") and F (gap along the query, "insertion") may follow each other freely —

@@ -39,6 +39,61 @@ def general_matrix(rng, off_hi=9):
             return m
 
 
+GLOBAL_PENS = [(5, 2, 7, 1), (11, 3, 4, 2), (0, 2, 1, 1), (3, 1, 9, 4)]   # (o_del, e_del, o_ins, e_ins): insertion != deletion in both
+
+
+def global_pair(rng, ql, lmax=None, drift=6, sub=0.08, indel=0.10, nrate=0.03, junk=0.2):
+    """A (query, target) pair for ksw_global2 whose narrow bands bind: a query of ql codes 0..4 read with many indels off a target
+    of ql +- drift bases (mutate's skips of 1..11 bases move the path off the diagonal), or with probability `junk` unrelated
+    to it; with lmax the junk target has any length 0..lmax, so |qlen - tlen| is large too.  N (code 4) at rate nrate in both."""
+    if rng.random() < junk:
+        tl = int(rng.integers(0, lmax + 1)) if lmax is not None else max(0, ql + int(rng.integers(-drift, drift + 1)))
+        t = rng.integers(0, 4, tl).astype(np.uint8)
+        q = rng.integers(0, 4, ql).astype(np.uint8)
+    else:
+        tl = max(0, ql + int(rng.integers(-drift, drift + 1)))
+        if lmax is not None:
+            tl = min(tl, lmax)
+        t = rng.integers(0, 4, tl).astype(np.uint8)
+        q = mutate(rng, t, ql, sub, indel)
+    q[rng.random(ql) < nrate] = 4
+    t[rng.random(tl) < nrate] = 4
+    return q, t
+
+
+def extremes_matrix(rng):
+    """The matrix of test_gpu_global_long.test_general_matrix_extremes_and_ns: entries from {-128, -127, -1, 0, 1, 126, 127},
+    the diagonal 126 / 127, N against N -128."""
+    mat = rng.choice(np.array([-128, -127, -1, 0, 1, 126, 127], dtype=np.int8), 25)
+    for k in range(5):
+        mat[k * 5 + k] = 127 if k % 2 else 126
+    mat[4 * 5 + 4] = -128
+    return mat
+
+
+def limit_matrix():
+    """a = 127 on the four base diagonals, -128 everywhere else (N against N too): the value limits of an int8 matrix"""
+    mat = np.full((5, 5), -128, dtype=np.int8)
+    for k in range(4):
+        mat[k, k] = 127
+    return mat.ravel()
+
+
+def clean_gap_pair(rng, n, gap, deletion, at=None):
+    """n bases of codes 0..2 against themselves with one block of `gap` bases of code 3 put into the target (deletion) or into
+    the query: the block is the only place the extra bases can go without losing a match.  Returns (query, target)."""
+    s = rng.integers(0, 3, n).astype(np.uint8)
+    at = n // 2 if at is None else at
+    long = np.concatenate([s[:at], np.full(gap, 3, np.uint8), s[at:]])
+    return (s, long) if deletion else (long, s)
+
+
+def clean_gap_cigar(n, gap, deletion, at=None):
+    """the one alignment of clean_gap_pair that keeps every match: [(op, len), ...] with 0 = M, 1 = I, 2 = D"""
+    at = n // 2 if at is None else at
+    return [(op, ln) for op, ln in ((0, at), (2 if deletion else 1, gap), (0, n - at)) if ln]
+
+
 def random_seeds(rng, n, qmin=1, qmax=140, tfac=2.0, sub=0.03, indel=0.01, junk=0.2, nrate=0.0, h0max=60,
                  both_sides=True, tmin=0):
     """List of seed dicts for host.make_tasks()."""

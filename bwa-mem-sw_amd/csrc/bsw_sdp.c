@@ -340,6 +340,24 @@ int bsw_sdp_feed(bsw_sdp_eng *e, const bsw_presult *res, size_t n)
     return BSW_OK;
 }
 
+/* what is left of a walked read, in bwa's order, to out[] (which may be a itself) -> how many */
+static size_t survivors(const bsw_sreg *a, size_t n, bsw_sreg *out, uint64_t *dups)
+{
+    size_t k, m, at = 0;
+    if (n <= 1) {
+        if (n) out[at++] = a[0];
+        return at;
+    }
+    for (k = 0; k < n; ++k)
+        if (a[k].qe > a[k].qb) out[at++] = a[k];
+    sort_regs(out, at, by_score);
+    for (k = m = 0; k < at; ++k) {                              /* against the neighbour, marked or not: the first of a run stays */
+        if (k > 0 && out[k].score == out[k - 1].score && out[k].rb == out[k - 1].rb && out[k].qb == out[k - 1].qb) { ++*dups; continue; }
+        out[m++] = out[k];                                      /* (m <= k: out[k] itself stays in place for the next comparison) */
+    }
+    return m;
+}
+
 int bsw_sdp_collect(bsw_sdp_eng *e, bsw_sreg *out, size_t *n_out, uint64_t *out_start, bsw_sdp_stats *stats)
 {
     size_t r, at = 0;
@@ -347,22 +365,9 @@ int bsw_sdp_collect(bsw_sdp_eng *e, bsw_sreg *out, size_t *n_out, uint64_t *out_
     if (!e || !e->finished || (!out && e->n_regs)) return BSW_E_INVAL;
     e->st.dups = 0;
     for (r = 0; r < e->n_reads; ++r) {
-        const bsw_sreg *a = e->a + e->start[r];
-        const size_t n = (size_t)(e->start[r + 1] - e->start[r]), lo = at;
-        size_t k, m;
+        const size_t n = (size_t)(e->start[r + 1] - e->start[r]);
         if (out_start) out_start[r] = at;
-        if (n <= 1) {
-            if (n) out[at++] = a[0];
-            continue;
-        }
-        for (k = 0; k < n; ++k)
-            if (a[k].qe > a[k].qb) out[at++] = a[k];
-        sort_regs(out + lo, at - lo, by_score);
-        for (k = m = lo; k < at; ++k) {                         /* against the neighbour, marked or not: the first of a run stays */
-            if (k > lo && out[k].score == out[k - 1].score && out[k].rb == out[k - 1].rb && out[k].qb == out[k - 1].qb) { ++e->st.dups; continue; }
-            out[m++] = out[k];                                  /* (m <= k: out[k] itself stays in place for the next comparison) */
-        }
-        at = m;
+        if (n) at += survivors(e->a + e->start[r], n, out + at, &e->st.dups);
     }
     if (out_start) out_start[e->n_reads] = at;
     e->st.regs_out = at;
@@ -377,6 +382,30 @@ __attribute__((visibility("hidden"))) int bsw_sdp_peek_stats(const bsw_sdp_eng *
     if (!e || !stats) return BSW_E_INVAL;
     *stats = e->st;
     return BSW_OK;
+}
+
+/* One read's pass with patch = 0 in place, for mem_matesw's call inside the rescue loop (bsw_rescue.c): the order of a[] on entry
+ * is the order behind both sorts' ties; src is carried along untouched (src_tmp: n values of scratch).  -> the regions left */
+__attribute__((visibility("hidden"))) size_t bsw_sdp_pass0(float mask_level_redun, int32_t max_chain_gap, bsw_sreg *a, size_t n, uint32_t *src_tmp)
+{
+    bsw_sdp_eng e;
+    sdp_read rd;
+    uint64_t start[2], dups = 0;
+    size_t k;
+    if (n <= 1) return n;                                       /* returned untouched, n_comp included */
+    memset(&e, 0, sizeof(e));
+    memset(&rd, 0, sizeof(rd));
+    e.opt.mask_level_redun = mask_level_redun; e.opt.max_chain_gap = max_chain_gap;
+    start[0] = 0; start[1] = n;
+    e.a = a; e.start = start; e.rd = &rd; e.n_regs = n; e.n_reads = 1;
+    rd.held = -1; rd.i = 1;
+    for (k = 0; k < n; ++k) { src_tmp[k] = a[k].src; a[k].src = (uint32_t)k; }
+    sort_regs(a, n, by_re);
+    for (k = 0; k < n; ++k) a[k].n_comp = 1;
+    (void)advance(&e, 0);                                       /* patch = 0: no pair is asked for, the walk never stalls */
+    n = survivors(a, n, a, &dups);
+    for (k = 0; k < n; ++k) a[k].src = src_tmp[a[k].src];
+    return n;
 }
 
 void bsw_sdp_close(bsw_sdp_eng *e)

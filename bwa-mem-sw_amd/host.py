@@ -81,6 +81,14 @@ SDP_OPT = np.dtype([("mask_level_redun", "<f4"), ("max_chain_gap", "<i4"), ("pat
 SDP_STATS = np.dtype([(k, "<u8") for k in ("reads", "regs_in", "regs_out", "merges", "kills_p", "kills_q", "dups", "rounds", "tasks_first",
                                            "tasks", "alns_bwa")])
 assert SREG.itemsize == 64 and SDP_OPT.itemsize == 16 and SDP_STATS.itemsize == 88
+# the mate-rescue loop of mem_sam_pe (bsw_rescue_*): the contig table, its options (mem_pestat_t and the mem_opt_t fields it reads), its counts
+CONTIG = np.dtype([("offset", "<i8"), ("len", "<i8")])
+RESCUE_OPT = np.dtype([("low", "<i4", (4,)), ("high", "<i4", (4,)), ("failed", "<i4", (4,)), ("pen_unpaired", "<i4"), ("max_matesw", "<i4"),
+                       ("min_seed_len", "<i4"), ("a", "<i4"), ("mask_level_redun", "<f4"), ("max_chain_gap", "<i4")])
+RESCUE_STATS = np.dtype([(k, "<u8") for k in ("pairs", "anchors", "rounds", "tasks_first", "tasks", "alns_bwa", "pushed", "regs_in", "regs_out",
+                                              "late")])
+RESCUE_NEW = 0x80000000
+assert CONTIG.itemsize == 16 and RESCUE_OPT.itemsize == 72 and RESCUE_STATS.itemsize == 80
 # how the reads of a block are encoded at its upload (BSW_READS_*): codes 0..4, FASTQ letters, 4-bit words
 READS_CODES, READS_ASCII, READS_PACKED = 0, 1, 2
 MAX_DEVICES = 16
@@ -233,6 +241,19 @@ def lib():
             "bsw_sdp_test": (C.c_int, [vp]),
             "bsw_sdp_finish": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp]),
             "bsw_sdp_job_stats": (C.c_int, [vp, vp]),
+            "bsw_rescue_default_opt": (None, [vp]),
+            "bsw_rescue_open": (C.c_int, [vp, vp, C.c_int64, vp, sz, vp, sz, vp, vp, sz, C.POINTER(vp), C.c_char_p, sz]),
+            "bsw_rescue_needs": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz)]),
+            "bsw_rescue_feed": (C.c_int, [vp, vp, sz]),
+            "bsw_rescue_collect": (C.c_int, [vp, vp, C.POINTER(sz), vp, vp, vp]),
+            "bsw_rescue_out_capacity": (sz, [vp]),
+            "bsw_rescue_close": (None, [vp]),
+            "bsw_rescue_ref_start": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, C.POINTER(vp)]),
+            "bsw_rescue_reads_start": (C.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(vp)]),
+            "bsw_rescue_test": (C.c_int, [vp]),
+            "bsw_rescue_finish": (C.c_int, [vp, vp, sz, C.POINTER(sz), vp, vp, vp]),
+            "bsw_rescue_job_stats": (C.c_int, [vp, vp]),
+            "bsw_rescue_job_out_capacity": (sz, [vp]),
             "bsw_infer_bw": (C.c_int, [C.c_int] * 6),
             "bsw_matesw_ref_batch": (C.c_int, [vp, vp, vp, vp, sz, vp]),
             "bsw_infer_dir": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
@@ -273,6 +294,9 @@ EXPORTS = ["bsw_c2a_default_opt", "bsw_chain2aln_plan", "bsw_chain2aln_replay", 
            "bsw_chain2aln_replay_batch", "bsw_chain2aln_replay_submit_t",
            "bsw_sdp_default_opt", "bsw_sdp_from_cregs", "bsw_sdp_open", "bsw_sdp_needs", "bsw_sdp_feed", "bsw_sdp_collect", "bsw_sdp_close",
            "bsw_sdp_ref_start", "bsw_sdp_reads_start", "bsw_sdp_test", "bsw_sdp_finish", "bsw_sdp_job_stats",
+           "bsw_rescue_default_opt", "bsw_rescue_open", "bsw_rescue_needs", "bsw_rescue_feed", "bsw_rescue_collect", "bsw_rescue_out_capacity",
+           "bsw_rescue_close", "bsw_rescue_ref_start", "bsw_rescue_reads_start", "bsw_rescue_test", "bsw_rescue_finish", "bsw_rescue_job_stats",
+           "bsw_rescue_job_out_capacity",
            "ksw_global2", "ksw_global", "bsw_global_batch", "bsw_cigar_ref_batch", "bsw_infer_bw", "bsw_matesw_ref_batch",
            "bsw_cigar_ref_submit_t", "bsw_matesw_ref_submit_t",
            "bsw_patch_ref_batch", "bsw_patch_ref_submit_t", "bsw_patch_reads_submit_t", "bsw_patch_pretest", "bsw_patch_decide",
@@ -846,6 +870,37 @@ class BswContext:
         self._jobs.add(job)
         return job
 
+    # mem_sam_pe's mate-rescue loop as a job around the rescue tickets
+    def rescue_start(self, params, ref, regs, reg_start, rd=None, reads=None, contigs=None, opt=None):
+        """bsw_rescue_reads_start (rd: a resident block) or bsw_rescue_ref_start (reads: a list of uint8 code arrays); reads 2k and
+        2k + 1 are mates.  regs: SREG array sorted by read (what SdpJob.finish gives), reg_start: uint64[n_reads + 1], contigs: a
+        CONTIG array or (offset, len) pairs (None: no table), opt: fields of RESCUE_OPT (low / high / failed: four values each).
+        Returns a RescueJob."""
+        regs, reg_start = np.ascontiguousarray(regs, dtype=SREG), np.ascontiguousarray(reg_start, dtype=np.uint64)
+        o, ct = rescue_opt(**(opt or {})), contig_table(contigs)
+        h = C.c_void_p()
+        keep = [params, regs, reg_start, o, ct]
+        if rd is not None:
+            n_reads = self.reads_info(rd)["n_reads"]
+            assert len(reg_start) == n_reads + 1
+            rc = lib().bsw_rescue_reads_start(self.handle, params.ctypes.data, o.ctypes.data, ref, rd, ct.ctypes.data, len(ct), regs.ctypes.data,
+                                              len(regs), reg_start.ctypes.data, C.byref(h))
+        else:
+            arrs = [np.ascontiguousarray(r, dtype=np.uint8) for r in reads]
+            ptrs = np.array([r.ctypes.data if len(r) else 0 for r in arrs], dtype=np.uint64)
+            lens = np.array([len(r) for r in arrs], dtype=np.int32)
+            assert len(reg_start) == len(arrs) + 1
+            keep += [arrs, ptrs, lens]
+            rc = lib().bsw_rescue_ref_start(self.handle, params.ctypes.data, o.ctypes.data, ref, ptrs.ctypes.data, lens.ctypes.data, len(arrs),
+                                            ct.ctypes.data, len(ct), regs.ctypes.data, len(regs), reg_start.ctypes.data, C.byref(h))
+            n_reads = len(arrs)
+        self._chk(rc, "bsw_rescue_start")
+        job = RescueJob(self, h, n_reads, keep)
+        if not hasattr(self, "_jobs"):
+            self._jobs = weakref.WeakSet()
+        self._jobs.add(job)
+        return job
+
     def align_batch(self, params, atasks):
         """Batched ksw_align2 (bwa's local alignment of mate rescue).  Returns a KSWR array."""
         res = np.zeros(len(atasks), dtype=KSWR)
@@ -1198,6 +1253,151 @@ class SdpJob:
             self.handle, self._keep = None, None
         self.ctx._chk(rc, "bsw_sdp_finish")
         return out[:n.value], start, _sdp_stats(st)
+
+
+def rescue_opt(**over):
+    """bsw_rescue_default_opt (every orientation failed, bwa's other defaults), with fields replaced: low / high / failed take
+    four values each"""
+    o = np.zeros(1, dtype=RESCUE_OPT)
+    lib().bsw_rescue_default_opt(o.ctypes.data)
+    for k, v in over.items():
+        o[k] = v
+    return o
+
+
+def contig_table(contigs):
+    """-> a CONTIG array from None, a CONTIG array or (offset, len) pairs"""
+    if contigs is None:
+        return np.zeros(0, dtype=CONTIG)
+    if isinstance(contigs, np.ndarray) and contigs.dtype == CONTIG:
+        return np.ascontiguousarray(contigs)
+    return np.array([(int(o), int(n)) for o, n in contigs], dtype=CONTIG)
+
+
+def _rescue_stats(st):
+    return {k: int(st[k][0]) for k in RESCUE_STATS.names}
+
+
+class RescueEngine:
+    """One bsw_rescue_eng (pure host): needs() -> RD_MTASK array (a copy; empty: every direction is finished), feed(MRESULT array of
+    exactly those tasks), collect() -> (SREG array, out_start, n_sw int32[n_reads / 2], stats dict).  Raises BswError with open's text."""
+
+    def __init__(self, params, l_pac, regs, reg_start, lens, contigs=None, opt=None):
+        regs, reg_start = np.ascontiguousarray(regs, dtype=SREG), np.ascontiguousarray(reg_start, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        o, ct = rescue_opt(**(opt or {})), contig_table(contigs)
+        self.handle, self.n_reads = C.c_void_p(), len(lens)
+        err = C.create_string_buffer(400)
+        rc = lib().bsw_rescue_open(params.ctypes.data, o.ctypes.data, l_pac, ct.ctypes.data, len(ct), regs.ctypes.data, len(regs),
+                                   reg_start.ctypes.data, lens.ctypes.data, len(lens), C.byref(self.handle), err, 400)
+        if rc:
+            self.handle = None
+            raise BswError(rc, err.value.decode())
+
+    def out_capacity(self):
+        return int(lib().bsw_rescue_out_capacity(self.handle))
+
+    def needs(self):
+        t, n = C.c_void_p(), C.c_size_t(0)
+        rc = lib().bsw_rescue_needs(self.handle, C.byref(t), C.byref(n))
+        if rc:
+            raise BswError(rc, "bsw_rescue_needs")
+        if not n.value:
+            return np.zeros(0, dtype=RD_MTASK)
+        return np.frombuffer(C.string_at(t.value, n.value * RD_MTASK.itemsize), dtype=RD_MTASK).copy()
+
+    def feed(self, results):
+        results = np.ascontiguousarray(results, dtype=MRESULT)
+        rc = lib().bsw_rescue_feed(self.handle, results.ctypes.data, len(results))
+        if rc:
+            raise BswError(rc, "bsw_rescue_feed")
+
+    def collect(self):
+        out = np.zeros(max(self.out_capacity(), 1), dtype=SREG)
+        start = np.zeros(self.n_reads + 1, dtype=np.uint64)
+        n_sw = np.zeros(self.n_reads // 2, dtype=np.int32)
+        st = np.zeros(1, dtype=RESCUE_STATS)
+        n = C.c_size_t(0)
+        rc = lib().bsw_rescue_collect(self.handle, out.ctypes.data, C.byref(n), start.ctypes.data, n_sw.ctypes.data, st.ctypes.data)
+        if rc:
+            raise BswError(rc, "bsw_rescue_collect")
+        return out[:n.value].copy(), start, n_sw, _rescue_stats(st)
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            lib().bsw_rescue_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RescueJob:
+    """One bsw_rescue_job: test() polls and moves the job on a round, finish() waits for the remaining rounds, returns the regions
+    and frees the job.  A job dropped without finish() is released as an SdpJob is."""
+
+    def __init__(self, ctx, handle, n_reads, keep):
+        self.ctx, self.handle, self.n_reads, self._keep = ctx, handle, n_reads, keep
+
+    def release(self):
+        h, self.handle = self.handle, None
+        if h and self.ctx.handle:
+            n = C.c_size_t(0)
+            if lib().bsw_rescue_finish(h, None, 0, C.byref(n), None, None, None) == -6:     # BSW_E_BUSY: the job is intact, the places are others'
+                self.handle = h
+                return
+        self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def test(self):
+        rc = lib().bsw_rescue_test(self.handle)
+        if rc < 0:
+            self.ctx._chk(rc, "bsw_rescue_test")
+        return bool(rc)
+
+    def stats(self):
+        s = np.zeros(1, dtype=RESCUE_STATS)
+        rc = lib().bsw_rescue_job_stats(self.handle, s.ctypes.data)
+        if rc:
+            raise BswError(rc, "bsw_rescue_job_stats")
+        return _rescue_stats(s)
+
+    def out_capacity(self):
+        return int(lib().bsw_rescue_job_out_capacity(self.handle))
+
+    def finish(self):
+        """-> (SREG array, out_start uint64[n_reads + 1], n_sw int32[n_reads / 2], stats dict).  BswError BSW_E_BUSY leaves the job
+        intact: collect a ticket, call again."""
+        out = np.zeros(max(self.out_capacity(), 1), dtype=SREG)
+        start = np.zeros(self.n_reads + 1, dtype=np.uint64)
+        n_sw = np.zeros(self.n_reads // 2, dtype=np.int32)
+        st = np.zeros(1, dtype=RESCUE_STATS)
+        n = C.c_size_t(0)
+        rc = lib().bsw_rescue_finish(self.handle, out.ctypes.data, len(out), C.byref(n), start.ctypes.data, n_sw.ctypes.data, st.ctypes.data)
+        if rc != -6:                                        # finish has freed the job
+            self.handle, self._keep = None, None
+        self.ctx._chk(rc, "bsw_rescue_finish")
+        return out[:n.value].copy(), start, n_sw, _rescue_stats(st)
 
 
 class HostArena:

@@ -39,6 +39,8 @@
  *                              is extended as one job of the pipeline, bwa's loop is replayed on the host (bwa host software)
  *   bsw_sdp_*_start,           mem_sort_dedup_patch (bwa 0.7.12 - 0.7.17, as recalled): the sort, the redundancy test, the merges through
  *   bsw_sdp_finish             mem_patch_reg and the removal of duplicates, as a job around the patch tickets; both sorts stable
+ *   bsw_rescue_*_start,        mem_sam_pe's mate-rescue loop with mem_matesw inside it (bwa 0.7.12 - 0.7.17, as recalled): the anchors,
+ *   bsw_rescue_finish          skip[], the contig clamp, the insertion and the sort-and-dedup pass, as a job around the rescue tickets
  *   bsw_cigar_ref_submit_t /   the three calls above as tickets of the streaming pipeline:
  *   bsw_matesw_ref_submit_t /  every device of the context, beside extension submits
  *   bsw_patch_ref_submit_t
@@ -284,7 +286,8 @@ int      bsw_host_unregister(void *p);
  *
  * THREADS.  bsw_submit*_t (and the forms without a ticket), bsw_cigar_ref_submit_t, bsw_matesw_ref_submit_t, bsw_patch_ref_submit_t, the four
  * *_reads_* submits (bsw_patch_reads_submit_t among them), bsw_reads_upload, bsw_reads_upload_enc, bsw_reads_upload_start, bsw_reads_upload_start_enc, bsw_reads_test,
- * bsw_reads_wait, bsw_reads_free, bsw_sdp_ref_start, bsw_sdp_reads_start, bsw_sdp_test, bsw_sdp_finish, bsw_sdp_job_stats (one job from one thread at a time),
+ * bsw_reads_wait, bsw_reads_free, bsw_sdp_ref_start, bsw_sdp_reads_start, bsw_sdp_test, bsw_sdp_finish, bsw_sdp_job_stats,
+ * bsw_rescue_ref_start, bsw_rescue_reads_start, bsw_rescue_test, bsw_rescue_finish, bsw_rescue_job_stats, bsw_rescue_job_out_capacity (one job from one thread at a time),
  * bsw_wait_ticket, bsw_test, bsw_wait and bsw_inflight may be called on ONE context from several threads at once, the first submit included;
  * every other call that takes the context (bsw_destroy, the synchronous and resident calls, bsw_ref_upload / bsw_ref_free,
  * bsw_host_stats, bsw_reads_image) needs it to itself.  bsw_set_align_long, bsw_align_long and bsw_align_long_stats take no
@@ -467,8 +470,8 @@ kswr_t ksw_align(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, con
 /* ---- mate rescue against a DEVICE-RESIDENT reference (bwa's mem_matesw, bwamem_pair.c): one ksw_align2 per window,
  * the window [rb, re) fetched on the GPU from the reference of bsw_ref_upload (bns_get_seq semantics, both strands), the
  * mate complemented and reversed on the GPU when is_rev.  Only the mates cross PCIe.  The whole batch runs on the context's
- * first device (bsw_matesw_ref_submit_t below: the same work as a ticket, over every device of the context).  mem_matesw's bookkeeping (which orientations to try, its order dependency) stays with the caller:
- * bsw_infer_dir and bsw_matesw_windows below, INTEGRATION.md "Mate rescue".  Kept (status 0) exactly when bwa keeps the
+ * first device (bsw_matesw_ref_submit_t below: the same work as a ticket, over every device of the context).  mem_matesw's bookkeeping (which orientations to try, its order dependency) is bsw_rescue_* further down, a job around
+ * these tickets; a host that keeps it to itself has bsw_infer_dir and bsw_matesw_windows below, INTEGRATION.md "Mate rescue".  Kept (status 0) exactly when bwa keeps the
  * region: aln.score >= min_score && aln.qb >= 0. ---- */
 typedef struct bsw_mtask {
     const uint8_t *mate;     /* the mate in READ order, codes 0..4 (bwa's ms)                                       */
@@ -507,8 +510,8 @@ int      bsw_matesw_ref_submit_t(bsw_ctx *ctx, const bsw_params *p, const struct
 int      bsw_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist);
 /* mem_matesw's windows for the four orientations r of an anchor at anchor_rb and a mate of l_ms bases, from the insert size
  * bounds low[r] / high[r] of bwa's mem_pestat_t: rb[r], re[r] clamped to [0, 2*l_pac) (the window may come out empty),
- * is_rev[r] = r>>1 != (r&1), skip[r] = failed[r] != 0.  The contig clamp of newer bwa's bns_fetch_seq and its rid check stay
- * with the caller.  Returns BSW_OK, or BSW_E_INVAL for NULL arrays, l_pac < 1 or l_ms < 0. */
+ * is_rev[r] = r>>1 != (r&1), skip[r] = failed[r] != 0.  The contig clamp of newer bwa's bns_fetch_seq and its rid check are not
+ * made here (bsw_rescue_* makes them).  Returns BSW_OK, or BSW_E_INVAL for NULL arrays, l_pac < 1 or l_ms < 0. */
 int      bsw_matesw_windows(int64_t anchor_rb, int l_ms, int64_t l_pac, const int32_t low[4], const int32_t high[4],
                             const int32_t failed[4], int64_t rb[4], int64_t re[4], int32_t is_rev[4], int32_t skip[4]);
 
@@ -1011,6 +1014,113 @@ int      bsw_sdp_reads_start(bsw_ctx *ctx, const bsw_params *p, const bsw_sdp_op
 int      bsw_sdp_test(bsw_sdp_job *job);
 int      bsw_sdp_finish(bsw_sdp_job *job, bsw_sreg *out, size_t *n_out, uint64_t *out_start, bsw_sdp_stats *stats);
 int      bsw_sdp_job_stats(const bsw_sdp_job *job, bsw_sdp_stats *stats);
+
+/* ---- the mate-rescue loop of mem_sam_pe with mem_matesw inside it (bwamem_pair.c of bwa 0.7.12 - 0.7.17, restated AS RECALLED:
+ * bwa's source is not in this tree), as a job around the rescue tickets above.
+ * BLOCK AND PAIRS.  Reads 2k and 2k+1 of the block are mates; n_reads is even.  INPUT: the regions of every read as
+ * bsw_sreg regs[n_regs] with reg_start[n_reads + 1] — what bsw_sdp_finish writes: bwa's order inside a read, score descending.
+ * DIRECTIONS.  For a pair and i in {0, 1}: the anchors come from read i, ma is a private copy of read !i's regions, the mate ms
+ * is read !i.  Direction i reads only the INITIAL regions of read i (bwa copies b[0] and b[1] before the first rescue) and
+ * mutates only a[!i]: the two directions of a pair are independent replays.
+ * ANCHORS.  Every j with regs[j].score >= regs[first of the read].score - pen_unpaired (a filter over all j, not a break), in
+ * input order, the first max_matesw of them.  A read without regions has no anchor.
+ * mem_matesw(anchor a, ma).  skip[r] = failed[r] != 0; for every region m of the current ma: r = bsw_infer_dir(l_pac, a.rb, m.rb,
+ * &dist), and low[r] <= dist <= high[r] sets skip[r] = 1; all four set: return 0.  skip[] is computed once per anchor, before
+ * its orientations.  Then for r = 0..3, not skipped: the window of bsw_matesw_windows; if rb < re the contig step below; the
+ * orientation RUNS when the contig step passed, re - rb >= min_seed_len after the clamp and the task's result is not status == 1.
+ * If it runs, ++n; if it runs with status == 0, b is built (rid = a.rid; rb / re / qb / qe / score / csub / seedcov from the
+ * bsw_mresult; truesc = w = sub = n_comp = 0) and inserted into ma in front of the first region with score < b.score, or at the
+ * end.  Then, inside the r loop, for every orientation that was not skipped, whether or not it ran: when n > 0,
+ * ma = mem_sort_dedup_patch with patch = 0 (mask_level_redun, max_chain_gap of the options) — bsw_sdp's own per-read pass with
+ * patch = 0, its two STABLE sorts on the order ma has at that moment; the TIES caveat of bsw_sdp_* above holds here verbatim: bwa's
+ * two sorts are ks_introsort, which is not stable, and of a full (score, rb, qb) tie the survivor may differ from bwa's in the
+ * fields outside the key (re, qe, w, seedcov, src, ...).  So ma shrinks as well as grows.
+ * CONTIG STEP (bns_fetch_seq).  mid = (rb + re) >> 1; fwd = mid >= l_pac ? 2*l_pac - 1 - mid : mid; rid' = the contig whose
+ * [offset, offset + len) holds fwd; the contig's interval on mid's strand is [offset, offset + len) when mid < l_pac and
+ * [2*l_pac - offset - len, 2*l_pac - offset) otherwise; rb is clamped up and re down to it; the step passes when rid' == a.rid.
+ * With n_contigs == 0 (a bwa-0.7.8 host) there is no clamp and no rid test: only the ticket's own status == 1 (a window that
+ * bridges l_pac) then keeps an orientation from running.
+ * TASK FIELDS.  xtra = KSW_XSUBO | KSW_XSTART | (l_ms * a < 250 ? KSW_XBYTE : 0) | (min_seed_len * a); min_score = min_seed_len.
+ * EXACTNESS AND ROUNDS.  A task's result depends only on (anchor, r, mate, contigs), never on ma: a held result is never stale,
+ * only WHETHER it is needed changes.  Round 1 asks for every (anchor, r) not skipped on the INITIAL ma whose clamped window
+ * passes the contig and length tests.  The replay uses a result only when bwa's loop reaches that (anchor, r).  A rescued region
+ * can make an initial region redundant and kill it; when that region was the only one that put a later anchor's orientation
+ * inside [low, high], the loop reaches an (anchor, r) it has no result for and the direction stalls.  The next needs asks for
+ * that (anchor, r), the rest of this anchor's orientations not in skip[], and for every later anchor every orientation not
+ * skipped under the CURRENT ma and not already held.  Every round resolves at least the stalling task and no (anchor, r) is
+ * ever asked twice, so it ends after at most 4 x anchors tasks per direction.
+ * OUTPUT.  Per read its final ma (out[], out_start[n_reads + 1]); for a read that no rescue touched, its input regions unchanged.
+ * src = the input index for an input region, BSW_RESCUE_NEW | the input index of the anchor for a rescued one (more than
+ * 2^31 - 1 regions: BSW_E_LIMIT).  n_sw[n_reads / 2] (may be NULL) = bwa's n per pair, summed over both directions. ---- */
+#define BSW_RESCUE_NEW 0x80000000u
+typedef struct bsw_contig {          /* bntann1_t: the contig covers [offset, offset + len) of the forward strand */
+    int64_t offset, len;
+} bsw_contig;                        /* 16 bytes */
+typedef struct bsw_rescue_opt {
+    int32_t low[4], high[4], failed[4];   /* mem_pestat_t per orientation */
+    int32_t pen_unpaired;            /* 17 */
+    int32_t max_matesw;              /* 50 */
+    int32_t min_seed_len;            /* 19 */
+    int32_t a;                       /* 1: the match score (xtra's KSW_XBYTE test and threshold) */
+    float   mask_level_redun;        /* .95f */
+    int32_t max_chain_gap;           /* 10000 */
+} bsw_rescue_opt;                    /* 72 bytes */
+typedef struct bsw_rescue_stats {
+    uint64_t pairs, anchors;
+    uint64_t rounds;                 /* submits the block needed */
+    uint64_t tasks_first, tasks;     /* windows sent in round 1 / in all rounds */
+    uint64_t alns_bwa;               /* orientations that run in bwa's sequential order (the sum of n_sw[]) */
+    uint64_t pushed;                 /* rescued regions inserted into some ma (before the pass that may remove them again) */
+    uint64_t regs_in, regs_out;
+    uint64_t late;                   /* tasks first asked after round 1: what a host that speculates once would have dropped */
+} bsw_rescue_stats;                  /* 80 bytes */
+/* Everything but the twelve pes values; ALL FOUR orientations are marked failed, so that a forgotten pes rescues nothing
+ * rather than something wrong. */
+void     bsw_rescue_default_opt(bsw_rescue_opt *o);
+/* The engine (pure host, no context), under the contracts of the bsw_sdp_* engine: the arrays are copied at open, everything
+ * is checked ONCE, by open, which names the first offender in err (may be NULL); p supplies nothing but is kept for the job;
+ * lens[read] = the read's length (l_ms of a task whose mate it is).  BSW_E_INVAL: what bsw_sdp_open refuses in a region or in
+ * reg_start; an odd n_reads; contigs that do not tile [0, l_pac) in ascending order; a rid outside the table when there is
+ * one; low[r] > high[r] for an orientation that has not failed; negative pen_unpaired, max_matesw or min_seed_len; a < 1;
+ * min_seed_len * a beyond 65535 (xtra's threshold is 16 bits).  BSW_E_LIMIT: more than 2^31 - 1 regions.
+ * bsw_rescue_needs returns the tasks it now needs (owned by the engine, valid until the next call; read = the mate); *n == 0:
+ * every direction is finished.  bsw_rescue_feed takes the results of exactly those tasks in that order (BSW_E_INVAL for another
+ * n).  bsw_rescue_collect (once *n == 0 was returned, BSW_E_INVAL before): out[] needs room for bsw_rescue_out_capacity(eng) =
+ * n_regs + 4 x anchors regions; out_start, n_sw and stats may be NULL.  One engine belongs to one thread at a time. */
+typedef struct bsw_rescue_eng bsw_rescue_eng;
+int      bsw_rescue_open(const bsw_params *p, const bsw_rescue_opt *opt, int64_t l_pac, const bsw_contig *contigs, size_t n_contigs,
+                         const bsw_sreg *regs, size_t n_regs, const uint64_t *reg_start, const int32_t *lens, size_t n_reads,
+                         bsw_rescue_eng **eng, char *err, size_t err_cap);
+int      bsw_rescue_needs(bsw_rescue_eng *eng, const bsw_rd_mtask **tasks, size_t *n);
+int      bsw_rescue_feed(bsw_rescue_eng *eng, const bsw_mresult *res, size_t n);
+int      bsw_rescue_collect(bsw_rescue_eng *eng, bsw_sreg *out, size_t *n_out, uint64_t *out_start, int32_t *n_sw, bsw_rescue_stats *stats);
+size_t   bsw_rescue_out_capacity(const bsw_rescue_eng *eng);     /* 0 for NULL */
+void     bsw_rescue_close(bsw_rescue_eng *eng);
+/* The engine as ONE JOB around the rescue tickets, under the contract of bsw_sdp_*_start / _test / _finish / _job_stats above word
+ * for word: start = open, the first needs, the tasks and results in DMA-able memory (bsw_host_alloc), bsw_matesw_ref_submit_t
+ * (bsw_rd_mtask turned into bsw_mtask with mate = reads[read], l_ms = lens[read]) / bsw_matesw_reads_submit_t.  A round is one
+ * of the context's BSW_MAX_INFLIGHT submits and runs over every device of the context.  A failed start leaves *job NULL and
+ * queues nothing (beside BSW_MAX_INFLIGHT submits: BSW_E_BUSY before anything is allocated); with nothing to submit the job is
+ * complete at once and holds no ticket.  regs[], reg_start[], lens[], contigs[] and the reads (the block) stay valid and
+ * unchanged until finish.  bsw_rescue_test never waits: 1 = finished, 0 = not yet (also when the follow-up submit answered
+ * BSW_E_BUSY), < 0 = the job has failed, and finish reports it.  bsw_rescue_finish waits until the engine has finished, writes
+ * collect's arrays (out_cap regions of room: bsw_rescue_job_out_capacity is always enough, fewer than the job's final count is
+ * BSW_E_INVAL) and frees the job WHATEVER it returns (job == NULL: BSW_E_INVAL), except that a follow-up round that finds no place
+ * answers BSW_E_BUSY with the job intact.  The limits are the rescue submit's own and fail the job with its text: a mate
+ * beyond BSW_ALIGN_MAX_QLEN bases without bsw_set_align_long, a window beyond BSW_MAX_TLEN.  The calls may come from several
+ * threads, one job from one thread at a time. */
+typedef struct bsw_rescue_job bsw_rescue_job;
+int      bsw_rescue_ref_start(bsw_ctx *ctx, const bsw_params *p, const bsw_rescue_opt *opt, const bsw_ref *ref, const uint8_t *const *reads,
+                              const int32_t *lens, size_t n_reads, const bsw_contig *contigs, size_t n_contigs, const bsw_sreg *regs,
+                              size_t n_regs, const uint64_t *reg_start, bsw_rescue_job **job);
+int      bsw_rescue_reads_start(bsw_ctx *ctx, const bsw_params *p, const bsw_rescue_opt *opt, const bsw_ref *ref, const bsw_reads *rd,
+                                const bsw_contig *contigs, size_t n_contigs, const bsw_sreg *regs, size_t n_regs, const uint64_t *reg_start,
+                                bsw_rescue_job **job);
+int      bsw_rescue_test(bsw_rescue_job *job);
+int      bsw_rescue_finish(bsw_rescue_job *job, bsw_sreg *out, size_t out_cap, size_t *n_out, uint64_t *out_start, int32_t *n_sw,
+                           bsw_rescue_stats *stats);
+int      bsw_rescue_job_stats(const bsw_rescue_job *job, bsw_rescue_stats *stats);
+size_t   bsw_rescue_job_out_capacity(const bsw_rescue_job *job); /* 0 for NULL */
 
 /* ---- device sequence format: 4 bits per base, 16 bases per uint64, base k of a word in bits [4k,4k+3];
  * codes > 4 are stored as 4 (N).  words must hold (len+15)/16 entries.  Returns 1 if an N was seen. ---- */
